@@ -15,6 +15,11 @@ IREC_DIST_BACKEND=gloo (test rigs with fewer GPUs than ranks) shares devices rou
 
 Prints ONE JSON line on rank 0.  Every figure in it is measured by this run or read from `profiles/` of the same
 source hash (roofline.traffic; null when the committed PMC profile is from other kernel sources).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  Everything else -- the socket power over the timed
+region, the decoder leg, the secondary configurations, the margins and skewed-K legs and the CPU baselines with their parity
+check -- runs only with --full.  --dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy
+(see dump_outputs); the inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -458,6 +463,34 @@ class PowerSampler:
         return {"power_w": means[i], "power_cap_w": cap, "samples": len(self.samples), "card": self.files[i].split("/")[4]}
 
 
+DUMP_LATENTS = 1024      # latents whose indices and sample --dump-outputs writes (a fixed, seeded choice when a step has more)
+
+
+def dump_outputs(dirname, lay, out, gathered, max_K):
+    """What a caller of the timed path receives from its last step, in the caller's (tensor, block) order rather than the
+    layout's row order, as float64 / float32 .npy files (about 40 MB at the default 65 536 latents):
+      K.npy                    [n_tensors, blocks_per_tensor]  partitions per block, every block of the step
+      code_nats.npy            [world * n_tensors]             code length per latent after the exchange
+      latent_ids.npy           [n]                             the latents of the two files below (all of them when n_tensors <= 1024)
+      indices.npy              [n, blocks_per_tensor, max_K]   the emitted indices of those latents' blocks, -1 beyond K
+      sample.npy               [n, dims]                       the encoder's sample of those latents"""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    L, bpt = lay.n_tensors, lay.blocks_per_tensor
+    rows = lay.natural.astype(np.int64).reshape(L, bpt)
+    K = out[0].cpu().numpy().astype(np.int64)
+    ids = np.arange(L) if L <= DUMP_LATENTS else np.sort(np.random.default_rng(SEED).choice(L, DUMP_LATENTS, replace=False))
+    idx = out[1].cpu().numpy()[rows[ids]].astype(np.float64)           # [n, bpt, max_K]
+    idx[np.arange(max_K)[None, None, :] >= K[rows[ids]][:, :, None]] = -1.0   # past K the buffer holds whatever was there
+    np.save(os.path.join(dirname, "K.npy"), K[rows].astype(np.float64))
+    np.save(os.path.join(dirname, "code_nats.npy"), gathered.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirname, "latent_ids.npy"), ids.astype(np.float64))
+    np.save(os.path.join(dirname, "indices.npy"), idx)
+    sample = out[2][torch.from_numpy(ids.astype(np.int64)).to(out[2].device)]
+    np.save(os.path.join(dirname, "sample.npy"), sample.cpu().numpy().astype(np.float32))
+    log(f"outputs of the last step written to {dirname} ({len(ids)} of {L} latents' indices and samples)")
+
+
 def run_rank_launch_only(args):
     """IREC_BENCH_LAUNCH_ONLY=1 (CPU test rigs, tests/test_bench_launcher.py): everything of the N-rank job except the GPU
     work -- rendezvous, the code-length exchange of irec/sharding.py over gloo on made-up K, max-over-ranks timing, the
@@ -492,6 +525,34 @@ def run_rank_launch_only(args):
                                      f"latents sharded over {world} rank(s), no data-path collective"}}), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def decoder_leg(eng, params, lay, q, out, dims, Kh):
+    """The batch just coded, decoded from its indices (outside the timed region): at the full size the round trip must be
+    exact (decode == the encoder's sample, bit for bit), and the decoder's own rate is reported."""
+    import torch
+    K, L = out[0], lay.n_tensors
+    samp_dec = eng.decode_blocks(params, lay, q[2], q[3], SEED, K, out[1])
+    torch.cuda.synchronize()
+    round_trip_exact = bool(torch.equal(samp_dec, out[2]))
+    # per-call events, median: the first call after `samp_dec` is held may pay the allocator's hipMalloc of a fresh output
+    dev_ = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+    dev_[0].record()
+    for i in range(5):
+        eng.decode_blocks(params, lay, q[2], q[3], SEED, K, out[1])
+        dev_[i + 1].record()
+    torch.cuda.synchronize()
+    decode_ms = sorted(dev_[i].elapsed_time(dev_[i + 1]) for i in range(5))[2]
+    assert round_trip_exact, "decode(encode) differs from the encoder's sample"
+    # decoder: its own roofline entry (SURVEY.md §8a12: 12 D + 4 K algorithmic bytes per block)
+    dec_bytes = int((12 * dims + 4 * Kh).sum())
+    return {"decode_round_trip_exact": round_trip_exact, "decode_ms": decode_ms, "decoded_latents_per_s": L / (decode_ms * 1e-3),
+            "decode_roofline": {"bound": "hbm", "achieved": dec_bytes / (decode_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+                                "unit": "GB/s", "frac": dec_bytes / (decode_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                "algorithmic_bytes": dec_bytes, "kernel_ms": decode_ms,
+                                "kernel": "decode_tensor_kernel<true,3> (whole tensors staged in LDS) + 2 x alpha_table_kernel",
+                                "note": "VALU-bound on the IEEE chain a = rho (var_p - c), sqrt, c += a of "
+                                        "beam_search_coder.py:131-147 (DESIGN.md §4)"}}
 
 
 def run_rank(args):
@@ -559,7 +620,7 @@ def run_rank(args):
     barrier()
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     power = None
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         try:
             pr = torch.cuda.get_device_properties(device)
             pci = f"{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}"
@@ -587,6 +648,8 @@ def run_rank(args):
 
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))   # table kernels + block kernel of one call
     log(f"rank {rank}: timed region {my_elapsed:.3f} s, {kernel_ms:.2f} ms per call (HIP events)")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lay, out, gathered, max_K)
     Kh = K.cpu().numpy().astype(np.int64)
     dims = lay.block_dim.cpu().numpy().astype(np.int64)
     assert Kh.min() >= 0 and Kh.max() <= max_K, "a block needed more than max_K partitions"
@@ -612,21 +675,6 @@ def run_rank(args):
         else:
             traffic_note = (f"profiles/traffic.json is for sources {tr.get('source_sha16')} / {tr.get('kernel')}; "
                             f"this build is {src_hash} / {plan['kernel']}: not reported")
-
-    # decoder leg (outside the timed region): the batch just coded is decoded from its indices -- at the full size the
-    # round trip must be exact (decode == the encoder's sample, bit for bit), and the decoder's own rate is reported
-    samp_dec = eng.decode_blocks(params, lay, q[2], q[3], SEED, K, out[1])
-    torch.cuda.synchronize()
-    round_trip_exact = bool(torch.equal(samp_dec, out[2]))
-    # per-call events, median: the first call after `samp_dec` is held may pay the allocator's hipMalloc of a fresh output
-    dev_ = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
-    dev_[0].record()
-    for i in range(5):
-        eng.decode_blocks(params, lay, q[2], q[3], SEED, K, out[1])
-        dev_[i + 1].record()
-    torch.cuda.synchronize()
-    decode_ms = sorted(dev_[i].elapsed_time(dev_[i + 1]) for i in range(5))[2]
-    assert round_trip_exact, "decode(encode) differs from the encoder's sample"
 
     result = {
         "metric": "encoded latents/sec", "value": world * L * args.steps / elapsed, "unit": "latents/s",
@@ -654,7 +702,7 @@ def run_rank(args):
                                  "note": "microbench_peak: the kernel's own address mixture and instruction stream at 12 waves per CU "
                                          "(scripts/microbench/bank_limits.hip, profiles/r05b); PMC fractions from profiles/traffic.json "
                                          "when it was taken on these sources, else null; power_w: socket power over the timed region "
-                                         "(amdgpu hwmon) -- the kernel runs the card at its cap, so 'achieved' per NOMINAL clock understates "
+                                         "(amdgpu hwmon; --full only, else null) -- the kernel runs the card at its cap, so 'achieved' per NOMINAL clock understates "
                                          "the rate per delivered clock (DESIGN.md 4)"},
                      "configs": []},
         "secondary": {"proposal_evals_per_s": evals / (kernel_ms * 1e-3), "n_cu": n_cu, "clock_ghz": clk_ghz,
@@ -666,21 +714,18 @@ def run_rank(args):
                       # assignment over three table copies, 8 waves per CU
                       "lds_gather_roofline": {"achieved": lookups, "peak": LDS_2CHOICE_LOOKUPS,
                                               "unit": "look-ups/clk/CU", "frac": lookups / LDS_2CHOICE_LOOKUPS},
-                      "mean_K": float(Kh.mean()), "code_nats_per_latent": float(gathered.mean().item()),
-                      "decode_round_trip_exact": round_trip_exact, "decode_ms": decode_ms,
-                      "decoded_latents_per_s": L / (decode_ms * 1e-3)},
+                      "mean_K": float(Kh.mean()), "code_nats_per_latent": float(gathered.mean().item())},
+        "full": args.full,
     }
-    # decoder: its own roofline entry (12 D + 4 K algorithmic bytes per block)
-    dec_bytes = int((12 * dims + 4 * Kh).sum())
-    result["secondary"]["decode_roofline"] = {"bound": "hbm", "achieved": dec_bytes / (decode_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
-                                              "unit": "GB/s", "frac": dec_bytes / (decode_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                              "algorithmic_bytes": dec_bytes, "kernel_ms": decode_ms,
-                                              "kernel": "decode_tensor_kernel<true,3> (whole tensors staged in LDS) + 2 x alpha_table_kernel",
-                                              "note": "VALU-bound on the IEEE chain a = rho (var_p - c), sqrt, c += a of "
-                                                      "beam_search_coder.py:131-147 (DESIGN.md §4)"}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    result["secondary"].update(decoder_leg(eng, params, lay, q, out, dims, Kh))
     if rank == 0 and world == 1 and not args.no_secondary:
         # BASELINE configs[3] and configs[4] (and the lossy settings on a latent batch), outside the timed region
-        del samp_dec
         torch.cuda.empty_cache()
         lossy = "examples/lossy/compress_with_lossy_model.py:120-124,222-227 (B = 10, Omega = 3, S = 20)"
         stress = "BASELINE.json configs[4] (ImageNet32 RVAE stress: B = 30, Omega = 5)"
@@ -751,11 +796,16 @@ def main():
                     "samples cannot miss it; the rate per latent is the same from 8192 latents up, profiles/archive/r03g/batch_size.log)")
     ap.add_argument("--cpu-ref-latents", type=int, default=20, help="latents per CPU-ref repeat (5 repeats, median)")
     ap.add_argument("--cpu-opt-seconds", type=float, default=8.0, help="time budget of the CPU-opt (OpenMP oracle) leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[3] / configs[4] runs after the timed region")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the power over the timed region, the decoder "
+                    "leg, the secondary configurations and the CPU baselines with their parity check (a plain run: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the configs[3] / configs[4] runs after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned in its last step to DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             return launch_ranks(args, sys.argv[1:])     # before anything touches a GPU

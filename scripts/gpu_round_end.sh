@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-end evidence on the GPU box: full GPU suite, the default bench line, rocprofv3 --kernel-trace --stats of the same bench
+# Round-end evidence on the GPU box: full GPU suite, the full bench line, rocprofv3 --kernel-trace --stats of the same bench
 # command, separate --pmc passes (LDS / VALU / HBM-side traffic) of the encoder, the 60-cell sweep grid.  Everything is
 # written under gpurun_out/$TAG/ as it goes (no output held back behind a pipe).
 set -u
@@ -22,7 +22,7 @@ for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_WAIT_INST_LDS" "GRBM_GUI_ACTIVE FETCH_SIZE" "WRITE_SIZE GRBM_COUNT"; do
   name=$(echo $set | tr ' ' '_' | cut -c1-40)
   echo "== pmc $name"
-  timeout -k 10 900 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/pmc_$name -- python3 bench.py --steps 2 --warmup 1 --latents $L --no-cpu-baseline --no-secondary > $O/pmc_$name.log 2>&1
+  timeout -k 10 900 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $O/pmc_$name -- python3 bench.py --steps 2 --warmup 1 --latents $L --full --no-cpu-baseline --no-secondary > $O/pmc_$name.log 2>&1
   f=$(find $O/pmc_$name -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && python3 scripts/pmc_summary.py "$f" encode_team | tee $O/pmc_$name.summary
   [ -n "$f" ] && python3 scripts/pmc_summary.py "$f" decode_tensor | tee -a $O/pmc_$name.summary
@@ -31,9 +31,9 @@ find $O -name "*.csv" -size +2M -delete
 python3 scripts/make_traffic_json.py $O $L encode_team > $O/traffic.json 2>&1 || true
 # the bench line is taken AFTER the PMC passes so that it carries roofline.traffic of exactly these sources (on the box's scratch copy)
 grep -q source_sha16 $O/traffic.json && cp $O/traffic.json profiles/traffic.json
-echo "== bench (default line)"; timeout -k 10 900 python bench.py --steps 20 --warmup 5 2> $O/bench_default.err > $O/bench_default.out; tail -1 $O/bench_default.out > $O/bench_default.log; grep -v amdgpu.ids $O/bench_default.err | tail -12
+echo "== bench (full line)"; timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 2> $O/bench_default.err > $O/bench_default.out; tail -1 $O/bench_default.out > $O/bench_default.log; grep -v amdgpu.ids $O/bench_default.err | tail -12
 echo "== kernel trace of the same command (no CPU baselines / secondary configs: the timed region is the same)"
-rm -rf $O/trace; timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/trace.log 2>&1
+rm -rf $O/trace; timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary > $O/trace.log 2>&1
 f=$(find $O/trace -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && python3 - "$f" $O/kernel_stats.csv <<'PY'
 import csv, sys

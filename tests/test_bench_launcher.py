@@ -77,7 +77,7 @@ def test_a_failing_rank_fails_the_job():
 
 @pytest.mark.gpu
 def test_two_ranks_on_one_gpu_over_gloo():
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--latents", "4096", "--no-cpu-baseline"],
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--latents", "4096", "--full", "--no-cpu-baseline"],
              {"IREC_DIST_BACKEND": "gloo"}, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -88,7 +88,7 @@ def test_two_ranks_on_one_gpu_over_gloo():
 
 @pytest.mark.gpu
 def test_single_rank_line_is_self_describing():
-    r = _run(["--steps", "2", "--warmup", "1", "--latents", "256", "--no-cpu-baseline"], {}, timeout=900)
+    r = _run(["--steps", "2", "--warmup", "1", "--latents", "256", "--full", "--no-cpu-baseline"], {}, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["roofline"]["kernel"] == "encode_team_kernel<20,3,1>"
@@ -111,8 +111,57 @@ def test_single_rank_line_is_self_describing():
 def test_rccl_code_path_with_a_world_of_one():
     """The collectives of the N-rank job (process group on RCCL, barrier, all_gather_into_tensor of the code lengths,
     all_gather of the rank times) executed for real over the nccl backend with one rank -- all a 1-GPU box can run."""
-    r = _run(["--steps", "2", "--warmup", "1", "--latents", "128", "--no-cpu-baseline"],
+    r = _run(["--steps", "2", "--warmup", "1", "--latents", "128", "--full", "--no-cpu-baseline"],
              {"IREC_BENCH_FORCE_DIST": "1", "IREC_DIST_BACKEND": "nccl"}, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["world_size"] == 1 and res["backend"] == "nccl" and res["value"] > 0
+
+
+def test_options_of_a_plain_and_a_full_run():
+    r = _run(["--help"], {}, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_outputs_of_its_last_step(tmp_path):
+    """A plain run: the headline only (no decoder leg, secondary configurations or CPU baselines), --steps timed steps, and
+    --dump-outputs writes what the timed path returned -- the same files from two runs of the same arguments, and what the
+    oracle computes for the dumped latents (1100 latents: the indices and samples of a seeded 1024 of them)."""
+    import numpy as np
+    import torch
+    import bench
+    from oracle import oracle as O
+    L, lines = 1100, []
+    for run in ("a", "b"):
+        r = _run(["--steps", "3", "--warmup", "1", "--latents", str(L), "--dump-outputs", str(tmp_path / run)], {}, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    res = lines[0]
+    assert res["metric"] == "encoded latents/sec" and res["unit"] == "latents/s" and res["higher_is_better"] is True
+    assert res["dtype"] == "f32" and res["steps"] == 3 and res["warmup"] == 1 and res["full"] is False
+    assert res["value"] > 0 and abs(res["ms_per_step"] - 1e3 * L / res["value"]) < 1e-6 * res["ms_per_step"]
+    assert "cpu_baseline" not in res and "decode_ms" not in res["secondary"] and res["roofline"]["configs"] == []
+    names = {"K", "code_nats", "latent_ids", "indices", "sample"}
+    assert {f.name for f in (tmp_path / "a").iterdir()} == {n + ".npy" for n in names}
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in names}
+    assert all(a[n].dtype in (np.float32, np.float64) and np.array_equal(a[n], b[n]) for n in names)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    ids = a["latent_ids"].astype(np.int64)
+    assert len(ids) == 1024 and len(np.unique(ids)) == 1024 and ids.max() < L
+    assert a["K"].shape == (L, 9) and a["code_nats"].shape == (L,) and a["indices"].shape == (1024, 9, 32)
+    assert a["sample"].shape == (1024, bench.N_DIMS)
+    # the dumped latents against the oracle, on the inputs the run drew (the bench's seeded generator on this device)
+    q = bench.synthetic_batch(L, torch.device("cuda", 0), 0)
+    pick = ids[[0, 1, 1023]]
+    hb = [t[torch.from_numpy(pick).cuda()].cpu().numpy() for t in q]
+    S = int(np.exp(bench.OMEGA * bench.EPS1))
+    ridx, rsamp, _ = O.encode_tensors_omp(*hb, bench.SEED, bench.OMEGA, S, bench.BEAMS, bench.BLOCK_SIZE, max_K=32, n_threads=4)
+    for n, i in enumerate(pick):
+        row = int(np.searchsorted(ids, i))
+        for j in range(9):
+            k = int(a["K"][i, j])
+            assert a["indices"][row, j, :k].astype(np.int64).tolist() == ridx[n][j] and (a["indices"][row, j, k:] == -1).all()
+        assert np.array_equal(a["sample"][row], rsamp[n].reshape(-1))
+    assert np.allclose(a["code_nats"][pick], a["K"][pick].sum(axis=1) * np.log(S))
