@@ -72,6 +72,23 @@ def test_host_helpers_match_oracle(oracle):
         assert np.array_equal(engine.tf_shuffle_perm(seed, n), oracle.tf_shuffle_perm(seed, n))
     for seed in (0, 42, 45, 2 ** 31 + 3):
         assert np.array_equal(engine.philox_uniform_int(seed, 4001), oracle.uniform_int(seed, 4001))
+    # coder.py:62-64 (tf.random.set_seed(seed); tf.random.shuffle(range(n))) with the seed pair the reference notebook's Bernoulli
+    # vector pins (tests/test_f64_referee.py: global seed 42, no op seed -> the first auto-seed): a forward Fisher-Yates driven by
+    # the raw uint32 Philox stream of that pair, whose float form (23 low bits) is the draw that reproduced the notebook's bits
+    s1, s2 = ctypes.c_uint64(), ctypes.c_uint64()
+    assert oracle.lib().irec_oracle_tf_get_seed(1, 42, 0, 0, 0, ctypes.byref(s1), ctypes.byref(s2)) == 0
+    s1, s2 = s1.value, s2.value
+
+    def u32(e):
+        return int(oracle.philox4x32([s1 & 0xFFFFFFFF, s1 >> 32], [e >> 2, 0, s2 & 0xFFFFFFFF, s2 >> 32])[e & 3])
+    floats = (np.array([u32(e) for e in range(100)], dtype=np.uint32) & np.uint32(0x7FFFFF) | np.uint32(0x3F800000)).view(np.float32) - 1
+    assert np.array_equal(floats, oracle.TfEagerRandom(42).uniform(100))
+    for n in (2, 100, 1000):
+        want = list(range(n))
+        for i in range(n - 1):
+            j = i + u32(i) % (n - i)
+            want[i], want[j] = want[j], want[i]
+        assert engine.tf_shuffle_perm(42, n).tolist() == want, n
     import irec
     lib = irec._lib.load()
     assert lib.irec_n_samples(3.0, 1.2) == 36 and lib.irec_n_samples(6.0, 1.0) == 403
