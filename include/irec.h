@@ -295,6 +295,54 @@ irec_status irec_beam_decode_tensors(irec_context *ctx, const irec_params *p, in
                                      const int32_t *indices, float *out_sample, void *workspace, size_t workspace_bytes,
                                      void *hip_stream);
 
+/* ---- the sequential importance coder: GaussianCoder(sampler=ImportanceSampler(coding_bits), alpha = inf) -----------------
+ * GaussianCoder.encode_block / decode_block (rec/coding/coder.py:493-584) driven the way GaussianCoder.encode / decode drive them
+ * (coder.py:412-491: the same seed for every block): per block K = ceil(KL / Omega) serial steps -- K - 1 auxiliary variables
+ * (ratio get_auxiliary_ratio(i), i = K-1 .. 1), then the block's sample -- each one encode_gaussian_importance_sample
+ * (importance_sampling.py:9-79) with seed + step, followed by the conditional update of target and coder (coder.py:157-171).
+ * A block emits max(K, 1) indices (a zero-KL block one, coder.py:548-557).  Arithmetic: DESIGN.md §3.
+ *
+ * The standard-normal proposals of step j are tf.random.normal([S, 1, D]) after tf.random.set_seed(seed + j): they depend on
+ * (seed + j, S, D) only, so every block of D dims reads the same S x D numbers at step j.  They pass through libm on the host
+ * (and through Eigen in TensorFlow), so they are DATA the kernels read, built by the caller -- like lut10007:
+ *   out[(j * dim + d) * S_pad + s] = element s * dim + d of the stream of seed + j,  j < steps, d < dim, s < n_samples,
+ *   S_pad = n_samples rounded up to IREC_NORMAL_TABLE_PAD (sample index fastest; the padding is zero).
+ * irec_normal_table_floats: floats of one table, or 0 (text in irec_last_error) for sizes out of range or a table of more than
+ * IREC_TABLE_BYTES_HARD bytes.  irec_normal_table_build: host memory, n_threads host threads (0: one per core, at most 16). */
+#define IREC_NORMAL_TABLE_PAD 16
+size_t irec_normal_table_floats(int32_t n_samples, int32_t dim, int32_t steps);
+irec_status irec_normal_table_build(int64_t seed, int32_t n_samples, int32_t dim, int32_t steps, float *out, int32_t n_threads);
+
+/* The tables of one call, on the device: table[i] serves the blocks of dim[i] dims (unused slots: NULL / 0), all built with the
+ * call's seed, n_samples = ceil(exp(coding_bits * log 2)) (irec_importance_n_samples) and `steps`. */
+typedef struct {
+  const float *table[4];
+  int32_t dim[4];
+  int32_t n_samples;
+  int32_t steps;
+} irec_normal_tables;
+
+/* Encode n_blocks blocks (layout arguments as irec_beam_encode; blocks of at most 1024 dims).  Asynchronous, no workspace.
+ *   max_K       index slots per row, 1 <= max_K <= tables->steps
+ *   out_K       [n_blocks] K = ceil(KL / kl_per_partition) of each block (the K of irec_block_kl).  K > max_K: not coded, call
+ *               again with a longer window; K > irec_max_partitions(ctx) (fitted ratios): not coded; -1: no table of the block's
+ *               dim, or more than 1024 dims
+ *   out_indices [n_blocks, max_K]: idx[t], t < max(K, 1), the sample chosen at step t (rest untouched)
+ *   out_sample  flat, indexed as the inputs (merged)
+ * Hand the blocks over longest first (by K): a workgroup codes one block at a time. */
+irec_status irec_gc_importance_encode(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
+                                      const int32_t *block_dim, const int32_t *perm, const float *q_loc, const float *q_scale,
+                                      const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
+                                      float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
+                                      float *out_sample, void *hip_stream);
+/* Decode: K [n_blocks], indices [n_blocks, max_K] in encoder order, max(K, 1) entries per row.  A row with K < 0, K > max_K,
+ * K > irec_max_partitions(ctx), an index outside [0, n_samples) or a dim without a table decodes to p_loc, as irec_beam_decode
+ * promises; any block dim with a table is served. */
+irec_status irec_gc_importance_decode(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
+                                      const int32_t *block_dim, const int32_t *perm, const float *p_loc, const float *p_scale,
+                                      const irec_normal_tables *tables, int32_t max_K, const int32_t *K, const int32_t *indices,
+                                      float *out_sample, void *hip_stream);
+
 /* ---- .rec wire format: entropy coder of the index streams (host memory; the reference's is CPU Cython too) ------------ */
 const char *irec_io_last_error(void);
 /* ArithmeticCoder(counts, precision).encode(message) -- rec/io/entropy_coding.pyx:51-121.  out_bits: one ASCII '0'/'1'

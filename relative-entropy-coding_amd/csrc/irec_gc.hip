@@ -1,0 +1,188 @@
+// irec_gc.hip -- the SEQUENTIAL iREC coder of the reference on the device: GaussianCoder.encode_block / decode_block with an
+// ImportanceSampler (rec/coding/coder.py:493-584 over rec/coding/importance_sampling.py:9-103), alpha = inf, gfx950 only.
+//
+// Arithmetic contract: DESIGN.md §3 "sequential importance coder".  float32, correctly rounded + - * / sqrt in the reference's
+// operator order, no contraction; the weight of a sample is the float64 sum of its float32 terms IN DIM ORDER, rounded once.
+// That order is kept by construction: one lane owns one (block, sample) pair and walks the dims serially -- no weight is ever
+// reduced across lanes; the only cross-lane step is the arg-max over a block's samples.
+//
+// The standard-normal proposals are DATA the kernels read (like the quantile table of the beam coder): built on the host by
+// irec_normal_table_build, tab[(t * D + d) * S_pad + s] = element s * D + d of tf.random.normal after set_seed(seed + t).
+// Lanes that own consecutive samples read consecutive floats.
+//
+// Shape: one workgroup per block at a time, blockDim = S rounded up to a wave (64 .. 1024 lanes; beyond 1024 samples a lane owns
+// several).  The block's (mu_q, sigma_q, mu_p, sigma_p) stay in LDS for all of its K steps.  Per step:
+//   (A) lanes over dims:    ts, tl / ts, c of the step's standardised target into LDS
+//   (B) lanes over samples: w[s] over d = 0 .. D-1 (constants as LDS broadcasts, table rows coalesced)
+//   (C) arg-max over the workgroup (DPP within a wave, LDS across waves): greatest w, first s on ties, a NaN never
+//   (D) lanes over dims:    the conditional update with A[d] = sqrt(a[d]) * x[j][d]
+#include <cfloat>
+
+#include "irec_device.h"
+#include "irec_kernels.h"
+
+namespace irec {
+
+namespace {
+
+constexpr float GC_HL2PI = 0.918938533204672742f;   // float32(0.5 * ln(2 pi))
+
+__device__ __forceinline__ int64_t gc_index(const GcArgs &A, int64_t base, int32_t pos, int d) {
+  return base + (A.perm ? (int64_t)A.perm[pos + d] : (int64_t)(pos + d));
+}
+__device__ __forceinline__ int gc_table_of(const GcArgs &A, int D) {
+  int q = -1;
+#pragma unroll
+  for (int i = 3; i >= 0; --i)
+    if (A.tab[i] && A.tab_dim[i] == D) q = i;
+  return q;
+}
+__device__ __forceinline__ bool gc_row_coded(const GcArgs &A, int K) {
+  return K >= 0 && K <= A.max_K && K <= A.steps && K <= A.K_limit;
+}
+
+} // namespace
+
+__global__ __launch_bounds__(1024) void gc_importance_encode_kernel(GcArgs A) {
+  __shared__ float s_mq[GC_MAX_DIM], s_sq[GC_MAX_DIM], s_mp[GC_MAX_DIM], s_sp[GC_MAX_DIM];
+  __shared__ float s_ts[GC_MAX_DIM], s_tt[GC_MAX_DIM], s_c[GC_MAX_DIM];
+  __shared__ unsigned long long s_best[16];
+  const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), nw = nt >> 6;
+  for (int64_t blk = blockIdx.x; blk < A.n_blocks; blk += gridDim.x) {   // (every exit below is uniform over the workgroup)
+    const int D = A.block_dim[blk];
+    const int K = A.out_K[blk];                 // ceil(KL / Omega), left there by the block-KL kernel of the same call
+    const int q = (D >= 1 && D <= GC_MAX_DIM) ? gc_table_of(A, D) : -1;
+    if (q < 0) {
+      if (tid == 0) A.out_K[blk] = -1;          // dim not covered
+      continue;
+    }
+    if (!gc_row_coded(A, K)) continue;          // not coded: out_K says how many partitions the block needs
+    const float *tab = A.tab[q];
+    const int64_t base = A.block_base[blk];
+    const int32_t pos = A.block_pos[blk];
+    const size_t S_pad = (size_t)A.S_pad;
+    for (int d = tid; d < D; d += nt) {
+      const int64_t ix = gc_index(A, base, pos, d);
+      s_mq[d] = A.q_loc[ix]; s_sq[d] = A.q_scale[ix]; s_mp[d] = A.p_loc[ix]; s_sp[d] = A.p_scale[ix];
+    }
+    const int n_steps = K < 1 ? 1 : K;          // len(indices) = max(K, 1), coder.py:548-557
+    for (int t = 0; t < n_steps; ++t) {
+      const bool last = t == n_steps - 1;
+      const float rho = last ? 0.0f : A.rho[K - 1 - t];   // get_auxiliary_ratio(i), i = K-1 .. 1 (coder.py:505-506)
+      // (A) the step's target, standardised w.r.t. its coder (importance_sampling.py:40-41)
+      for (int d = tid; d < D; d += nt) {
+        const float mq = s_mq[d], sq = s_sq[d], mp = s_mp[d], sp = s_sp[d];
+        float tl, ts;
+        if (last) {
+          tl = (mq - mp) / sp;
+          ts = sq / sp;
+        } else {
+          const float cv = sp * sp, tv = sq * sq, a = rho * cv;
+          const float ta_loc = (mq - mp) * a / cv;                                          // coder.py:147-154
+          const float ta_scale = sqrtf(tv * (a * a) / (cv * cv) + a * (cv - a) / cv);
+          const float pa_scale = sqrtf(a);                                                  // coder.py:141-144
+          tl = (ta_loc - 0.0f) / pa_scale;
+          ts = ta_scale / pa_scale;
+        }
+        s_ts[d] = ts;
+        s_tt[d] = tl / ts;
+        s_c[d] = GC_HL2PI + (float)det_log((double)ts);
+      }
+      __syncthreads();
+      // (B) importance weights, one lane per sample, dims in order
+      const float *row = tab + (size_t)t * (size_t)D * S_pad;
+      float best = -FLT_MAX;
+      int best_s = 0;
+      for (int s = tid; s < A.S; s += nt) {
+        const float *col = row + s;
+        double acc = 0.0;
+#pragma unroll 4
+        for (int d = 0; d < D; ++d) {
+          const float x = col[(size_t)d * S_pad];
+          const float e = x / s_ts[d] - s_tt[d];
+          const float lt = -0.5f * (e * e) - s_c[d];
+          const float lp = -0.5f * (x * x) - GC_HL2PI;
+          acc = acc + (double)(lt - lp);
+        }
+        const float w = (float)acc;
+        if (w > best) { best = w; best_s = s; }
+      }
+      // (C) greatest weight, lowest sample index on ties; a lane without a candidate holds (-FLT_MAX, 0), the accumulator's start
+      unsigned long long pk = ((unsigned long long)score_key(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)best_s);
+      pk = wave_max_u64(pk);
+      if (lane == 0) s_best[wave] = pk;
+      __syncthreads();
+      pk = s_best[0];
+      for (int w = 1; w < nw; ++w) { const unsigned long long o = s_best[w]; pk = o > pk ? o : pk; }
+      const int j = (int)(0xFFFFFFFFu - (uint32_t)pk);
+      if (tid == 0) A.out_indices[blk * (int64_t)A.max_K + t] = j;
+      // (D) the chosen sample: the next step's distributions (coder.py:157-171), or the block's sample
+      for (int d = tid; d < D; d += nt) {
+        const float x = row[(size_t)d * S_pad + (size_t)j];
+        const float mq = s_mq[d], sq = s_sq[d], mp = s_mp[d], sp = s_sp[d];
+        if (last) {
+          A.out_sample[gc_index(A, base, pos, d)] = sp * x + mp;
+        } else {
+          const float cv = sp * sp, tv = sq * sq, a = rho * cv;
+          const float av = sqrtf(a) * x + 0.0f;                                             // pa.scale * x + pa.loc
+          s_mq[d] = mp + (av * tv * cv + (mq - mp) * (cv - a) * cv) / (tv * a + cv * (cv - a));
+          s_sq[d] = sqrtf(tv * cv * (cv - a) / (a * tv + cv * (cv - a)));
+          s_mp[d] = mp + av;
+          s_sp[d] = sqrtf(cv - a);
+        }
+      }
+      // (every lane rewrites only the dims it read in (A) and (D); the barrier after (A) of the next step -- or of the next
+      //  block -- separates this step's reads of s_best from the next write)
+    }
+    __syncthreads();
+  }
+}
+
+// GaussianCoder.decode_block (coder.py:561-584): the p recursion alone, every dim on its own.
+__global__ __launch_bounds__(256) void gc_importance_decode_kernel(GcArgs A) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int64_t blk = blockIdx.x; blk < A.n_blocks; blk += gridDim.x) {
+    const int D = A.block_dim[blk];
+    const int K = A.K[blk];
+    const int q = D >= 1 ? gc_table_of(A, D) : -1;
+    const int n_steps = K < 1 ? 1 : K;
+    const int32_t *idx = A.indices + blk * (int64_t)A.max_K;
+    bool ok = q >= 0 && gc_row_coded(A, K);
+    if (ok)
+      for (int t = 0; t < n_steps; ++t) ok = ok && (uint32_t)idx[t] < (uint32_t)A.S;
+    const float *tab = ok ? A.tab[q] : nullptr;
+    const int64_t base = A.block_base[blk];
+    const int32_t pos = A.block_pos[blk];
+    const size_t S_pad = (size_t)A.S_pad;
+    for (int d = tid; d < D; d += nt) {
+      const int64_t ix = gc_index(A, base, pos, d);
+      float mp = A.p_loc[ix];
+      if (!ok) { A.out_sample[ix] = mp; continue; }   // not decodable: p_loc, and no table row is addressed
+      float sp = A.p_scale[ix];
+      for (int t = 0; t < n_steps - 1; ++t) {
+        const float x = tab[((size_t)t * (size_t)D + (size_t)d) * S_pad + (size_t)idx[t]];
+        const float cv = sp * sp, a = A.rho[K - 1 - t] * cv;
+        const float av = sqrtf(a) * x + 0.0f;
+        mp = mp + av;
+        sp = sqrtf(cv - a);
+      }
+      const float x = tab[((size_t)(n_steps - 1) * (size_t)D + (size_t)d) * S_pad + (size_t)idx[n_steps - 1]];
+      A.out_sample[ix] = sp * x + mp;
+    }
+  }
+}
+
+int gc_encode_threads(int S) { const int r = (S + 63) / 64 * 64; return r < 64 ? 64 : r > 1024 ? 1024 : r; }
+
+hipError_t launch_gc_importance_encode(const GcArgs &A, int grid, hipStream_t st) {
+  hipLaunchKernelGGL(gc_importance_encode_kernel, dim3(grid), dim3(gc_encode_threads(A.S)), 0, st, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_gc_importance_decode(const GcArgs &A, int grid, hipStream_t st) {
+  hipLaunchKernelGGL(gc_importance_decode_kernel, dim3(grid), dim3(256), 0, st, A);
+  return hipGetLastError();
+}
+
+} // namespace irec

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <exception>
 #include <cfloat>
 #include <cmath>
@@ -14,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "irec_internal.h"   // include/irec.h (the boundary) + the diagnostic flags and test hooks this library also exports
@@ -1578,6 +1580,110 @@ irec_status irec_device_tables(irec_context *ctx, const float **lut, const float
   if (lut2) *lut2 = ctx->d_lut2;
   if (dlog4r) *dlog4r = ctx->d_dlog4r;
   if (rho) *rho = ctx->d_rho;
+  return IREC_OK;
+}
+
+// ---- the sequential importance coder (irec_gc.hip) ---------------------------------------------------------------------------
+size_t irec_normal_table_floats(int32_t n_samples, int32_t dim, int32_t steps) {
+  if (n_samples < 1 || dim < 1 || steps < 1 || steps > IREC_TABLE_STEPS_MAX) {
+    fail(IREC_E_INVALID, "irec_normal_table_floats: n_samples %d, dim %d, steps %d out of range", n_samples, dim, steps);
+    return 0;
+  }
+  const size_t S_pad = round_up_sz((size_t)n_samples, IREC_NORMAL_TABLE_PAD);
+  const size_t n = (size_t)steps * (size_t)dim * S_pad;
+  if (n > (size_t)IREC_TABLE_BYTES_HARD / sizeof(float)) {
+    fail(IREC_E_INVALID, "irec_normal_table_floats: %d steps of %d samples x %d dims need %zu bytes, more than IREC_TABLE_BYTES_HARD", steps,
+         n_samples, dim, n * sizeof(float));
+    return 0;
+  }
+  return n;
+}
+
+irec_status irec_normal_table_build(int64_t seed, int32_t n_samples, int32_t dim, int32_t steps, float *out, int32_t n_threads) try {
+  const size_t n = irec_normal_table_floats(n_samples, dim, steps);
+  if (!n) return IREC_E_INVALID;
+  if (!out) return fail(IREC_E_INVALID, "irec_normal_table_build: null output");
+  const size_t S_pad = round_up_sz((size_t)n_samples, IREC_NORMAL_TABLE_PAD);
+  // work items: (step, group of 16 samples) -- a group fills whole 64-byte lines of every row it touches
+  const int64_t groups = (int64_t)(S_pad / IREC_NORMAL_TABLE_PAD), items = (int64_t)steps * groups;
+  std::atomic<int64_t> next{0};
+  auto work = [&]() {
+    for (int64_t it = next.fetch_add(1); it < items; it = next.fetch_add(1)) {
+      const int64_t j = it / groups, s0 = (it % groups) * IREC_NORMAL_TABLE_PAD;
+      TfNormalStream st(seed + j);
+      float *tab = out + (size_t)j * (size_t)dim * S_pad;
+      for (int64_t s = s0; s < s0 + IREC_NORMAL_TABLE_PAD; ++s)
+        for (int64_t d = 0; d < dim; ++d)
+          tab[(size_t)d * S_pad + (size_t)s] = s < n_samples ? st.element((uint64_t)(s * dim + d)) : 0.0f;
+    }
+  };
+  int nt = n_threads > 0 ? n_threads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  nt = (int)std::min<int64_t>(nt, items);
+  std::vector<std::thread> pool;
+  pool.reserve((size_t)nt);
+  try {
+    for (int i = 1; i < nt; ++i) pool.emplace_back(work);
+  } catch (const std::exception &) {}   // a thread that could not be started: the ones that exist (and this one) do its share
+  work();
+  for (auto &t : pool) t.join();
+  return IREC_OK;
+} catch (const std::exception &e) { return fail(IREC_E_INVALID, "irec_normal_table_build: %s", e.what()); }
+
+static irec_status gc_fill(const char *who, irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
+                           const int32_t *block_dim, const irec_normal_tables *tables, int32_t max_K, irec::GcArgs &A) {
+  if (!ctx) return fail(IREC_E_INVALID, "%s: null context", who);
+  if (n_blocks < 0) return fail(IREC_E_INVALID, "%s: n_blocks < 0", who);
+  if (!block_base || !block_pos || !block_dim || !tables) return fail(IREC_E_INVALID, "%s: null pointer argument", who);
+  if (tables->n_samples < 1 || tables->steps < 1 || tables->steps > IREC_TABLE_STEPS_MAX)
+    return fail(IREC_E_INVALID, "%s: tables of %d samples, %d steps", who, tables->n_samples, tables->steps);
+  if (max_K < 1 || max_K > tables->steps) return fail(IREC_E_INVALID, "%s: max_K %d outside [1, tables->steps = %d]", who, max_K, tables->steps);
+  int n_tab = 0;
+  for (int i = 0; i < 4; ++i) {
+    if (!tables->table[i]) { A.tab[i] = nullptr; A.tab_dim[i] = 0; continue; }
+    if (!irec_normal_table_floats(tables->n_samples, tables->dim[i], tables->steps)) return IREC_E_INVALID;
+    A.tab[i] = tables->table[i]; A.tab_dim[i] = tables->dim[i]; ++n_tab;
+  }
+  if (!n_tab) return fail(IREC_E_INVALID, "%s: no table", who);
+  A.block_base = block_base; A.block_pos = block_pos; A.block_dim = block_dim; A.n_blocks = n_blocks;
+  A.S = tables->n_samples; A.S_pad = (int32_t)round_up_sz((size_t)tables->n_samples, IREC_NORMAL_TABLE_PAD);
+  A.steps = tables->steps; A.max_K = max_K; A.K_limit = ctx->n_rho; A.rho = ctx->d_rho;
+  return IREC_OK;
+}
+
+irec_status irec_gc_importance_encode(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
+                                      const int32_t *block_dim, const int32_t *perm, const float *q_loc, const float *q_scale,
+                                      const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
+                                      float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
+                                      float *out_sample, void *hip_stream) {
+  irec::GcArgs G{};
+  if (irec_status s = gc_fill("irec_gc_importance_encode", ctx, n_blocks, block_base, block_pos, block_dim, tables, max_K, G)) return s;
+  if (!(kl_per_partition > 0.0f)) return fail(IREC_E_INVALID, "irec_gc_importance_encode: kl_per_partition must be positive");
+  if (n_blocks == 0) return IREC_OK;
+  if (!q_loc || !q_scale || !p_loc || !p_scale || !out_K || !out_indices || !out_sample)
+    return fail(IREC_E_INVALID, "irec_gc_importance_encode: null pointer argument");
+  IREC_ON_DEVICE(ctx->device);
+  irec::EncArgs A{};   // K = ceil(KL / Omega) of every block into out_K: the kernel of irec_block_kl
+  A.block_base = block_base; A.block_pos = block_pos; A.block_dim = block_dim; A.perm = perm;
+  A.q_loc = q_loc; A.q_scale = q_scale; A.p_loc = p_loc; A.p_scale = p_scale;
+  A.n_blocks = n_blocks; A.omega = kl_per_partition; A.S = tables->n_samples; A.B = 1; A.out_K = out_K; A.K_limit = ctx->n_rho;
+  HIP_TRY(irec::launch_block_kl(A, nullptr, (int)std::min<int64_t>(n_blocks, 8LL * ctx->n_cu), (hipStream_t)hip_stream));
+  G.perm = perm; G.q_loc = q_loc; G.q_scale = q_scale; G.p_loc = p_loc; G.p_scale = p_scale;
+  G.out_K = out_K; G.out_indices = out_indices; G.out_sample = out_sample;
+  HIP_TRY(irec::launch_gc_importance_encode(G, (int)std::min<int64_t>(n_blocks, 16LL * ctx->n_cu), (hipStream_t)hip_stream));
+  return IREC_OK;
+}
+
+irec_status irec_gc_importance_decode(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
+                                      const int32_t *block_dim, const int32_t *perm, const float *p_loc, const float *p_scale,
+                                      const irec_normal_tables *tables, int32_t max_K, const int32_t *K, const int32_t *indices,
+                                      float *out_sample, void *hip_stream) {
+  irec::GcArgs G{};
+  if (irec_status s = gc_fill("irec_gc_importance_decode", ctx, n_blocks, block_base, block_pos, block_dim, tables, max_K, G)) return s;
+  if (n_blocks == 0) return IREC_OK;
+  if (!p_loc || !p_scale || !K || !indices || !out_sample) return fail(IREC_E_INVALID, "irec_gc_importance_decode: null pointer argument");
+  IREC_ON_DEVICE(ctx->device);
+  G.perm = perm; G.p_loc = p_loc; G.p_scale = p_scale; G.K = K; G.indices = indices; G.out_sample = out_sample;
+  HIP_TRY(irec::launch_gc_importance_decode(G, (int)std::min<int64_t>(n_blocks, 16LL * ctx->n_cu), (hipStream_t)hip_stream));
   return IREC_OK;
 }
 

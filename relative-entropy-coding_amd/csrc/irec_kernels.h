@@ -216,6 +216,23 @@ hipError_t launch_shim_cat_elu(const float *y, const float *latent, float *out, 
                                const float *by, hipStream_t st);
 hipError_t launch_shim_residual_elu(const float *inp, const float *t, float alpha, float *out, float *out_elu, int64_t count,
                                     const float *bt, int C, int HW, hipStream_t st);
+// the sequential importance coder (irec_gc.hip): GaussianCoder.encode_block / decode_block over an ImportanceSampler, alpha = inf
+constexpr int GC_MAX_DIM = 1024;    // dims of a block the encoder keeps in LDS
+struct GcArgs {
+  const int64_t *block_base; const int32_t *block_pos; const int32_t *block_dim; const int32_t *perm;
+  const float *q_loc, *q_scale, *p_loc, *p_scale;   // (the decoder reads p only)
+  int64_t n_blocks;
+  int32_t S, S_pad, steps, max_K;   // samples, padded row length of the tables, steps the tables cover, index slots per row
+  int32_t K_limit;                  // as EncArgs::K_limit
+  const float *rho;
+  const float *tab[4]; int32_t tab_dim[4];   // normal proposal tables (irec_normal_table_build), one per distinct block dim
+  int32_t *out_K; int32_t *out_indices;      // encoder: out_K holds ceil(KL / Omega) on entry (block_kl_kernel)
+  const int32_t *K; const int32_t *indices;  // decoder
+  float *out_sample;
+};
+int gc_encode_threads(int S);
+hipError_t launch_gc_importance_encode(const GcArgs &A, int grid, hipStream_t st);
+hipError_t launch_gc_importance_decode(const GcArgs &A, int grid, hipStream_t st);
 hipError_t launch_dec_sqrt_test(unsigned long long *out, hipStream_t st);
 hipError_t launch_uniform_int(int64_t seed, int64_t n, int32_t *out, hipStream_t st);
 hipError_t launch_select_test(const float *scores, int N, int Bnew, int Bcur, uint32_t *keys, int32_t *sel, bool quick, hipStream_t st);

@@ -27,6 +27,7 @@ IREC_FLAG_SHAPE_SHIFT = 8          # diagnostic workgroup shapes of the team enc
 IREC_FLAG_SHAPE = {"default": 0, "2": 2 << 8, "3": 3 << 8, "1x2": 5 << 8, "team": 6 << 8}
 IREC_TABLE_STEPS_DEFAULT = 32
 IREC_TABLE_STEPS_MAX = 4096
+IREC_NORMAL_TABLE_PAD = 16
 BIG_PRIME = 10007
 MAX_BEAMS = 256
 MAX_PARTITIONS = 65536
@@ -40,6 +41,11 @@ class IrecParams(ctypes.Structure):
 class IrecTables(ctypes.Structure):
     """irec_tables of include/irec.h: the caller-supplied tables of a context (irec_create_with)."""
     _fields_ = [("lut10007", ctypes.c_void_p), ("aux_ratios", ctypes.c_void_p), ("n_aux_ratios", ctypes.c_int32)]
+
+
+class IrecNormalTables(ctypes.Structure):
+    """irec_normal_tables of include/irec.h: the device tables of one call of the sequential importance coder."""
+    _fields_ = [("table", ctypes.c_void_p * 4), ("dim", ctypes.c_int32 * 4), ("n_samples", ctypes.c_int32), ("steps", ctypes.c_int32)]
 
 
 class IrecPlanInfo(ctypes.Structure):
@@ -106,6 +112,12 @@ SIGNATURES = {
     "irec_decode_tensors_supported": (_i32, [_PP, _i32, _i32]),
     "irec_beam_decode_tensors": (ctypes.c_int, [_vp, _PP, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
                                                 ctypes.c_size_t, _vp]),
+    "irec_normal_table_floats": (ctypes.c_size_t, [_i32, _i32, _i32]),
+    "irec_normal_table_build": (ctypes.c_int, [_i64, _i32, _i32, _i32, _vp, _i32]),
+    "irec_gc_importance_encode": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables),
+                                                 ctypes.c_float, _i32, _vp, _vp, _vp, _vp]),
+    "irec_gc_importance_decode": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables), _i32,
+                                                 _vp, _vp, _vp, _vp]),
     "irec_io_last_error": (ctypes.c_char_p, []),
     "irec_ac_encode": (ctypes.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
     "irec_ac_decode": (ctypes.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _i64, ctypes.POINTER(_i64)]),

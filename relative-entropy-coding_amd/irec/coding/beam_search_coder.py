@@ -34,6 +34,8 @@ class PendingCode:
     """Result of one asynchronous encode call: everything stays on the device until the host asks.
     K [n_blocks] int32, idx [n_blocks, max_K] int32 (rows in layout order), sample (input shape)."""
 
+    min_indices = 0   # indices a coded row holds at least: 1 for the sequential coder, whose zero-KL block emits one (coder.py:548-557)
+
     def __init__(self, coder, lay, K, idx, sample, max_K, shared=False, params=None):
         self.coder, self.lay, self.K, self.idx, self.sample, self.max_K = coder, lay, K, idx, sample, max_K
         self.shared, self.params = shared, params   # the call was allowed to share blocks between workgroups / teams; its irec_params
@@ -78,7 +80,7 @@ class PendingCode:
         gc_was_on = gc.isenabled()
         gc.disable()
         try:
-            rows, ks = idx_host.tolist(), K_host.tolist()
+            rows, ks = idx_host.tolist(), (np.maximum(K_host, self.min_indices) if self.min_indices else K_host).tolist()
             nat = lay.natural.tolist() if hasattr(lay.natural, "tolist") else list(lay.natural)
             return [[rows[r][:ks[r]] for r in nat[i * bpt:(i + 1) * bpt]] for i in range(lay.n_tensors)]
         finally:
@@ -124,6 +126,8 @@ class PendingCode:
             PendingCode._all_gave_up(pendings)
         if retry is not None:
             raise retry
+        if pendings[0].min_indices:
+            K = np.maximum(K, pendings[0].min_indices)
         return np.ascontiguousarray(K), np.ascontiguousarray(idx)
 
     @staticmethod

@@ -1,9 +1,10 @@
-"""Host mirror of rec/coding/coder.py for the beam-search path (reference file:line in each docstring).
+"""Host mirror of rec/coding/coder.py (reference file:line in each docstring).
 
-Only what `sampler='beam_search'` needs is implemented: the block split/merge bookkeeping and the auxiliary-variance
-ratios -- extrapolated (the power law), or FITTED ones handed over as data (round 5).  The sampler-driven
-GaussianCoder.encode_block (coder.py:493-584) and the SGD ratio fitter that produces fitted ratios (coder.py:233-410) are
-out of scope.
+The block split/merge bookkeeping, the auxiliary-variance ratios -- extrapolated (the power law), or FITTED ones handed over
+as data (round 5) -- and the sampler-driven GaussianCoder.encode / decode / encode_block / decode_block (coder.py:412-587):
+the reference's loop on the host for any Sampler object, the gfx950 kernels of csrc/irec_gc.hip for the ImportanceSampler at
+alpha = inf on GPU tensors.  The SGD ratio fitter that produces fitted ratios (coder.py:233-410) and the update_sampler branch
+are out of scope.
 """
 import abc
 
@@ -11,9 +12,75 @@ import numpy as np
 import torch
 
 from .utils import CodingError
-from ..engine import tf_shuffle_perm
+from .. import _lib
+from ..engine import Engine, NormalTableTooLarge, get_engine, tf_shuffle_perm
 
 AUX_RATIO_POWER_LAW = -0.7864636765648174  # coder.py:16
+
+
+def _det_log(x):
+    """The deterministic float64 log of csrc/irec_device.h (det_log), operation by operation."""
+    x = np.array(x, dtype=np.float64, copy=True).reshape(-1)
+    bits = x.view(np.uint64)
+    e = ((bits >> np.uint64(52)) & np.uint64(0x7FF)).astype(np.int64)
+    sub = e == 0
+    if sub.any():
+        x = np.where(sub, x * 18014398509481984.0, x)
+        bits = x.view(np.uint64)
+        e = np.where(sub, ((bits >> np.uint64(52)) & np.uint64(0x7FF)).astype(np.int64) - 54, e)
+    e = e - 1023
+    m = ((bits & np.uint64(0x000FFFFFFFFFFFFF)) | np.uint64(0x3FF0000000000000)).view(np.float64)
+    big = m > 1.4142135623730951
+    m = np.where(big, m * 0.5, m)
+    e = e + big
+    s = (m - 1.0) / (m + 1.0)
+    s2 = s * s
+    q = np.full_like(s, 1.0 / 25.0)
+    for k in (23, 21, 19, 17, 15, 13, 11, 9, 7, 5, 3):
+        q = q * s2 + 1.0 / k
+    return e.astype(np.float64) * 0.6931471805599453 + (2.0 * s + (2.0 * s) * (s2 * q))
+
+
+def canonical_partitions(mq, sq, mp, sp, omega):
+    """K = ceil(KL / Omega) of one block as block_kl_kernel computes it (csrc/irec_kernels.hip): the float64 KL of
+    every dim, dims in groups of 256, lane l chains dims 4l .. 4l+3, the 64 lane sums paired at distance 32, 16, .., 1, group sums
+    added in order, rounded to float32 once; then ceil in float32.  A KL that is not positive gives 0, an infinite one 10^9."""
+    with np.errstate(all="ignore"):
+        mq, sq, mp, sp = (np.asarray(v, np.float32).reshape(-1).astype(np.float64) for v in (mq, sq, mp, sp))
+        t = sq / sp
+        dm = (mq - mp) / sp
+        kl = 0.5 * (dm * dm) + (0.5 * (t * t - 1.0) - _det_log(t))
+        groups = -(-kl.size // 256)
+        if not groups:
+            return 0
+        v = np.zeros(groups * 256)
+        v[:kl.size] = kl
+        v = v.reshape(groups, 64, 4)
+        lanes = np.zeros((groups, 64))
+        for i in range(4):
+            lanes = lanes + v[:, :, i]
+        at = np.arange(64)
+        for off in (32, 16, 8, 4, 2, 1):
+            lanes = lanes + lanes[:, at ^ off]
+        total = lanes[0, 0]
+        for g in range(1, groups):
+            total = total + lanes[g, 0]
+        total = np.float32(total)
+        if not total > 0:
+            return 0
+        k = np.ceil(total / np.float32(omega))
+        return int(k) if k < np.float32(1.0e9) else 1000000000
+
+
+class DeviceWindowExceeded(NormalTableTooLarge):
+    """A block of a device call needs more partitions than its normal tables can cover: the call takes the host loop."""
+
+
+class _Dist:
+    """Duck-typed distribution: samplers and coders read only .loc and .scale (coder.py:427-430)."""
+
+    def __init__(self, loc, scale):
+        self.loc, self.scale = loc, scale
 
 
 class Coder(abc.ABC):
@@ -86,6 +153,10 @@ class GaussianCoder(Coder):
         if not self.extrapolate_auxiliary_ratios:          # coder.py:203-216: the variables a checkpoint restores
             self.aux_variable_variance_ratios = np.array([1.], dtype=np.float32)
             self._initialized = False
+        self.table_steps = 0         # steps the normal proposal tables of a device call cover; 0 = the default window
+        self._max_K_hint = _lib.IREC_TABLE_STEPS_DEFAULT   # index slots per block of a device call (raised when a block needs more)
+        self._K_seen, self._K_reads, self._split_strikes = 28, 0, 0   # (PendingCode's bookkeeping, shared with the beam coder)
+        self.last_path = None        # "device" / "host": which path the sequential coder's last encode / decode call took
 
     def set_auxiliary_variance_ratios(self, ratios):
         """The FITTED ratios of an extrapolate_auxiliary_ratios=False coder, as data: what the reference restores into
@@ -122,16 +193,258 @@ class GaussianCoder(Coder):
             raise CodingError("fitting auxiliary variance ratios is outside the beam-search path: "
                               "set_auxiliary_variance_ratios(ratios) takes fitted ones as data")
 
-    def encode(self, target_dist, coding_dist, seed, **kwargs):
-        raise CodingError("GaussianCoder with a rejection/importance sampler is outside the beam-search path; "
-                          "use BeamSearchCoder")
+    # ---- the sequential coder (coder.py:412-587): any Sampler on the host, the ImportanceSampler of the reference's models
+    #      (alpha = inf) in the gfx950 kernels behind irec_gc_importance_encode / _decode ---------------------------------
+    DEVICE_MAX_DIM = 1024    # dims of a block the kernels keep in LDS (csrc/irec_gc.hip)
 
-    def decode(self, coding_dist, indices, seed, **kwargs):
-        raise CodingError("GaussianCoder with a rejection/importance sampler is outside the beam-search path; "
-                          "use BeamSearchCoder")
+    def get_codelength(self, indicies):
+        """coder.py:586-587."""
+        return sum([self.sampler.get_codelength(i) for i in indicies])
 
-    def encode_block(self, target_dist, coding_dist, seed, **kwargs):
-        raise CodingError("GaussianCoder.encode_block (sequential sampler) is outside the beam-search path")
+    def table_window(self):
+        """Steps the normal proposal tables of a call cover (`table_steps`, or the beam coder's default window)."""
+        return int(self.table_steps) if self.table_steps else _lib.IREC_TABLE_STEPS_DEFAULT
+
+    def _on_device(self, loc, block_size):
+        """The kernels take the call: the reference's own ImportanceSampler at alpha = inf, tensors on the GPU, blocks of at most
+        DEVICE_MAX_DIM dims.  Everything else runs the reference's loop on the host."""
+        from .samplers import ImportanceSampler
+        if type(self.sampler) is not ImportanceSampler or not (self.sampler.alpha == np.inf):
+            return False
+        t = torch.as_tensor(loc)
+        if t.device.type != "cuda" or t.ndim < 2 or t.shape[0] < 1 or t[0].numel() < 1:
+            return False
+        n = t[0].numel()
+        return min(n, n if block_size is None else int(block_size)) <= self.DEVICE_MAX_DIM
+
+    def _engine_for(self, tensor):
+        t = torch.as_tensor(tensor)
+        if self.extrapolate_auxiliary_ratios:
+            return get_engine(t.device if t.device.type == "cuda" else None)
+        self.get_auxiliary_ratio(0)      # fitted ratios: a context of this coder's own carries them (keyed on device and table bytes)
+        ratios = np.ascontiguousarray(np.asarray(self.aux_variable_variance_ratios, dtype=np.float32))
+        key = (str(t.device), ratios.tobytes())
+        if getattr(self, "_ratio_engine", None) is None or getattr(self, "_ratio_engine_key", None) != key:
+            self._ratio_engine = Engine(t.device, aux_ratios=ratios)
+            self._ratio_engine_key = key
+        return self._ratio_engine
+
+    @staticmethod
+    def _dev(t, device):
+        return torch.as_tensor(t).detach().to(device=device, dtype=torch.float32).contiguous()
+
+    def encode_tensors_device(self, q_loc, q_scale, p_loc, p_scale, seed, block_size, max_K=None, table_steps=None):
+        """Asynchronous core of the device path: one block-KL and one encode launch for all blocks of all tensors (leading dim
+        = independent latent tensors); returns a `PendingCode`, nothing is copied to the host."""
+        from .beam_search_coder import PendingCode
+        src = torch.as_tensor(q_loc)
+        shapes = {tuple(torch.as_tensor(t).shape) for t in (q_loc, q_scale, p_loc, p_scale)}
+        if len(shapes) != 1:
+            raise CodingError("All tensor arguments supplied to split must have the same batch dimensions!")
+        eng = self._engine_for(src)
+        ql, qs, pl, ps = (self._dev(t, eng.device) for t in (q_loc, q_scale, p_loc, p_scale))
+        lay = eng.layout(src.shape[0], src[0].numel(), block_size, seed)
+        self._max_K_hint = min(self._max_K_hint, self.DEVICE_MAX_K)
+        max_K = max(1, min(self._max_K_hint if max_K is None else int(max_K), self.DEVICE_MAX_K))
+        self.last_path = "device"
+        steps = max(int(table_steps) if table_steps else self.table_window(), max_K)
+        K, idx, sample = eng.gc_encode_blocks(lay, ql, qs, pl, ps, seed, self.kl_per_partition, self.sampler.n_samples(), max_K, steps)
+        pending = PendingCode(self, lay, K, idx, sample.reshape(src.shape).to(src.device), max_K)
+        pending.min_indices = 1
+        return pending
+
+    DEVICE_MAX_K = _lib.IREC_TABLE_STEPS_MAX   # partitions of a block the tables of a device call can cover
+    DEVICE_ATTEMPTS = 4
+
+    def encode_tensors(self, q_loc, q_scale, p_loc, p_scale, seed, block_size):
+        """Synchronous device path.  A block with more partitions than the window is coded again with a longer one -- a bounded
+        number of times; one that needs more than the tables can cover (DEVICE_MAX_K) sends the call to the host loop
+        (DeviceWindowExceeded, a NormalTableTooLarge: the callers fall back as for tables that do not fit)."""
+        from .beam_search_coder import MorePartitionsNeeded
+        max_K, need = None, 0
+        for _ in range(self.DEVICE_ATTEMPTS):
+            pending = self.encode_tensors_device(q_loc, q_scale, p_loc, p_scale, seed, block_size, max_K)
+            try:
+                return pending.to_lists(), pending.sample
+            except MorePartitionsNeeded as e:
+                need = e.need
+                self._max_K_hint = min(self._max_K_hint, self.DEVICE_MAX_K)   # (never a hint the tables cannot cover)
+                if need > self.DEVICE_MAX_K:
+                    break
+                max_K = need
+        raise DeviceWindowExceeded(f"a block needs {need} partitions; the device path covers {self.DEVICE_MAX_K} "
+                                   f"and codes a call at most {self.DEVICE_ATTEMPTS} times")
+
+    def decode_tensors(self, p_loc, p_scale, indices, seed, block_size):
+        src = torch.as_tensor(p_loc)
+        eng = self._engine_for(src)
+        pl, ps = (self._dev(t, eng.device) for t in (p_loc, p_scale))
+        lay = eng.layout(src.shape[0], src[0].numel(), block_size, seed)
+        bpt = lay.blocks_per_tensor
+        if len(indices) != src.shape[0] or any(len(b) != bpt for b in indices):
+            raise CodingError("indices do not match the block structure of coding_dist")
+        if any(len(ix) < 1 for b in indices for ix in b):
+            raise CodingError("every block of the sequential coder holds at least one index")
+        max_K = max(len(ix) for b in indices for ix in b)
+        if not self.extrapolate_auxiliary_ratios:
+            self.get_auxiliary_ratio(max_K - 1)   # (raises the reference's text for a list longer than the fitted table)
+        K = np.zeros(lay.n_blocks, dtype=np.int32)
+        idx = np.zeros((lay.n_blocks, max_K), dtype=np.int32)
+        for i in range(src.shape[0]):
+            for j in range(bpt):
+                row, ix = lay.natural[i * bpt + j], indices[i][j]
+                K[row] = len(ix)
+                idx[row, :len(ix)] = np.asarray(ix, dtype=np.int32)
+        S = self.sampler.n_samples()
+        if idx.min() < 0 or idx.max() >= S:
+            raise CodingError("index out of range [0, n_samples)")
+        self.last_path = "device"
+        sample = eng.gc_decode_blocks(lay, pl, ps, seed, S, torch.from_numpy(K).to(eng.device), torch.from_numpy(idx).to(eng.device),
+                                      max(self.table_window(), max_K))
+        return sample.reshape(src.shape).to(src.device)
+
+    # the reference's loop on the host, any Sampler object.  float32 numpy, one correctly rounded operation per operator of the
+    # reference (torch's vectorised CPU sqrt is not correctly rounded, and one ulp in a conditional scale moves the sample)
+    @staticmethod
+    def _host(t):
+        return torch.as_tensor(t).detach().to("cpu", torch.float32).numpy()
+
+    @staticmethod
+    def _dist(loc, scale):
+        return _Dist(torch.from_numpy(np.ascontiguousarray(loc)), torch.from_numpy(np.ascontiguousarray(scale)))
+
+    def _kl_partitions(self, mq, sq, mp, sp):
+        """K = int32(ceil(sum KL(q || p) / Omega)) (coder.py:499-501) -- the canonical K, bit for bit what the device path gets from
+        block_kl_kernel, so that one coder emits the same number of indices for CPU and GPU tensors; a degenerate block raises as
+        the device path does."""
+        K = canonical_partitions(mq, sq, mp, sp, self.kl_per_partition)
+        if K > _lib.MAX_PARTITIONS:
+            raise CodingError(f"KL divergence needs {K} partitions; this build supports {_lib.MAX_PARTITIONS}")
+        return K
+
+    def _encode_block_host(self, target_dist, coding_dist, seed):
+        """coder.py:497-559 in the notation of DESIGN.md §3 (cv, tv, a): K - 1 auxiliary variables, then the block's sample, every
+        draw through `self.sampler.coded_sample`."""
+        mq, sq, mp, sp = (self._host(t) for t in (target_dist.loc, target_dist.scale, coding_dist.loc, coding_dist.scale))
+        device = torch.as_tensor(target_dist.loc).device
+        picked, self.last_path = [], "host"
+        with np.errstate(all="ignore"):
+            for i in range(self._kl_partitions(mq, sq, mp, sp) - 1, 0, -1):
+                cv, tv = sp * sp, sq * sq
+                a = np.float32(self.get_auxiliary_ratio(i)) * cv
+                ta = self._dist((mq - mp) * a / cv, np.sqrt(tv * (a * a) / (cv * cv) + a * (cv - a) / cv))   # coder.py:147-154
+                pa = self._dist(np.zeros_like(mp), np.sqrt(a))                                             # coder.py:141-144
+                j, drawn = self.sampler.coded_sample(target=ta, coder=pa, seed=seed)
+                picked.append(j)
+                seed += 1
+                A = self._host(drawn)
+                mq, sq = mp + (A * tv * cv + (mq - mp) * (cv - a) * cv) / (tv * a + cv * (cv - a)), \
+                    np.sqrt(tv * cv * (cv - a) / (a * tv + cv * (cv - a)))                                 # coder.py:163-171
+                mp, sp = mp + A, np.sqrt(cv - a)                                                           # coder.py:157-160
+        j, z = self.sampler.coded_sample(target=self._dist(mq, sq), coder=self._dist(mp, sp), seed=seed)
+        picked.append(j)
+        return picked, torch.as_tensor(z).to(device)
+
+    def _decode_block_host(self, coding_dist, indices, seed):
+        """coder.py:561-584: the p recursion alone, indices read in encoder order (the caller's list is not touched)."""
+        mp, sp = self._host(coding_dist.loc), self._host(coding_dist.scale)
+        device = torch.as_tensor(coding_dist.loc).device
+        n, self.last_path = len(indices), "host"
+        with np.errstate(all="ignore"):
+            for t in range(n - 1):
+                cv = sp * sp
+                a = np.float32(self.get_auxiliary_ratio(n - 1 - t)) * cv
+                A = self._host(self.sampler.decode_sample(coder=self._dist(np.zeros_like(mp), np.sqrt(a)), sample_index=indices[t],
+                                                          seed=seed + t))
+                mp, sp = mp + A, np.sqrt(cv - a)
+        return torch.as_tensor(self.sampler.decode_sample(coder=self._dist(mp, sp), sample_index=indices[n - 1], seed=seed + n - 1)).to(device)
+
+    def _check_sampler(self, update_sampler=False):
+        if self.sampler is None:
+            raise CodingError("GaussianCoder needs a sampler (e.g. irec.ImportanceSampler(coding_bits))")
+        if update_sampler:
+            raise CodingError("update_sampler=True (the training-time branch that draws target.sample() instead of coding, "
+                              "coder.py:516-519,543-546) is not part of this build")
+
+    def encode_block(self, target_dist, coding_dist, seed, update_sampler=False, verbose=False, numpy=True):
+        """coder.py:493-559.  Returns (list of max(K, 1) indices, sample with the shape of loc)."""
+        if target_dist.loc.shape[0] != 1:
+            raise CodingError("For encoding, batch size must be 1.")
+        self._check_sampler(update_sampler)
+        if self._on_device(target_dist.loc, None):
+            try:
+                idx, sample = self.encode_tensors(target_dist.loc, target_dist.scale, coding_dist.loc, coding_dist.scale, seed, None)
+                return list(idx[0][0]), sample
+            except NormalTableTooLarge:
+                pass
+        return self._encode_block_host(target_dist, coding_dist, seed)
 
     def decode_block(self, coding_dist, indices, seed, **kwargs):
-        raise CodingError("GaussianCoder.decode_block (sequential sampler) is outside the beam-search path")
+        """coder.py:561-584.  The caller's list is left as it is."""
+        self._check_sampler()
+        indices = [int(v) for v in indices]
+        loc = torch.as_tensor(coding_dist.loc)
+        if loc.ndim >= 2 and loc.shape[0] == 1 and self._on_device(loc, None):
+            try:
+                return self.decode_tensors(loc, torch.as_tensor(coding_dist.scale), [[indices]], seed, None)
+            except NormalTableTooLarge:
+                pass
+        return self._decode_block_host(coding_dist, indices, seed)
+
+    def encode(self, target_dist, coding_dist, seed, **kwargs):
+        """coder.py:412-457.  Extensions, as BeamSearchCoder.encode has them (device path only): `batched=True` codes a leading
+        batch of independent latent tensors in one launch, `defer=True` returns (PendingCode, sample) without a host sync."""
+        batched, defer = kwargs.pop("batched", False), kwargs.pop("defer", False)
+        max_K, table_steps = kwargs.pop("max_K", None), kwargs.pop("table_steps", None)
+        self._check_sampler(kwargs.get("update_sampler", False))
+        if target_dist.loc.shape[0] != 1 and not batched:
+            raise CodingError("For encoding, batch size must be 1.")
+        if self._on_device(target_dist.loc, self.block_size):
+            args = (target_dist.loc, target_dist.scale, coding_dist.loc, coding_dist.scale, seed, self.block_size)
+            try:
+                if defer:
+                    pending = self.encode_tensors_device(*args, max_K, table_steps)
+                    return pending, pending.sample
+                idx, sample = self.encode_tensors(*args)
+                if self.block_size is None:
+                    idx = [blocks[0] for blocks in idx]
+                return (idx if batched else idx[0]), sample
+            except NormalTableTooLarge:
+                pass
+        if defer:
+            raise CodingError("defer=True needs the device path: an ImportanceSampler with alpha = inf, tensors on the GPU, "
+                              f"blocks of at most {self.DEVICE_MAX_DIM} dims whose proposal tables fit")
+        if batched:
+            loc, scale = torch.as_tensor(target_dist.loc), torch.as_tensor(target_dist.scale)
+            c_loc, c_scale = torch.as_tensor(coding_dist.loc), torch.as_tensor(coding_dist.scale)
+            out = [self.encode(_Dist(loc[i:i + 1], scale[i:i + 1]), _Dist(c_loc[i:i + 1], c_scale[i:i + 1]), seed, **kwargs)
+                   for i in range(loc.shape[0])]
+            return [o[0] for o in out], torch.cat([o[1] for o in out], dim=0)
+        if self.block_size is None:
+            return self._encode_block_host(target_dist, coding_dist, seed)
+        stats = self.split(target_dist.loc, target_dist.scale, coding_dist.loc, coding_dist.scale, seed=seed)   # coder.py:427-457
+        coded = [self._encode_block_host(_Dist(b[0][None, :], b[1][None, :]), _Dist(b[2][None, :], b[3][None, :]), seed) for b in zip(*stats)]
+        sample, = self.merge([z[0, :] for _, z in coded], shape=target_dist.loc.shape, seed=seed)
+        return [ix for ix, _ in coded], sample
+
+    def decode(self, coding_dist, indices, seed, **kwargs):
+        """coder.py:459-491 (`batched=True`: as `encode`)."""
+        batched = kwargs.pop("batched", False)
+        self._check_sampler()
+        loc, scale = torch.as_tensor(coding_dist.loc), torch.as_tensor(coding_dist.scale)
+        if self._on_device(loc, self.block_size):
+            per_tensor = indices if batched else [indices]
+            if self.block_size is None:
+                per_tensor = [[ix] for ix in per_tensor]
+            try:
+                return self.decode_tensors(loc, scale, [[[int(v) for v in ix] for ix in b] for b in per_tensor], seed, self.block_size)
+            except NormalTableTooLarge:
+                pass
+        if batched:
+            return torch.cat([self.decode(_Dist(loc[i:i + 1], scale[i:i + 1]), indices[i], seed) for i in range(loc.shape[0])], dim=0)
+        if self.block_size is None:
+            return self._decode_block_host(coding_dist, indices, seed)
+        locs, scales = self.split(loc, scale, seed=seed)                                                        # coder.py:471-491
+        parts = [self._decode_block_host(_Dist(m[None, :], sd[None, :]), ix, seed)[0, :] for ix, m, sd in zip(indices, locs, scales)]
+        sample, = self.merge(parts, shape=loc.shape, seed=seed)
+        return sample

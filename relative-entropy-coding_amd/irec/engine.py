@@ -41,6 +41,25 @@ def philox_uniform_int(seed, n):
     return out
 
 
+class NormalTableTooLarge(_lib.IrecLibraryError):
+    """The normal proposal tables of a call exceed what the library builds (IREC_TABLE_BYTES_HARD): the caller takes the host path."""
+
+
+def build_normal_table(seed, n_samples, dim, steps, n_threads=0):
+    """irec_normal_table_build (host): float32 [steps, dim, S_pad], entry [j, d, s] = element s * dim + d of
+    tf.random.normal after tf.random.set_seed(seed + j); S_pad = n_samples rounded up to IREC_NORMAL_TABLE_PAD, zero padded."""
+    lib = _lib.load()
+    n = lib.irec_normal_table_floats(int(n_samples), int(dim), int(steps))
+    if not n:
+        raise NormalTableTooLarge("irec_normal_table_floats: " + lib.irec_last_error().decode())
+    s_pad = -(-int(n_samples) // _lib.IREC_NORMAL_TABLE_PAD) * _lib.IREC_NORMAL_TABLE_PAD
+    out = np.empty((int(steps), int(dim), s_pad), dtype=np.float32)
+    assert out.size == n
+    _lib.check(lib.irec_normal_table_build(int(seed), int(n_samples), int(dim), int(steps), out.ctypes.data_as(ctypes.c_void_p),
+                                           int(n_threads)), "irec_normal_table_build")
+    return out
+
+
 class BlockLayout:
     """Descriptors of the blocks of `n_tensors` latent tensors of `n` dims each, cut into <= block_size slices of the
     shuffled order (coder.py:69-83).  Blocks are listed largest first so the persistent kernels end on short ones;
@@ -160,6 +179,8 @@ class Engine:
         self._ws = {}      # one scratch buffer per HIP stream: calls on different streams never share counters / slabs
         self._tls = threading.local()   # table_session(): key of the calling THREAD's previous call of a back-to-back run of twins
         self._dec_ws = {}  # decode scratch (proposal tables of a call) per HIP stream
+        self._normal_tables = {}   # (seed, S, dim, steps) -> device table of the sequential importance coder
+        self._normal_tables_lock = threading.Lock()
 
     def __del__(self):
         try:
@@ -401,6 +422,85 @@ class Engine:
                                                 _ptr(p_loc), _ptr(p_scale), int(seed), max_K, _ptr(K), _ptr(indices),
                                                 _ptr(sample), _ptr(ws), ws.numel() if ws is not None else 0,
                                                 self._stream()), "irec_beam_decode_ws")
+        return sample
+
+    # ---- the sequential importance coder (irec_gc_importance_encode / _decode) -------------------------------------------
+    NORMAL_TABLE_CACHE_BYTES = 2 << 30
+
+    def normal_tables(self, seed, n_samples, dims, steps):
+        """irec_normal_tables of a call: built on the host, uploaded and cached per (seed, S, dim, steps) -- the reference's
+        drivers code every image with one seed, so a run builds them once.  At most four distinct dims.
+        A caller that changes the seed per call rebuilds the tables on the host every time (milliseconds to seconds, by S x dim x
+        steps) and the cache holds up to NORMAL_TABLE_CACHE_BYTES of device memory before it is emptied wholesale; a table in use
+        by a kernel in flight stays alive through torch's stream-ordered allocator.  The cache is guarded by a lock (engines are
+        shared between threads)."""
+        dims = [int(d) for d in dims]
+        if not 1 <= len(dims) <= 4:
+            raise _lib.IrecLibraryError(f"a call names one to four distinct block dims, got {dims}")
+        tabs = []
+        with self._normal_tables_lock:
+            for d in dims:
+                key = (int(seed), int(n_samples), d, int(steps))
+                t = self._normal_tables.get(key)
+                if t is None:
+                    host = torch.from_numpy(build_normal_table(seed, n_samples, d, steps))
+                    held = sum(v.numel() * 4 for v in self._normal_tables.values())
+                    if held + host.numel() * 4 > self.NORMAL_TABLE_CACHE_BYTES:
+                        self._normal_tables.clear()
+                    t = host.to(self.device)
+                    self._normal_tables[key] = t
+                tabs.append(t)
+        c = _lib.IrecNormalTables()
+        for i, (d, t) in enumerate(zip(dims, tabs)):
+            c.table[i], c.dim[i] = t.data_ptr(), d
+        c.n_samples, c.steps = int(n_samples), int(steps)
+        return c, tabs
+
+    def gc_encode_blocks(self, lay, q_loc, q_scale, p_loc, p_scale, seed, kl_per_partition, n_samples, max_K, steps=None,
+                         order_by_K=True):
+        """Asynchronous.  GaussianCoder.encode over an ImportanceSampler (alpha = inf) on every block of `lay`: device tensors
+        (K [n_blocks], indices [n_blocks, max_K] -- max(K, 1) entries of a row count --, sample [like q_loc]), rows in `lay` order.
+        order_by_K: the blocks go to the kernel longest first (a workgroup codes one block at a time)."""
+        for t in (q_loc, q_scale, p_loc, p_scale):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
+            assert t.numel() == lay.n_tensors * lay.n
+        max_K = max(1, int(max_K))
+        steps = max_K if steps is None else max(int(steps), max_K)
+        tables, keep = self.normal_tables(seed, n_samples, lay.distinct_dims, steps)
+        base, pos, dim, order = lay.block_base, lay.block_pos, lay.block_dim, None
+        if order_by_K and lay.n_blocks > 1:
+            _, K0 = self.block_kl(self.params(kl_per_partition, n_samples, 1), lay, q_loc, q_scale, p_loc, p_scale)
+            order = torch.argsort(K0, descending=True, stable=True)
+            base, pos, dim = base[order], pos[order], dim[order]
+        out_K = torch.empty(lay.n_blocks, dtype=torch.int32, device=self.device)
+        out_idx = torch.zeros((lay.n_blocks, max_K), dtype=torch.int32, device=self.device)
+        sample = torch.empty_like(q_loc)
+        _lib.check(self.lib.irec_gc_importance_encode(self.ctx, lay.n_blocks, _ptr(base), _ptr(pos), _ptr(dim), _ptr(lay.perm),
+                                                      _ptr(q_loc), _ptr(q_scale), _ptr(p_loc), _ptr(p_scale), ctypes.byref(tables),
+                                                      float(np.float32(kl_per_partition)), max_K, _ptr(out_K), _ptr(out_idx),
+                                                      _ptr(sample), self._stream()), "irec_gc_importance_encode")
+        del keep
+        if order is not None:
+            K2, idx2 = torch.empty_like(out_K), torch.empty_like(out_idx)
+            K2[order] = out_K
+            idx2[order] = out_idx
+            out_K, out_idx = K2, idx2
+        return out_K, out_idx, sample
+
+    def gc_decode_blocks(self, lay, p_loc, p_scale, seed, n_samples, K, indices, steps=None):
+        """Asynchronous.  K / indices rows in `lay` order (max(K, 1) entries of a row count)."""
+        for t in (p_loc, p_scale):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
+        assert K.dtype == torch.int32 and indices.dtype == torch.int32 and indices.is_contiguous()
+        max_K = int(indices.shape[1])
+        steps = max_K if steps is None else max(int(steps), max_K)
+        tables, keep = self.normal_tables(seed, n_samples, lay.distinct_dims, steps)
+        sample = torch.empty_like(p_loc)
+        _lib.check(self.lib.irec_gc_importance_decode(self.ctx, lay.n_blocks, _ptr(lay.block_base), _ptr(lay.block_pos),
+                                                      _ptr(lay.block_dim), _ptr(lay.perm), _ptr(p_loc), _ptr(p_scale),
+                                                      ctypes.byref(tables), max_K, _ptr(K), _ptr(indices), _ptr(sample),
+                                                      self._stream()), "irec_gc_importance_decode")
+        del keep
         return sample
 
     # ---- test hooks ------------------------------------------------------------------------------------------------

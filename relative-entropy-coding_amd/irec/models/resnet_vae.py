@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..coding import BeamSearchCoder
+from ..coding import BeamSearchCoder, GaussianCoder, ImportanceSampler
 from ..coding.beam_search_coder import MorePartitionsNeeded, PendingCode, SplitNotResident
 
 
@@ -153,8 +153,11 @@ class BidirectionalResidualBlock(nn.Module):
             self.coder = BeamSearchCoder(kl_per_partition=kl_per_partition, n_beams=sampler_args['n_beams'],
                                          extra_samples=sampler_args['extra_samples'], name=f"encoder_for_{self.name}",
                                          **coder_args)
-        elif sampler in ("rejection", "importance"):
-            raise ModelError(f"sampler '{sampler}' is outside the beam-search path of this build")
+        elif sampler == "importance":                      # resnet_vae.py:126-131
+            self.coder = GaussianCoder(kl_per_partition=kl_per_partition, sampler=ImportanceSampler(**sampler_args),
+                                       name=f"encoder_for_{self.name}", **coder_args)
+        elif sampler == "rejection":
+            raise ModelError(f"sampler '{sampler}' is outside the beam-search and importance paths of this build")
         else:
             raise ModelError("Sampler must be one of ['rejection', 'importance', 'beam_search'],"
                              f"but got {sampler}!")
