@@ -181,7 +181,7 @@ irec_status irec_create_ex(int device, const float *lut10007, irec_context **out
  *   aux_ratios     host float [n_aux_ratios]: the FITTED auxiliary-variance ratios of a coder constructed with
  *                  extrapolate_auxiliary_ratios=False -- the values of its `aux_variable_variance_ratios` variable, which
  *                  GaussianCoder.get_auxiliary_ratio(index) returns in place of the power law (coder.py:203-231; the SGD fitter that
- *                  produces them, coder.py:233-410, stays on the caller's side: SURVEY.md §2).  Every entry must lie in (0, 1].
+ *                  produces them, coder.py:233-410, is irec_fit_aux_ratios below).  Every entry must lie in (0, 1].
  *                  A block whose K = ceil(KL / Omega) exceeds n_aux_ratios is NOT coded (out_K = K is still written, as for K > max_K):
  *                  the reference raises "KL divergence higher than auxiliary variables can account for" there (coder.py:222-229), and so
  *                  does the Python mirror.  The decoder treats such a row as not decodable.  irec_max_partitions(ctx) tells the bound. */
@@ -342,6 +342,49 @@ irec_status irec_gc_importance_decode(irec_context *ctx, int64_t n_blocks, const
                                       const int32_t *block_dim, const int32_t *perm, const float *p_loc, const float *p_scale,
                                       const irec_normal_tables *tables, int32_t max_K, const int32_t *K, const int32_t *indices,
                                       float *out_sample, void *hip_stream);
+
+/* ---- the fitter of the auxiliary-variance ratios: GaussianCoder.update_block_auxiliary_variance_ratios (coder.py:266-410) ----------
+ * For ratio = M .. 2 (M = the largest 1 + floor(KL / Omega) of the rows, coder.py:284): an SGD over the rows with at least `ratio`
+ * partitions finds the variance ratio whose auxiliary variable carries Omega nats and leaves Omega * (ratio - 1), the result is
+ * averaged into ratios[ratio - 1] (coder.py:385-389), and the rows are conditioned on a draw of that auxiliary variable
+ * (coder.py:390-408).  Arithmetic: DESIGN.md §3 "ratio fit" -- float64 over det_log / det_exp, canonical reduction trees; the device
+ * entry point and the host twin give the same bits.
+ *   q_loc .. p_scale  [n_rows, dim] float32, row-major; not modified (the conditional statistics live in the workspace)
+ *   normal_table      irec_normal_table_build(seed, n_samples = n_rows, dim, steps = table_steps): the draw of row n, dim d at fit step j
+ *                     (ratio = M - j) is element n * dim + d of tf.random.normal after tf.random.set_seed(seed + j).  The reference draws
+ *                     from TensorFlow's unseeded global generator there (aux_target.sample(), coder.py:393); here the fit is seeded.
+ *                     table_steps >= M - 1 (irec_fit_partitions tells M beforehand); may be NULL when M <= 1.
+ *   ratios, average_counts  HOST float32 [capacity], in/out: the coder's `aux_variable_variance_ratios` and `average_counts`
+ *                     (initially {1.} each, coder.py:203-212); *length entries are valid on entry, max(*length, M) on return
+ *                     (grown with zeros, coder.py:289-302)
+ *   out_iters         HOST int32 [M - 1]: SGD iterations of every fit step
+ *   workspace         irec_fit_workspace_bytes(n_rows, dim) bytes, 256-byte aligned: device memory for irec_fit_aux_ratios / irec_fit_partitions,
+ *                     host memory for irec_fit_aux_ratios_host
+ * irec_fit_aux_ratios enqueues one launch per SGD iteration in chunks and reads a `done` word between chunks: it SYNCHRONISES the stream
+ * and returns when the fit is over.  No kernel waits for another workgroup.  Two fits on two streams (two workspaces) may run at once.
+ * An infinite or NaN KL, M > IREC_MAX_PARTITIONS, M > capacity or a table of fewer than M - 1 steps: IREC_E_INVALID, nothing fitted.
+ * The host twin needs no GPU and no context; n_threads host threads over rows (0: one per core, at most 16). */
+typedef struct {
+  float kl_per_partition;      /* Omega (float32, coder.py:192) */
+  double relative_tolerance;   /* stop when |previous loss - loss| < this (coder.py:373) */
+  double learning_rate;        /* SGD step (coder.py:335) */
+  int32_t max_iters;           /* iterations per fit step, at most (coder.py:340); >= 1 */
+} irec_fit_params;
+size_t irec_fit_workspace_bytes(int64_t n_rows, int32_t dim);
+/* out_kl [n_rows] float32 canonical KL of every row, out_num [n_rows] = 1 + floor(kl / Omega) in float32 (coder.py:282-284): HOST memory. */
+irec_status irec_fit_partitions(irec_context *ctx, float kl_per_partition, int64_t n_rows, int32_t dim, const float *q_loc,
+                                const float *q_scale, const float *p_loc, const float *p_scale, float *out_kl, int32_t *out_num,
+                                void *workspace, size_t workspace_bytes, void *hip_stream);
+irec_status irec_fit_partitions_host(float kl_per_partition, int64_t n_rows, int32_t dim, const float *q_loc, const float *q_scale,
+                                     const float *p_loc, const float *p_scale, float *out_kl, int32_t *out_num, int32_t n_threads);
+irec_status irec_fit_aux_ratios(irec_context *ctx, const irec_fit_params *p, int64_t n_rows, int32_t dim, const float *q_loc,
+                                const float *q_scale, const float *p_loc, const float *p_scale, const float *normal_table,
+                                int32_t table_steps, float *ratios, float *average_counts, int32_t capacity, int32_t *length,
+                                int32_t *out_iters, void *workspace, size_t workspace_bytes, void *hip_stream);
+irec_status irec_fit_aux_ratios_host(const irec_fit_params *p, int64_t n_rows, int32_t dim, const float *q_loc, const float *q_scale,
+                                     const float *p_loc, const float *p_scale, const float *normal_table, int32_t table_steps,
+                                     float *ratios, float *average_counts, int32_t capacity, int32_t *length, int32_t *out_iters,
+                                     void *workspace, size_t workspace_bytes, int32_t n_threads);
 
 /* ---- .rec wire format: entropy coder of the index streams (host memory; the reference's is CPU Cython too) ------------ */
 const char *irec_io_last_error(void);

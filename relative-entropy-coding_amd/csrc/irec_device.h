@@ -80,17 +80,18 @@ __device__ __forceinline__ uint32_t hash_from_sum(int32_t sum) {
 }
 
 // ---- deterministic float64 log (same operation sequence as the test oracle's restatement) ------------------
-__device__ __forceinline__ double det_log(double x) {
-  uint64_t bits = (uint64_t)__double_as_longlong(x);
+// (__host__ too: the host twin of the ratio fit, irec_fit.hip, runs this very function)
+__host__ __device__ __forceinline__ double det_log(double x) {
+  uint64_t bits = __builtin_bit_cast(uint64_t, x);
   int64_t e = (int64_t)((bits >> 52) & 0x7FF);
   if (e == 0) {
     x = x * 18014398509481984.0;
-    bits = (uint64_t)__double_as_longlong(x);
+    bits = __builtin_bit_cast(uint64_t, x);
     e = (int64_t)((bits >> 52) & 0x7FF) - 54;
   }
   e -= 1023;
   bits = (bits & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull;
-  double m = __longlong_as_double((long long)bits);
+  double m = __builtin_bit_cast(double, bits);
   if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
   const double s = (m - 1.0) / (m + 1.0);
   const double s2 = s * s;
@@ -110,8 +111,36 @@ __device__ __forceinline__ double det_log(double x) {
   return (double)e * 0.6931471805599453 + lnm;
 }
 
+// ---- deterministic float64 exp: + - * / only (DESIGN.md §3 "ratio fit"; host and device run this one function) ----
+// x = k ln 2 + r, k = floor(x / ln 2 + 1/2), r by a two-word ln 2 (|r| <= 0.347); exp(r) = the degree-13 Taylor polynomial in
+// Horner form (truncation < 4e-18 relative); the result is scaled by 2^k through the exponent bits.  Below -708: 0, above 709: +inf,
+// NaN: NaN.  Measured against libm over [-40, 40]: at most 2 ulp (tests/test_ratio_fit_host.py).
+__host__ __device__ __forceinline__ double det_exp(double x) {
+  if (!(x == x)) return x;
+  if (x < -708.0) return 0.0;
+  if (x > 709.0) return __builtin_bit_cast(double, (uint64_t)0x7FF0000000000000ull);
+  const double kf = __builtin_floor(x * 1.4426950408889634 + 0.5);
+  const double r = (x - kf * 0.693147180369123816490) - kf * 1.90821492927058770002e-10;
+  double p = 1.0 / 6227020800.0;
+  p = p * r + 1.0 / 479001600.0;
+  p = p * r + 1.0 / 39916800.0;
+  p = p * r + 1.0 / 3628800.0;
+  p = p * r + 1.0 / 362880.0;
+  p = p * r + 1.0 / 40320.0;
+  p = p * r + 1.0 / 5040.0;
+  p = p * r + 1.0 / 720.0;
+  p = p * r + 1.0 / 120.0;
+  p = p * r + 1.0 / 24.0;
+  p = p * r + 1.0 / 6.0;
+  p = p * r + 0.5;
+  p = p * r + 1.0;
+  p = p * r + 1.0;
+  const int64_t k = (int64_t)kf;                                              // in [-1021, 1023]
+  return p * __builtin_bit_cast(double, (uint64_t)(k + 1023) << 52);
+}
+
 // KL(N(mq,sq) || N(mp,sp)) of one dim in float64 (canonical form of tfd.kl_divergence, beam_search_coder.py:57).
-__device__ __forceinline__ double kl_dim(float mq, float sq, float mp, float sp) {
+__host__ __device__ __forceinline__ double kl_dim(float mq, float sq, float mp, float sp) {
   const double t = (double)sq / (double)sp;
   const double r = t * t;
   const double dm = ((double)mq - (double)mp) / (double)sp;

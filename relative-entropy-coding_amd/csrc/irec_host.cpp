@@ -288,6 +288,13 @@ struct irec_context {
   unsigned long long *d_dbg = nullptr; // IREC_STAMPS=1 diagnostics only
 };
 
+// what irec_fit.hip (a translation unit with entry points of its own) needs of this one
+namespace irec {
+irec_status set_last_error(irec_status code, const char *who, const char *what) { return fail(code, "%s: %s", who, what); }
+int context_device(const irec_context *ctx) { return ctx->device; }
+int context_cus(const irec_context *ctx) { return ctx->n_cu > 0 ? ctx->n_cu : 256; }
+} // namespace irec
+
 extern "C" {
 
 const char *irec_last_error(void) { return g_last_error.c_str(); }

@@ -64,6 +64,12 @@ irec_status irec_tf_random_normal(int64_t seed, int64_t count, float *out);
  * stateless_gumbel_sample (rec/coding/utils.py:9-12).  Host memory; test hook. */
 irec_status irec_tf_stateless_normal(int64_t seed0, int64_t seed1, int64_t count, float *out);
 
+/* The ratio fitter (irec_fit.hip).  irec_test_fit_chunk: launches irec_fit_aux_ratios enqueues between two reads of its `done` word
+ * (<= 0: the default, 64); returns the previous value.  Results never depend on it.  irec_test_det_exp: out[i] = det_exp(in[i]), the
+ * float64 exponential of the fit (csrc/irec_device.h), on the host. */
+int32_t irec_test_fit_chunk(int32_t chunk);
+irec_status irec_test_det_exp(const double *in, int64_t n, double *out);
+
 /* ---- hand-offs of the RVAE model shim (device pointers, asynchronous; rec/models/resnet_vae.py:372-497) -------------------------
  * What lies between the convolutions of BidirectionalResidualBlock.call on the compression path, one launch each instead of
  * ~10 elementwise PyTorch launches per residual block and pass.  Activations NCHW float32 contiguous; statistics / latent NHWC.

@@ -48,6 +48,12 @@ class IrecNormalTables(ctypes.Structure):
     _fields_ = [("table", ctypes.c_void_p * 4), ("dim", ctypes.c_int32 * 4), ("n_samples", ctypes.c_int32), ("steps", ctypes.c_int32)]
 
 
+class IrecFitParams(ctypes.Structure):
+    """irec_fit_params of include/irec.h: the ratio fitter's parameters."""
+    _fields_ = [("kl_per_partition", ctypes.c_float), ("relative_tolerance", ctypes.c_double), ("learning_rate", ctypes.c_double),
+                ("max_iters", ctypes.c_int32)]
+
+
 class IrecPlanInfo(ctypes.Structure):
     """irec_plan_info of include/irec.h."""
     _fields_ = [("kernel", ctypes.c_char * 64), ("table_kernel", ctypes.c_char * 32), ("grid", ctypes.c_int32),
@@ -118,6 +124,15 @@ SIGNATURES = {
                                                  ctypes.c_float, _i32, _vp, _vp, _vp, _vp]),
     "irec_gc_importance_decode": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables), _i32,
                                                  _vp, _vp, _vp, _vp]),
+    "irec_fit_workspace_bytes": (ctypes.c_size_t, [_i64, _i32]),
+    "irec_fit_partitions": (ctypes.c_int, [_vp, ctypes.c_float, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_fit_partitions_host": (ctypes.c_int, [ctypes.c_float, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "irec_fit_aux_ratios": (ctypes.c_int, [_vp, ctypes.POINTER(IrecFitParams), _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32,
+                                           ctypes.POINTER(_i32), _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_fit_aux_ratios_host": (ctypes.c_int, [ctypes.POINTER(IrecFitParams), _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32,
+                                                ctypes.POINTER(_i32), _vp, _vp, ctypes.c_size_t, _i32]),
+    "irec_test_fit_chunk": (_i32, [_i32]),
+    "irec_test_det_exp": (ctypes.c_int, [_vp, _i64, _vp]),
     "irec_io_last_error": (ctypes.c_char_p, []),
     "irec_ac_encode": (ctypes.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _i64, ctypes.POINTER(_i64)]),
     "irec_ac_decode": (ctypes.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _i64, ctypes.POINTER(_i64)]),

@@ -1,10 +1,10 @@
 """Host mirror of rec/coding/coder.py (reference file:line in each docstring).
 
-The block split/merge bookkeeping, the auxiliary-variance ratios -- extrapolated (the power law), or FITTED ones handed over
-as data (round 5) -- and the sampler-driven GaussianCoder.encode / decode / encode_block / decode_block (coder.py:412-587):
-the reference's loop on the host for any Sampler object, the gfx950 kernels of csrc/irec_gc.hip for the ImportanceSampler at
-alpha = inf on GPU tensors.  The SGD ratio fitter that produces fitted ratios (coder.py:233-410) and the update_sampler branch
-are out of scope.
+The block split/merge bookkeeping, the auxiliary-variance ratios -- extrapolated (the power law), FITTED ones handed over
+as data, or fitted here by update_auxiliary_variance_ratios (coder.py:233-410: the kernels of csrc/irec_fit.hip for GPU tensors,
+their host twin for CPU tensors) -- and the sampler-driven GaussianCoder.encode / decode / encode_block / decode_block
+(coder.py:412-587): the reference's loop on the host for any Sampler object, the gfx950 kernels of csrc/irec_gc.hip for the
+ImportanceSampler at alpha = inf on GPU tensors.  The update_sampler branch is out of scope.
 """
 import abc
 
@@ -13,7 +13,7 @@ import torch
 
 from .utils import CodingError
 from .. import _lib
-from ..engine import Engine, NormalTableTooLarge, get_engine, tf_shuffle_perm
+from ..engine import Engine, FitError, NormalTableTooLarge, fit_aux_ratios_host, get_engine, tf_shuffle_perm
 
 AUX_RATIO_POWER_LAW = -0.7864636765648174  # coder.py:16
 
@@ -39,6 +39,25 @@ def _det_log(x):
     for k in (23, 21, 19, 17, 15, 13, 11, 9, 7, 5, 3):
         q = q * s2 + 1.0 / k
     return e.astype(np.float64) * 0.6931471805599453 + (2.0 * s + (2.0 * s) * (s2 * q))
+
+
+def _det_exp(x):
+    """The deterministic float64 exp of csrc/irec_device.h (det_exp), operation by operation."""
+    x = np.array(x, dtype=np.float64, copy=True).reshape(-1)
+    with np.errstate(all="ignore"):
+        xs = np.clip(np.nan_to_num(x, nan=0.0), -708.0, 709.0)
+        kf = np.floor(xs * 1.4426950408889634 + 0.5)
+        r = (xs - kf * 0.693147180369123816490) - kf * 1.90821492927058770002e-10
+        p = np.full_like(r, 1.0 / 6227020800.0)
+        for c in (479001600.0, 39916800.0, 3628800.0, 362880.0, 40320.0, 5040.0, 720.0, 120.0, 24.0, 6.0):
+            p = p * r + 1.0 / c
+        p = p * r + 0.5
+        p = p * r + 1.0
+        p = p * r + 1.0
+        scale = ((kf.astype(np.int64) + 1023).astype(np.uint64) << np.uint64(52)).view(np.float64)
+        out = p * scale
+    out = np.where(x < -708.0, 0.0, np.where(x > 709.0, np.inf, out))
+    return np.where(np.isnan(x), x, out)
 
 
 def canonical_partitions(mq, sq, mp, sp, omega):
@@ -152,22 +171,29 @@ class GaussianCoder(Coder):
         self.extrapolate_auxiliary_ratios = extrapolate_auxiliary_ratios
         if not self.extrapolate_auxiliary_ratios:          # coder.py:203-216: the variables a checkpoint restores
             self.aux_variable_variance_ratios = np.array([1.], dtype=np.float32)
+            self.average_counts = np.array([1.], dtype=np.float32)   # batch elements every ratio was averaged over
             self._initialized = False
+        self.last_fit_iters = None   # SGD iterations of every step of the last ratio fit (ratio = M .. 2)
         self.table_steps = 0         # steps the normal proposal tables of a device call cover; 0 = the default window
         self._max_K_hint = _lib.IREC_TABLE_STEPS_DEFAULT   # index slots per block of a device call (raised when a block needs more)
         self._K_seen, self._K_reads, self._split_strikes = 28, 0, 0   # (PendingCode's bookkeeping, shared with the beam coder)
         self.last_path = None        # "device" / "host": which path the sequential coder's last encode / decode call took
 
-    def set_auxiliary_variance_ratios(self, ratios):
+    def set_auxiliary_variance_ratios(self, ratios, average_counts=None):
         """The FITTED ratios of an extrapolate_auxiliary_ratios=False coder, as data: what the reference restores into
-        `aux_variable_variance_ratios` / `_initialized` from a checkpoint (coder.py:203-216).  The fitter itself
-        (update_auxiliary_variance_ratios, coder.py:233-410) stays on the caller's side."""
+        `aux_variable_variance_ratios` / `average_counts` / `_initialized` from a checkpoint (coder.py:203-216).
+        average_counts (None: ones): over how many batch elements every ratio was averaged -- a later
+        update_auxiliary_variance_ratios keeps averaging from there (coder.py:385-389)."""
         if self.extrapolate_auxiliary_ratios:
             raise CodingError("this coder extrapolates its auxiliary ratios (extrapolate_auxiliary_ratios=True)")
         r = np.ascontiguousarray(np.asarray(ratios, dtype=np.float32).reshape(-1))
         if r.size < 1 or not np.all((r > 0) & (r <= 1)):
             raise CodingError("auxiliary variance ratios must be a non-empty sequence of numbers in (0, 1]")
+        c = np.ones_like(r) if average_counts is None else np.ascontiguousarray(np.asarray(average_counts, dtype=np.float32).reshape(-1))
+        if c.shape != r.shape or not np.all(c >= 0):
+            raise CodingError("average_counts must hold one non-negative number per ratio")
         self.aux_variable_variance_ratios = r
+        self.average_counts = c
         self._initialized = True
         self._ratio_engine = None
 
@@ -186,12 +212,63 @@ class GaussianCoder(Coder):
                               "Requested {}".format(self.aux_variable_variance_ratios.shape[0], index + 1))
         return self.aux_variable_variance_ratios[index]
 
-    def update_auxiliary_variance_ratios(self, target_dist, coding_dist, seed=42, **kwargs):
-        """coder.py:233-264.  A no-op with extrapolated ratios (the coder is stateless); the SGD fit of
-        coder.py:265-410 is out of scope -- hand fitted ratios over with set_auxiliary_variance_ratios."""
-        if not self.extrapolate_auxiliary_ratios:
-            raise CodingError("fitting auxiliary variance ratios is outside the beam-search path: "
-                              "set_auxiliary_variance_ratios(ratios) takes fitted ones as data")
+    def update_auxiliary_variance_ratios(self, target_dist, coding_dist, seed=42, relative_tolerance=1e-4, max_iters=10000,
+                                         learning_rate=0.001):
+        """coder.py:233-264.  A no-op with extrapolated ratios (the coder is stateless).  Otherwise the rows of the
+        fit: with block_size=None the leading dim indexes them and the rest is flattened; with a block size every block BUT THE
+        LAST of every tensor of the leading batch after split(seed=seed) (the last is dropped even when it is full, coder.py:253-258).
+        `seed` also seeds the fit's auxiliary draws (DESIGN.md §3 "ratio fit": the reference's are unseeded)."""
+        if self.extrapolate_auxiliary_ratios:
+            return
+        stats = [torch.as_tensor(t).detach() for t in (target_dist.loc, target_dist.scale, coding_dist.loc, coding_dist.scale)]
+        if len({tuple(t.shape) for t in stats}) != 1:
+            raise CodingError("All tensor arguments supplied to split must have the same batch dimensions!")
+        if stats[0].ndim < 1 or stats[0].numel() < 1:
+            raise CodingError("update_auxiliary_variance_ratios needs at least one row")
+        if self.block_size is None:
+            rows = [t.reshape(t.shape[0], -1) for t in stats]
+        else:
+            per = [[] for _ in stats]
+            for i in range(stats[0].shape[0]):
+                blocks = self.split(*(t[i:i + 1] for t in stats), seed=seed)
+                for k, b in enumerate(blocks):
+                    per[k].extend(b[:-1])
+            if not per[0]:
+                raise CodingError("update_auxiliary_variance_ratios: no full block to fit to (every tensor has a single block, "
+                                  "and the last block of a tensor is left off, coder.py:253-258)")
+            rows = [torch.stack(b, dim=0) for b in per]
+        self.update_block_auxiliary_variance_ratios(_Dist(rows[0], rows[1]), _Dist(rows[2], rows[3]), seed=seed,
+                                                    relative_tolerance=relative_tolerance, max_iters=max_iters, learning_rate=learning_rate)
+
+    def update_block_auxiliary_variance_ratios(self, target_dist, coding_dist, seed=42, relative_tolerance=1e-4, max_iters=10000,
+                                               learning_rate=0.001):
+        """coder.py:266-410 over [rows, ...] statistics: the kernels of csrc/irec_fit.hip for GPU tensors, their host twin for CPU
+        tensors -- same bits (DESIGN.md §3 "ratio fit").  `last_path` says which one ran."""
+        if self.extrapolate_auxiliary_ratios:
+            return
+        stats = [torch.as_tensor(t).detach() for t in (target_dist.loc, target_dist.scale, coding_dist.loc, coding_dist.scale)]
+        if len({tuple(t.shape) for t in stats}) != 1:
+            raise CodingError("All tensor arguments supplied to split must have the same batch dimensions!")
+        if stats[0].ndim < 1 or stats[0].numel() < 1:
+            raise CodingError("update_auxiliary_variance_ratios needs at least one row")
+        if int(max_iters) < 1:
+            raise CodingError("max_iters must be at least 1")
+        n = stats[0].shape[0]
+        args = (seed, self.kl_per_partition, self.aux_variable_variance_ratios, self.average_counts, relative_tolerance, max_iters,
+                learning_rate)
+        try:
+            if stats[0].device.type == "cuda":
+                eng = get_engine(stats[0].device)
+                r, c, iters = eng.fit_aux_ratios(*(self._dev(t.reshape(n, -1), eng.device) for t in stats), *args)
+                self.last_path = "device"
+            else:
+                r, c, iters = fit_aux_ratios_host(*(self._host(t.reshape(n, -1)) for t in stats), *args)
+                self.last_path = "host"
+        except FitError as e:
+            raise CodingError(str(e))
+        self.aux_variable_variance_ratios, self.average_counts, self.last_fit_iters = r, c, [int(v) for v in iters]
+        self._initialized = True
+        self._ratio_engine = None    # the next encode builds a context over the new table
 
     # ---- the sequential coder (coder.py:412-587): any Sampler on the host, the ImportanceSampler of the reference's models
     #      (alpha = inf) in the gfx950 kernels behind irec_gc_importance_encode / _decode ---------------------------------

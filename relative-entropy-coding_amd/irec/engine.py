@@ -60,6 +60,69 @@ def build_normal_table(seed, n_samples, dim, steps, n_threads=0):
     return out
 
 
+class FitError(_lib.IrecLibraryError):
+    """The ratio fit cannot run on these rows (an infinite KL, more partitions than the build supports, a table that does not fit)."""
+
+
+def _fit_counts(kl, num):
+    if not np.all(np.isfinite(kl)):
+        raise FitError("a row's KL divergence is infinite or NaN: the auxiliary variance ratios cannot be fitted to it")
+    M = int(num.max())
+    if M > _lib.MAX_PARTITIONS:
+        raise FitError(f"KL divergence needs {M} partitions; this build supports {_lib.MAX_PARTITIONS}")
+    return M
+
+
+def _fit_state(ratios, counts, M):
+    """The two state arrays with room for M entries (irec_fit_aux_ratios grows them in place) and their length."""
+    ratios = np.asarray(ratios, dtype=np.float32).reshape(-1)
+    counts = np.asarray(counts, dtype=np.float32).reshape(-1)
+    assert ratios.size == counts.size >= 1
+    cap = max(M, ratios.size)
+    r, c = np.zeros(cap, dtype=np.float32), np.zeros(cap, dtype=np.float32)
+    r[:ratios.size], c[:counts.size] = ratios, counts
+    return r, c, ctypes.c_int32(ratios.size), np.zeros(max(M - 1, 1), dtype=np.int32)
+
+
+def _fit_params(kl_per_partition, relative_tolerance, max_iters, learning_rate):
+    return _lib.IrecFitParams(float(np.float32(kl_per_partition)), float(relative_tolerance), float(learning_rate), int(max_iters))
+
+
+def _fit_table(seed, n, D, M):
+    try:
+        return build_normal_table(seed, n, D, M - 1) if M > 1 else None
+    except NormalTableTooLarge as e:
+        raise FitError(f"the normal draws of a fit of {n} rows x {D} dims x {M - 1} steps do not fit: {e}")
+
+
+def fit_aux_ratios_host(q_loc, q_scale, p_loc, p_scale, seed, kl_per_partition, ratios, counts, relative_tolerance=1e-4,
+                        max_iters=10000, learning_rate=0.001, n_threads=0):
+    """irec_fit_aux_ratios_host: the ratio fit (coder.py:266-410) on host float32 [rows, D] arrays.  Returns the new
+    (ratios, average_counts) and the SGD iterations of every fit step.  Needs no GPU."""
+    lib = _lib.load()
+    arrs = [np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in (q_loc, q_scale, p_loc, p_scale)]
+    n, D = arrs[0].shape
+    assert all(a.shape == (n, D) for a in arrs)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    kl, num = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
+    _lib.check(lib.irec_fit_partitions_host(float(np.float32(kl_per_partition)), n, D, *(vp(a) for a in arrs), vp(kl), vp(num),
+                                            int(n_threads)), "irec_fit_partitions_host")
+    M = _fit_counts(kl, num)
+    r, c, length, iters = _fit_state(ratios, counts, M)
+    table = _fit_table(seed, n, D, M)
+    need = lib.irec_fit_workspace_bytes(n, D)
+    if not need:
+        raise FitError(f"a fit of {n} rows x {D} dims is out of range")
+    ws = np.empty(need + 256, dtype=np.uint8)
+    off = (-ws.ctypes.data) % 256
+    params = _fit_params(kl_per_partition, relative_tolerance, max_iters, learning_rate)
+    _lib.check(lib.irec_fit_aux_ratios_host(ctypes.byref(params), n, D, *(vp(a) for a in arrs),
+                                            vp(table) if table is not None else None, max(M - 1, 0), vp(r), vp(c), r.size,
+                                            ctypes.byref(length), vp(iters), ctypes.c_void_p(ws.ctypes.data + off), need, int(n_threads)),
+               "irec_fit_aux_ratios_host")
+    return r[:length.value].copy(), c[:length.value].copy(), iters[:max(M - 1, 0)].copy()
+
+
 class BlockLayout:
     """Descriptors of the blocks of `n_tensors` latent tensors of `n` dims each, cut into <= block_size slices of the
     shuffled order (coder.py:69-83).  Blocks are listed largest first so the persistent kernels end on short ones;
@@ -502,6 +565,33 @@ class Engine:
                                                       self._stream()), "irec_gc_importance_decode")
         del keep
         return sample
+
+    def fit_aux_ratios(self, q_loc, q_scale, p_loc, p_scale, seed, kl_per_partition, ratios, counts, relative_tolerance=1e-4,
+                       max_iters=10000, learning_rate=0.001):
+        """irec_fit_aux_ratios on the current stream: the ratio fit (coder.py:266-410) over device float32 [rows, D] tensors.
+        Synchronises the stream.  Same return as fit_aux_ratios_host, bit for bit."""
+        for t in (q_loc, q_scale, p_loc, p_scale):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and t.shape == q_loc.shape
+        n, D = q_loc.shape
+        need = self.lib.irec_fit_workspace_bytes(n, D)
+        if not need:
+            raise FitError(f"a fit of {n} rows x {D} dims is out of range")
+        ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        kl, num = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32)
+        _lib.check(self.lib.irec_fit_partitions(self.ctx, float(np.float32(kl_per_partition)), n, D, _ptr(q_loc), _ptr(q_scale),
+                                                _ptr(p_loc), _ptr(p_scale), vp(kl), vp(num), _ptr(ws), need, self._stream()),
+                   "irec_fit_partitions")
+        M = _fit_counts(kl, num)
+        r, c, length, iters = _fit_state(ratios, counts, M)
+        host = _fit_table(seed, n, D, M)
+        table = torch.from_numpy(host).to(self.device) if host is not None else None
+        params = _fit_params(kl_per_partition, relative_tolerance, max_iters, learning_rate)
+        _lib.check(self.lib.irec_fit_aux_ratios(self.ctx, ctypes.byref(params), n, D, _ptr(q_loc), _ptr(q_scale), _ptr(p_loc),
+                                                _ptr(p_scale), _ptr(table), max(M - 1, 0), vp(r), vp(c), r.size, ctypes.byref(length),
+                                                vp(iters), _ptr(ws), need, self._stream()), "irec_fit_aux_ratios")
+        del table, ws
+        return r[:length.value].copy(), c[:length.value].copy(), iters[:max(M - 1, 0)].copy()
 
     # ---- test hooks ------------------------------------------------------------------------------------------------
     def device_uniform_int(self, seed, n):

@@ -225,8 +225,16 @@ class BidirectionalResidualBlock(nn.Module):
                                torch.cat([m.weight for m in heads_g]).contiguous(), torch.cat([m.bias for m in heads_g]).contiguous())
         return self._fused[1:]
 
-    def forward(self, tensor, inference_pass=True, encoder_args=None, decoder_args=None):
-        """resnet_vae.py:372-497."""
+    def update_coders(self, **fit_args):
+        """resnet_vae.py:497-499: fit the coder's auxiliary variance ratios to the posterior / prior of the last pass."""
+        if self.posterior is None or self.prior is None:
+            raise ModelError(f"{self.name}: update_coders needs the posterior and prior of a pass over some images first")
+        self.coder.update_auxiliary_variance_ratios(target_dist=self.posterior, coding_dist=self.prior, **fit_args)
+
+    def forward(self, tensor, inference_pass=True, encoder_args=None, decoder_args=None, sample_args=None):
+        """resnet_vae.py:372-497.  sample_args={"generator": g}: the generative pass of the reference's `call` -- the latent is a
+        draw from the posterior (standard normals from the CPU generator g), nothing is coded; it leaves the block's posterior and
+        prior in place for update_coders."""
         inp = tensor
         pre = getattr(tensor, "_irec_elu", None)          # the previous block's residual kernel already formed elu(tensor)
         tensor = pre if pre is not None else F.elu(tensor)
@@ -252,17 +260,17 @@ class BidirectionalResidualBlock(nn.Module):
                 else:
                     tensor = self.infer_conv2(F.elu(y[:, 2 * s:]))
         else:
-            if encoder_args is None and decoder_args is None:
+            if encoder_args is None and decoder_args is None and sample_args is None:
                 raise ModelError("training / sampling passes are outside the compression shim")
-            if encoder_args is not None and self._infer_y is None:
+            if (encoder_args is not None or sample_args is not None) and self._infer_y is None:
                 raise ModelError(f"{self.name}: a compression pass needs the statistics of an inference pass over the same input first")
-            if encoder_args is not None and fused != (self._infer_bias is not None):
+            if (encoder_args is not None or sample_args is not None) and fused != (self._infer_bias is not None):
                 raise ModelError(f"{self.name}: use_handoff_kernels changed between the inference and the generative pass")
             y = F.conv2d(tensor, w_g, None if fused else b_g, padding=self._pad)  # [N, 4s + d, H, W]
             if fused:
                 y = y.contiguous()
             n, _, h, w = y.shape
-            if encoder_args is not None:                                          # :462-470
+            if encoder_args is not None or sample_args is not None:               # :462-470
                 if fused:
                     st = _HandOff.stats(y, self._infer_y, s, 4, b_g, self._infer_bias)   # all four statistics, NHWC, one launch
                 else:
@@ -270,7 +278,11 @@ class BidirectionalResidualBlock(nn.Module):
                     st = y[:, :4 * s].view(n, 4, s, h, w).permute(1, 0, 3, 4, 2).contiguous()   # coder sees NHWC, as in the reference
                     st[1::2].exp_()                                               # the two scales
                 self.prior, self.posterior = _Normal(st[0], st[1]), _Normal(st[2], st[3])
-                indices, latent_code = self.coder.encode(self.posterior, self.prior, **encoder_args)
+                if encoder_args is not None:
+                    indices, latent_code = self.coder.encode(self.posterior, self.prior, **encoder_args)
+                else:                                                             # :471-473, posterior.sample()
+                    noise = torch.randn(self.posterior.loc.shape, generator=sample_args["generator"], dtype=torch.float32)
+                    latent_code = self.posterior.loc + self.posterior.scale * noise.to(self.posterior.loc.device)
             else:                                                                 # :475-476
                 if fused:
                     st = _HandOff.stats(y, None, s, 2, b_g)                       # the SAME kernel and exp as the encoder's prior
@@ -328,6 +340,23 @@ class BidirectionalResNetVAE(nn.Module):
         pre = getattr(tensor, "_irec_elu", None)
         reconstruction = self.last_gen_conv(pre if pre is not None else F.elu(tensor))
         return torch.clamp(reconstruction, -0.5 + 1. / 512., 0.5 - 1. / 512.)
+
+    @torch.no_grad()
+    def update_coders(self, images, seed=42, **fit_args):
+        """resnet_vae.py:795-801: a forward pass over `images` ([N, 3, H, W]) sets the posterior and prior of every residual block
+        (the latents are posterior draws, seeded by `seed`), then every block's coder fits its auxiliary variance ratios to them
+        (GaussianCoder.update_auxiliary_variance_ratios; fit_args: relative_tolerance, max_iters, learning_rate)."""
+        batch_size, _, height, width = images.shape
+        with deterministic_transforms():
+            tensor = self.first_infer_conv(images)
+            for resnet_block in list(self.residual_blocks)[::-1]:
+                tensor = resnet_block(tensor, inference_pass=True)
+            tensor = self.generative_base(batch_size=batch_size, width=width, height=height)
+            generator = torch.Generator().manual_seed(int(seed))
+            for resnet_block in self.residual_blocks:
+                tensor = resnet_block(tensor, inference_pass=False, sample_args={"generator": generator})
+        for resnet_block in self.residual_blocks:
+            resnet_block.update_coders(seed=seed, **fit_args)
 
     @torch.no_grad()
     def compress(self, image, seed, update_sampler=False):
