@@ -322,11 +322,12 @@ typedef struct {
   int32_t steps;
 } irec_normal_tables;
 
-/* Encode n_blocks blocks (layout arguments as irec_beam_encode; blocks of at most 1024 dims).  Asynchronous, no workspace.
+/* Encode n_blocks blocks (layout arguments as irec_beam_encode; blocks of at most 1024 dims -- wider ones: the _ws entry below).
+ * Asynchronous, no workspace.
  *   max_K       index slots per row, 1 <= max_K <= tables->steps
  *   out_K       [n_blocks] K = ceil(KL / kl_per_partition) of each block (the K of irec_block_kl).  K > max_K: not coded, call
  *               again with a longer window; K > irec_max_partitions(ctx) (fitted ratios): not coded; -1: no table of the block's
- *               dim, or more than 1024 dims
+ *               dim, or (this entry only) more than 1024 dims
  *   out_indices [n_blocks, max_K]: idx[t], t < max(K, 1), the sample chosen at step t (rest untouched)
  *   out_sample  flat, indexed as the inputs (merged)
  * Hand the blocks over longest first (by K): a workgroup codes one block at a time. */
@@ -335,6 +336,21 @@ irec_status irec_gc_importance_encode(irec_context *ctx, int64_t n_blocks, const
                                       const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
                                       float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
                                       float *out_sample, void *hip_stream);
+/* The same for blocks of ANY dim: the remaining limit is the size of the tables (IREC_TABLE_BYTES_HARD, IREC_TABLE_STEPS_MAX).
+ * The call's largest block is the largest tables->dim[i] that has a table.  At most 1024 dims: dispatched exactly as
+ * irec_gc_importance_encode -- same kernel, same launch, the workspace is ignored (it may be NULL).  More: one kernel codes every
+ * block of the call, narrow ones included (the same bits: DESIGN.md §3), and keeps a block's state in a slab of the workspace,
+ * four float arrays of max_block_dim rounded up to 1024 per workgroup.
+ * GRID RULE: min(n_blocks, compute units of the context) workgroups of 1024 lanes, each coding one block at a time;
+ * irec_gc_encode_workspace_bytes = that many slabs (rounded up to 256 bytes), 0 when max_block_dim <= 1024 or n_blocks == 0.
+ * A workspace that is NULL, not 256-byte aligned or smaller than that: IREC_E_WORKSPACE with the needed size in irec_last_error;
+ * nothing is launched and the outputs are untouched. */
+size_t irec_gc_encode_workspace_bytes(irec_context *ctx, int64_t n_blocks, int32_t max_block_dim);
+irec_status irec_gc_importance_encode_ws(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
+                                         const int32_t *block_dim, const int32_t *perm, const float *q_loc, const float *q_scale,
+                                         const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
+                                         float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
+                                         float *out_sample, void *workspace, size_t workspace_bytes, void *hip_stream);
 /* Decode: K [n_blocks], indices [n_blocks, max_K] in encoder order, max(K, 1) entries per row.  A row with K < 0, K > max_K,
  * K > irec_max_partitions(ctx), an index outside [0, n_samples) or a dim without a table decodes to p_loc, as irec_beam_decode
  * promises; any block dim with a table is served. */

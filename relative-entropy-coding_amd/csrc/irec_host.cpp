@@ -1657,17 +1657,41 @@ static irec_status gc_fill(const char *who, irec_context *ctx, int64_t n_blocks,
   return IREC_OK;
 }
 
-irec_status irec_gc_importance_encode(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
-                                      const int32_t *block_dim, const int32_t *perm, const float *q_loc, const float *q_scale,
-                                      const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
-                                      float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
-                                      float *out_sample, void *hip_stream) {
+// The wide encoder's grid: one workgroup of 1024 lanes per block, at most one per compute unit (its registers leave room for one:
+// every workgroup of the grid is resident); the workspace holds one slab per workgroup of that grid.
+static int gc_wide_grid(const irec_context *ctx, int64_t n_blocks) { return (int)std::min<int64_t>(n_blocks, (int64_t)ctx->n_cu); }
+static size_t gc_wide_slab_dim(int32_t max_block_dim) { return round_up_sz((size_t)max_block_dim, (size_t)irec::GC_WIDE_THREADS); }
+
+size_t irec_gc_encode_workspace_bytes(irec_context *ctx, int64_t n_blocks, int32_t max_block_dim) {
+  if (!ctx || n_blocks < 0 || max_block_dim < 0) {
+    fail(IREC_E_INVALID, "irec_gc_encode_workspace_bytes: bad arguments");
+    return 0;
+  }
+  if (max_block_dim <= irec::GC_MAX_DIM || n_blocks == 0) return 0;
+  return round_up_sz((size_t)gc_wide_grid(ctx, n_blocks) * 4 * gc_wide_slab_dim(max_block_dim) * sizeof(float), 256);
+}
+
+// wide: the kernel of any block dim over slabs of `workspace` (irec_gc_importance_encode_ws with a block of more than 1024 dims)
+static irec_status gc_encode(const char *who, bool ws_entry, irec_context *ctx, int64_t n_blocks, const int64_t *block_base,
+                             const int32_t *block_pos, const int32_t *block_dim, const int32_t *perm, const float *q_loc,
+                             const float *q_scale, const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
+                             float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices, float *out_sample,
+                             void *workspace, size_t workspace_bytes, void *hip_stream) {
   irec::GcArgs G{};
-  if (irec_status s = gc_fill("irec_gc_importance_encode", ctx, n_blocks, block_base, block_pos, block_dim, tables, max_K, G)) return s;
-  if (!(kl_per_partition > 0.0f)) return fail(IREC_E_INVALID, "irec_gc_importance_encode: kl_per_partition must be positive");
+  if (irec_status s = gc_fill(who, ctx, n_blocks, block_base, block_pos, block_dim, tables, max_K, G)) return s;
+  if (!(kl_per_partition > 0.0f)) return fail(IREC_E_INVALID, "%s: kl_per_partition must be positive", who);
   if (n_blocks == 0) return IREC_OK;
   if (!q_loc || !q_scale || !p_loc || !p_scale || !out_K || !out_indices || !out_sample)
-    return fail(IREC_E_INVALID, "irec_gc_importance_encode: null pointer argument");
+    return fail(IREC_E_INVALID, "%s: null pointer argument", who);
+  int32_t max_dim = 0;   // the call's largest block: every block that is coded has a table of its dim
+  for (int i = 0; i < 4; ++i)
+    if (G.tab[i]) max_dim = std::max(max_dim, G.tab_dim[i]);
+  const bool wide = ws_entry && max_dim > irec::GC_MAX_DIM;
+  if (wide) {
+    const size_t need = irec_gc_encode_workspace_bytes(ctx, n_blocks, max_dim);
+    if (!workspace || workspace_bytes < need) return fail(IREC_E_WORKSPACE, "%s: workspace %zu bytes < required %zu", who, workspace_bytes, need);
+    if (((uintptr_t)workspace & 255) != 0) return fail(IREC_E_WORKSPACE, "%s: workspace must be 256-byte aligned", who);
+  }
   IREC_ON_DEVICE(ctx->device);
   irec::EncArgs A{};   // K = ceil(KL / Omega) of every block into out_K: the kernel of irec_block_kl
   A.block_base = block_base; A.block_pos = block_pos; A.block_dim = block_dim; A.perm = perm;
@@ -1676,8 +1700,31 @@ irec_status irec_gc_importance_encode(irec_context *ctx, int64_t n_blocks, const
   HIP_TRY(irec::launch_block_kl(A, nullptr, (int)std::min<int64_t>(n_blocks, 8LL * ctx->n_cu), (hipStream_t)hip_stream));
   G.perm = perm; G.q_loc = q_loc; G.q_scale = q_scale; G.p_loc = p_loc; G.p_scale = p_scale;
   G.out_K = out_K; G.out_indices = out_indices; G.out_sample = out_sample;
+  if (wide) {
+    G.slab = static_cast<float *>(workspace); G.slab_dim = (int32_t)gc_wide_slab_dim(max_dim);
+    HIP_TRY(irec::launch_gc_importance_encode_wide(G, gc_wide_grid(ctx, n_blocks), (hipStream_t)hip_stream));
+    return IREC_OK;
+  }
   HIP_TRY(irec::launch_gc_importance_encode(G, (int)std::min<int64_t>(n_blocks, 16LL * ctx->n_cu), (hipStream_t)hip_stream));
   return IREC_OK;
+}
+
+irec_status irec_gc_importance_encode(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
+                                      const int32_t *block_dim, const int32_t *perm, const float *q_loc, const float *q_scale,
+                                      const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
+                                      float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
+                                      float *out_sample, void *hip_stream) {
+  return gc_encode("irec_gc_importance_encode", false, ctx, n_blocks, block_base, block_pos, block_dim, perm, q_loc, q_scale, p_loc,
+                   p_scale, tables, kl_per_partition, max_K, out_K, out_indices, out_sample, nullptr, 0, hip_stream);
+}
+
+irec_status irec_gc_importance_encode_ws(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
+                                         const int32_t *block_dim, const int32_t *perm, const float *q_loc, const float *q_scale,
+                                         const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
+                                         float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
+                                         float *out_sample, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  return gc_encode("irec_gc_importance_encode_ws", true, ctx, n_blocks, block_base, block_pos, block_dim, perm, q_loc, q_scale, p_loc,
+                   p_scale, tables, kl_per_partition, max_K, out_K, out_indices, out_sample, workspace, workspace_bytes, hip_stream);
 }
 
 irec_status irec_gc_importance_decode(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,

@@ -217,7 +217,8 @@ hipError_t launch_shim_cat_elu(const float *y, const float *latent, float *out, 
 hipError_t launch_shim_residual_elu(const float *inp, const float *t, float alpha, float *out, float *out_elu, int64_t count,
                                     const float *bt, int C, int HW, hipStream_t st);
 // the sequential importance coder (irec_gc.hip): GaussianCoder.encode_block / decode_block over an ImportanceSampler, alpha = inf
-constexpr int GC_MAX_DIM = 1024;    // dims of a block the encoder keeps in LDS
+constexpr int GC_MAX_DIM = 1024;    // dims of a block the encoder keeps in LDS; wider blocks: the wide kernel over a slab of the workspace
+constexpr int GC_WIDE_THREADS = 1024;   // lanes of the wide kernel's workgroup = dims of a chunk
 struct GcArgs {
   const int64_t *block_base; const int32_t *block_pos; const int32_t *block_dim; const int32_t *perm;
   const float *q_loc, *q_scale, *p_loc, *p_scale;   // (the decoder reads p only)
@@ -229,9 +230,11 @@ struct GcArgs {
   int32_t *out_K; int32_t *out_indices;      // encoder: out_K holds ceil(KL / Omega) on entry (block_kl_kernel)
   const int32_t *K; const int32_t *indices;  // decoder
   float *out_sample;
+  float *slab; int32_t slab_dim;             // wide encoder: [grid][4][slab_dim] floats of the workspace, slab_dim a multiple of 1024
 };
 int gc_encode_threads(int S);
 hipError_t launch_gc_importance_encode(const GcArgs &A, int grid, hipStream_t st);
+hipError_t launch_gc_importance_encode_wide(const GcArgs &A, int grid, hipStream_t st);
 hipError_t launch_gc_importance_decode(const GcArgs &A, int grid, hipStream_t st);
 hipError_t launch_dec_sqrt_test(unsigned long long *out, hipStream_t st);
 hipError_t launch_uniform_int(int64_t seed, int64_t n, int32_t *out, hipStream_t st);

@@ -122,6 +122,9 @@ SIGNATURES = {
     "irec_normal_table_build": (ctypes.c_int, [_i64, _i32, _i32, _i32, _vp, _i32]),
     "irec_gc_importance_encode": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables),
                                                  ctypes.c_float, _i32, _vp, _vp, _vp, _vp]),
+    "irec_gc_encode_workspace_bytes": (ctypes.c_size_t, [_vp, _i64, _i32]),
+    "irec_gc_importance_encode_ws": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables),
+                                                    ctypes.c_float, _i32, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "irec_gc_importance_decode": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables), _i32,
                                                  _vp, _vp, _vp, _vp]),
     "irec_fit_workspace_bytes": (ctypes.c_size_t, [_i64, _i32]),

@@ -4,7 +4,8 @@ The block split/merge bookkeeping, the auxiliary-variance ratios -- extrapolated
 as data, or fitted here by update_auxiliary_variance_ratios (coder.py:233-410: the kernels of csrc/irec_fit.hip for GPU tensors,
 their host twin for CPU tensors) -- and the sampler-driven GaussianCoder.encode / decode / encode_block / decode_block
 (coder.py:412-587): the reference's loop on the host for any Sampler object, the gfx950 kernels of csrc/irec_gc.hip for the
-ImportanceSampler at alpha = inf on GPU tensors.  The update_sampler branch is out of scope.
+ImportanceSampler at alpha = inf on GPU tensors -- blocks of any dim, block_size=None included; the size of the normal proposal
+tables (IREC_TABLE_BYTES_HARD, IREC_TABLE_STEPS_MAX) is the remaining limit.  The update_sampler branch is out of scope.
 """
 import abc
 
@@ -272,8 +273,6 @@ class GaussianCoder(Coder):
 
     # ---- the sequential coder (coder.py:412-587): any Sampler on the host, the ImportanceSampler of the reference's models
     #      (alpha = inf) in the gfx950 kernels behind irec_gc_importance_encode / _decode ---------------------------------
-    DEVICE_MAX_DIM = 1024    # dims of a block the kernels keep in LDS (csrc/irec_gc.hip)
-
     def get_codelength(self, indicies):
         """coder.py:586-587."""
         return sum([self.sampler.get_codelength(i) for i in indicies])
@@ -283,16 +282,14 @@ class GaussianCoder(Coder):
         return int(self.table_steps) if self.table_steps else _lib.IREC_TABLE_STEPS_DEFAULT
 
     def _on_device(self, loc, block_size):
-        """The kernels take the call: the reference's own ImportanceSampler at alpha = inf, tensors on the GPU, blocks of at most
-        DEVICE_MAX_DIM dims.  Everything else runs the reference's loop on the host."""
+        """The kernels take the call: the reference's own ImportanceSampler at alpha = inf, tensors on the GPU, blocks of any dim
+        (the size of the proposal tables is the remaining limit: NormalTableTooLarge sends a call to the host loop).  Everything
+        else runs the reference's loop on the host."""
         from .samplers import ImportanceSampler
         if type(self.sampler) is not ImportanceSampler or not (self.sampler.alpha == np.inf):
             return False
         t = torch.as_tensor(loc)
-        if t.device.type != "cuda" or t.ndim < 2 or t.shape[0] < 1 or t[0].numel() < 1:
-            return False
-        n = t[0].numel()
-        return min(n, n if block_size is None else int(block_size)) <= self.DEVICE_MAX_DIM
+        return t.device.type == "cuda" and t.ndim >= 2 and t.shape[0] >= 1 and t[0].numel() >= 1
 
     def _engine_for(self, tensor):
         t = torch.as_tensor(tensor)
@@ -490,7 +487,7 @@ class GaussianCoder(Coder):
                 pass
         if defer:
             raise CodingError("defer=True needs the device path: an ImportanceSampler with alpha = inf, tensors on the GPU, "
-                              f"blocks of at most {self.DEVICE_MAX_DIM} dims whose proposal tables fit")
+                              "and proposal tables that fit (IREC_TABLE_BYTES_HARD, IREC_TABLE_STEPS_MAX)")
         if batched:
             loc, scale = torch.as_tensor(target_dist.loc), torch.as_tensor(target_dist.scale)
             c_loc, c_scale = torch.as_tensor(coding_dist.loc), torch.as_tensor(coding_dist.scale)

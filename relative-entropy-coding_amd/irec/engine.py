@@ -523,7 +523,8 @@ class Engine:
                          order_by_K=True):
         """Asynchronous.  GaussianCoder.encode over an ImportanceSampler (alpha = inf) on every block of `lay`: device tensors
         (K [n_blocks], indices [n_blocks, max_K] -- max(K, 1) entries of a row count --, sample [like q_loc]), rows in `lay` order.
-        order_by_K: the blocks go to the kernel longest first (a workgroup codes one block at a time)."""
+        order_by_K: the blocks go to the kernel longest first (a workgroup codes one block at a time).  Blocks of any dim whose
+        tables fit (NormalTableTooLarge otherwise): a call with a block of more than 1024 dims runs the wide kernel over a workspace."""
         for t in (q_loc, q_scale, p_loc, p_scale):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
             assert t.numel() == lay.n_tensors * lay.n
@@ -538,11 +539,15 @@ class Engine:
         out_K = torch.empty(lay.n_blocks, dtype=torch.int32, device=self.device)
         out_idx = torch.zeros((lay.n_blocks, max_K), dtype=torch.int32, device=self.device)
         sample = torch.empty_like(q_loc)
-        _lib.check(self.lib.irec_gc_importance_encode(self.ctx, lay.n_blocks, _ptr(base), _ptr(pos), _ptr(dim), _ptr(lay.perm),
-                                                      _ptr(q_loc), _ptr(q_scale), _ptr(p_loc), _ptr(p_scale), ctypes.byref(tables),
-                                                      float(np.float32(kl_per_partition)), max_K, _ptr(out_K), _ptr(out_idx),
-                                                      _ptr(sample), self._stream()), "irec_gc_importance_encode")
-        del keep
+        # blocks of more than 1024 dims keep their state in slabs of a workspace (csrc/irec_gc.hip, the wide kernel); 0 bytes otherwise
+        ws_bytes = self.lib.irec_gc_encode_workspace_bytes(self.ctx, lay.n_blocks, max(int(d) for d in lay.distinct_dims))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device) if ws_bytes else None
+        _lib.check(self.lib.irec_gc_importance_encode_ws(self.ctx, lay.n_blocks, _ptr(base), _ptr(pos), _ptr(dim), _ptr(lay.perm),
+                                                         _ptr(q_loc), _ptr(q_scale), _ptr(p_loc), _ptr(p_scale), ctypes.byref(tables),
+                                                         float(np.float32(kl_per_partition)), max_K, _ptr(out_K), _ptr(out_idx),
+                                                         _ptr(sample), _ptr(ws), ws_bytes, self._stream()),
+                   "irec_gc_importance_encode_ws")
+        del keep, ws
         if order is not None:
             K2, idx2 = torch.empty_like(out_K), torch.empty_like(out_idx)
             K2[order] = out_K
