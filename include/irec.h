@@ -94,7 +94,7 @@ typedef struct {
 #define IREC_TABLE_BYTES_BIG (4ull << 30)   /* the bound of calls whose blocks exceed 1024 dims (block_size = None on a whole tensor:  */
                                             /* K grows with the dims -- an 8192-dim block has ~60 partitions of 590 KB of rows each)   */
 
-/* What irec_beam_encode does for a given call: filled by irec_encode_plan (same decision code as the launch). */
+/* What irec_beam_encode does for a given call: filled by irec_encode_plan from the settled plan the launch itself runs from. */
 typedef struct {
   char kernel[64];         /* block kernel, e.g. "encode_team_kernel<20,2,1>"                                   */
   char table_kernel[32];   /* who builds the proposal tables: "prep_kernel (copy bits)" / "prep_kernel (plain rows)" -- the call's one */

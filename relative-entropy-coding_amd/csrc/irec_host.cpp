@@ -538,7 +538,8 @@ struct Plan {
   int gang_blocks;   // chunk plans: blocks of one call that gangs of teams may code (0: no gang build for the shape), and
   size_t gang_stride, gang_bytes;   // the exchange of one block / of all, behind the slabs
 };
-size_t plan_ws_bytes(const Plan &pl) { return irec::WS_HEAD_BYTES + pl.tab_bytes + (size_t)pl.grid_cap * pl.ws_per_wg + pl.gang_bytes; }
+size_t plan_fixed_bytes(const Plan &pl) { return irec::WS_HEAD_BYTES + pl.tab_bytes + pl.gang_bytes; }   // (everything but the slabs)
+size_t plan_ws_bytes(const Plan &pl) { return plan_fixed_bytes(pl) + (size_t)pl.grid_cap * pl.ws_per_wg; }
 
 // steps of proposal tables the byte bounds allow at `per_step` bytes per step: what IREC_TABLE_BYTES_MAX holds, but not fewer
 // than IREC_TABLE_STEPS_FLOOR while those stay within IREC_TABLE_BYTES_HARD
@@ -561,10 +562,9 @@ irec_status check_params(const irec_params *p) {
   return IREC_OK;
 }
 
-Plan make_plan(const irec_context *ctx, const irec_params *p, int32_t max_dim, int32_t max_K) {
+Plan make_plan(int n_cu, const irec_params *p, int32_t max_dim, int32_t max_K) {
   Plan pl;
   const int B = p->n_beams, S = p->n_samples;
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
   pl.shape = (p->flags & IREC_FLAG_SHAPE_MASK) >> IREC_FLAG_SHAPE_SHIFT;
   pl.dpad = round_up(max_dim > 0 ? max_dim : 1, 256);
   pl.fast = !(p->flags & IREC_FLAG_FORCE_GENERIC) && max_dim <= irec::FAST_MAX_DIM && irec::fast_nb_for(B) != 0 &&
@@ -669,9 +669,6 @@ Plan make_plan(const irec_context *ctx, const irec_params *p, int32_t max_dim, i
   return pl;
 }
 
-// (defined below) workgroups of the chunked encoder for a call: one per CU, not more than blocks nor than the plan's slabs
-static int chunk_grid(const irec_context *ctx, const Plan &pl, const irec_params *p, int64_t n_blocks);
-
 // Workgroups of a persistent batch encoder (team / one-beam): one per CU, not more than blocks -- rounded up to a multiple of
 // 8 where that fits, so that hand-out slot u runs on XCD u mod 8 (irec_fast_common.h: xcd_static_row); the extra workgroups
 // find no row and leave.
@@ -680,8 +677,8 @@ static int batch_grid(int64_t n_blocks, int cap) {
   return (int)(r <= cap ? r : g);
 }
 
-static int chunk_grid(const irec_context *ctx, const Plan &pl, const irec_params *p, int64_t n_blocks) {
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
+// workgroups of the chunked encoder for a call: one per CU, not more than blocks nor than the plan's slabs
+static int chunk_grid(int n_cu, const Plan &pl, const irec_params *p, int64_t n_blocks) {
   const int teams = std::max(1, irec::chunk_teams(p->n_beams, p->n_samples));
   return batch_grid(n_blocks, std::min(n_cu, std::max(1, pl.grid_cap / teams)));
 }
@@ -689,10 +686,9 @@ static int chunk_grid(const irec_context *ctx, const Plan &pl, const irec_params
 // latents -- has G teams code each block together, a chunk of 1024 dims (or several) per member.  All n_blocks * G teams must be resident
 // at once (one static hand-out slot each; they wait for each other twice per step).  Returns G (0: every block on one team) and the
 // grid that puts the members on CUs of their own as far as the CUs go.
-int gang_width(const irec_context *ctx, const Plan &pl, const irec_params *p, int64_t n_blocks, int32_t max_block_dim, int *grid, int *chunk_owners) {
+int gang_width(int n_cu, const Plan &pl, const irec_params *p, int64_t n_blocks, int32_t max_block_dim, int *grid, int *chunk_owners) {
   if (!pl.chunk || pl.gang_blocks < 1 || n_blocks < 1 || n_blocks > pl.gang_blocks || (p->flags & (IREC_FLAG_NO_SPLIT | IREC_FLAG_MARGINS))) return 0;
   if (!irec::IREC_COOP_GRANULES_ON) return 0;   // (the gangs' arrival counters are exchange granules: zeroed by the preparation kernel only in that form)
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
   const int teams = irec::chunk_gang_teams(p->n_beams, p->n_samples);   // (of the gang build: three, or one for the shapes without a three-team build)
   if (teams < 1) return 0;
   const int wgs = std::min(n_cu, std::max(1, pl.grid_cap / teams));
@@ -722,8 +718,7 @@ int gang_width(const irec_context *ctx, const Plan &pl, const irec_params *p, in
 // Calls of fewer blocks than this take the one-table / split encoders (cheaper set-up: a 6 us plain table and 40 KB of LDS to fill, against
 // the bank assignment and 120 KB); from here on the team encoder.  A QUARTER OF THE CUs -- 64 on the 256-CU device the crossover was measured
 // on (r02b, r03m) -- within what the split encoder's arrival counters hold (COOP_SPLIT_MAX_BLOCKS) and not below 8.
-int small_call_blocks(const irec_context *ctx) {
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
+int small_call_blocks(int n_cu) {
   return std::max(8, std::min(irec::COOP_SPLIT_MAX_BLOCKS, n_cu / 4));
 }
 
@@ -731,12 +726,11 @@ int small_call_blocks(const irec_context *ctx) {
 // per block, each scoring a stripe of the samples (irec_kernels.hip).  All n_blocks * W workgroups must be resident at once
 // (they wait for each other every step), so the grid stays within HALF the CUs -- room for a second such call on another
 // stream -- and W within what the exchange buffers hold.  0 = not split.
-int split_width(const irec_context *ctx, const Plan &pl, const irec_params *p, int64_t n_blocks) {
+int split_width(int n_cu, const Plan &pl, const irec_params *p, int64_t n_blocks) {
   if (!pl.table || pl.chunk || (p->flags & IREC_FLAG_NO_SPLIT)) return 0;
   const int B = p->n_beams, S = p->n_samples, nb = irec::fast_nb_for(B);
   if (!nb || irec::fast_waves_for(B, S, true) != 4 || (int64_t)S * nb > 1024) return 0;   // aliased-key 4-wave builds only
   if (n_blocks < 1 || n_blocks > irec::COOP_SPLIT_MAX_BLOCKS) return 0;
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
   int64_t W = (n_cu / 2) / n_blocks;
   W = std::min<int64_t>(W, S);                                             // at least one sample per workgroup
   const int want = (p->flags & IREC_FLAG_SPLIT_MASK) >> IREC_FLAG_SPLIT_SHIFT;
@@ -770,10 +764,9 @@ int split_beam_width(const irec_params *p, int W) {
 // 126 blocks 0.331 -> 0.287, 162 blocks 0.332 -> 0.312 (three partners or more; with two the per-step wait for the slower partner
 // costs more than half a step's scoring saves: 180 blocks 0.332 -> 0.368); B = 10 (whose default build has three 4-wave teams of which
 // such a call uses one): 72 blocks 0.159 -> 0.134, 252 blocks 0.183 -> 0.168 -- also with two partners.
-bool share_all_auto(const irec_context *ctx, const Plan &pl, const irec_params *p, int64_t n_blocks) {
+bool share_all_auto(int n_cu, const Plan &pl, const irec_params *p, int64_t n_blocks) {
   if (!pl.team || pl.lone || pl.team_only || pl.chunk || !pl.table || (p->flags & IREC_FLAG_NO_SPLIT)) return false;
-  if ((p->flags & IREC_FLAG_SHAPE_MASK) != 0 || n_blocks < small_call_blocks(ctx) || n_blocks > irec::COOP_MAX_BLOCKS) return false;
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
+  if ((p->flags & IREC_FLAG_SHAPE_MASK) != 0 || n_blocks < small_call_blocks(n_cu) || n_blocks > irec::COOP_MAX_BLOCKS) return false;
   const int B = p->n_beams, S = p->n_samples;
   if (B > 20 || irec::team_shareable(B, S, 2) != 2 || irec::team_lds_for(B, S, 2) == (size_t)-1 ||
       irec::team_ws_extra_for(B, S, 2) > irec::team_ws_extra_for(B, S, 0) || irec::team_count_for(B, S, 0) < 2)
@@ -784,17 +777,16 @@ bool share_all_auto(const irec_context *ctx, const Plan &pl, const irec_params *
   if (B <= 10 && !(p->flags & IREC_FLAG_NO_TEN) && irec::ten_applies(B, S)) return false;
   return B > 10 ? W >= 3 : (W >= 2 && n_blocks <= n_cu);
 }
-int team_share_width(const irec_context *ctx, const Plan &pl, const irec_params *p, int64_t n_blocks, int shape, int64_t *first, int *grid) {
+int team_share_width(int n_cu, const Plan &pl, const irec_params *p, int64_t n_blocks, int shape, int64_t *first, int *grid) {
   if (!pl.team || pl.lone || pl.team_only || (p->flags & IREC_FLAG_NO_SPLIT)) return 0;
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
   const int teams = irec::team_shareable(p->n_beams, p->n_samples, shape);
   if (teams < 2) return 0;
   const int want = (p->flags & IREC_FLAG_SPLIT_MASK) >> IREC_FLAG_SPLIT_SHIFT;
   const int64_t cap = std::min<int64_t>(8, p->n_samples);
   const int64_t slots = (int64_t)teams * n_cu;
   int64_t W = 0, f = 0;
-  if (shape == 2 && share_all_auto(ctx, pl, p, n_blocks)) {
-    if (n_blocks < small_call_blocks(ctx) || n_blocks > irec::COOP_MAX_BLOCKS || 2 * n_blocks > slots) return 0;
+  if (shape == 2 && share_all_auto(n_cu, pl, p, n_blocks)) {
+    if (n_blocks < small_call_blocks(n_cu) || n_blocks > irec::COOP_MAX_BLOCKS || 2 * n_blocks > slots) return 0;
     W = slots / n_blocks;
   } else {
     if (p->n_beams <= 10 || n_blocks <= n_cu || n_blocks >= slots || n_blocks - n_cu > irec::COOP_MAX_BLOCKS) return 0;
@@ -813,26 +805,20 @@ int team_share_width(const irec_context *ctx, const Plan &pl, const irec_params 
   return (int)W;
 }
 
-// teams per workgroup of the kernel a team call of this shape runs: encode_ten_kernel's (irec_ten.hip) for plain calls of at most ten beams
-int call_teams(const irec_params *p, int shape, int share_W, bool margins) {
-  const int tt = (share_W >= 2 || margins || (p->flags & IREC_FLAG_NO_TEN)) ? 0 : irec::team_ten_teams(p->n_beams, p->n_samples, shape);
-  return tt ? tt : irec::team_count_for(p->n_beams, p->n_samples, shape);
-}
 // small calls (a single image's res-block: 9 blocks) are latency-bound: the one-table encoder's set-up (a 6 us proposal
 // table, 40 KB of LDS to fill) beats the team encoder's (38 us per table for the bank assignment, 120 KB); the scratch
 // sized for the team plan covers both
-bool team_for_call(const irec_context *ctx, const Plan &pl, const irec_params *p, int64_t n_blocks) {
-  return pl.team && (pl.team_only || (p->flags & IREC_FLAG_TEAM) || n_blocks >= small_call_blocks(ctx));
+bool team_for_call(int n_cu, const Plan &pl, const irec_params *p, int64_t n_blocks) {
+  return pl.team && (pl.team_only || (p->flags & IREC_FLAG_TEAM) || n_blocks >= small_call_blocks(n_cu));
 }
 // Workgroup shape of the team encoder for THIS call.  With at most one block per CU a lone 4-wave team is latency-bound
 // (one wave per SIMD, ~43 us per step at B = 20, S = 36): the 8-wave beam-striped team (two stripes of 10 beams: half the
 // look-ups and half the update per wave) codes 252 blocks in 0.45 ms against 0.57 ms.  From ~1.3 blocks per CU on the
 // three-team shape wins again.  Same scratch (fewer slabs, same slab size), same outputs.
-int shape_for_call(const irec_context *ctx, const Plan &pl, const irec_params *p, int64_t n_blocks) {
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
+int shape_for_call(int n_cu, const Plan &pl, const irec_params *p, int64_t n_blocks) {
   const int B = p->n_beams, S = p->n_samples;
-  if (share_all_auto(ctx, pl, p, n_blocks)) return 2;                             // every row shared between the teams of the two-team build
-  if (pl.shape != 0 || !pl.team || pl.lone || n_blocks < small_call_blocks(ctx) || n_blocks > 2 * (int64_t)n_cu || B > 20) return pl.shape;   // (< 64 blocks: only calls
+  if (share_all_auto(n_cu, pl, p, n_blocks)) return 2;                             // every row shared between the teams of the two-team build
+  if (pl.shape != 0 || !pl.team || pl.lone || n_blocks < small_call_blocks(n_cu) || n_blocks > 2 * (int64_t)n_cu || B > 20) return pl.shape;   // (< 64 blocks: only calls
                                                                          // that pin IREC_FLAG_TEAM get here, tests of the default shape among them)
   if (irec::team_count_for(B, S, 0) < 2) return pl.shape;                       // already one striped team
   if (n_blocks <= n_cu && B <= 10) return pl.shape;                             // (no 8-wave build for 10 beams)
@@ -854,20 +840,23 @@ int shape_for_call(const irec_context *ctx, const Plan &pl, const irec_params *p
 
 // A call with IREC_FLAG_MARGINS: the team-encoder shape whose MARGIN build (irec_team_margin.hip) serves it, or -1 = the generic kernel.
 // No block is shared under the flag (the cooperative forms have no margin builds), so the call's shape is the plain one of its size.
-int margin_team_shape(const irec_context *ctx, const Plan &pl, const irec_params *p, int64_t n_blocks) {
+int margin_team_shape(int n_cu, const Plan &pl, const irec_params *p, int64_t n_blocks) {
   if (!pl.table || !pl.team || pl.lone || pl.chunk || (p->flags & (IREC_FLAG_FORCE_GENERIC | IREC_FLAG_FUSED_PHILOX | IREC_FLAG_ONE_TABLE))) return -1;
-  const int shape = shape_for_call(ctx, pl, p, n_blocks);
+  const int shape = shape_for_call(n_cu, pl, p, n_blocks);
   if (irec::team_margin_build(p->n_beams, p->n_samples, shape)) return shape;
   if (irec::team_margin_build(p->n_beams, p->n_samples, pl.shape)) return pl.shape;
   return -1;
 }
 
-// What ONE call launches, in numbers: the grid, the teams (= scratch slabs) per workgroup, the cooperative width and what the kernels'
-// own checks rest on.  irec_beam_encode_ex takes its launch from here; irec_test_plan (csrc/irec_internal.h) returns it for any CU count,
-// so that the planner's invariants are tested host-only at 32 ... 304 CUs (round 5's review: every threshold had been measured on one
-// 256-CU box).  `pl` is the call's plan with pl.team / pl.shape already settled for the call.
-struct CallDetail {
-  int kind = 0;             // 1 chunk, 2 lone, 3 team, 4 one-table / split (fast, table), 5 fused fast, 6 generic
+// ONE call, settled once: the workspace layout (the Plan, with team / shape final for THIS call) and what the call launches, in numbers -- the
+// kernel, the grid, the teams (= scratch slabs) per workgroup, the cooperative width, what the kernels' own checks rest on, the deferred pass
+// and the bytes.  plan_call is the only place these are decided: irec_beam_encode_ex launches from it, irec_encode_plan and the test hooks
+// (csrc/irec_internal.h) print it -- for any CU count, so that the planner's invariants are tested host-only at 32 ... 304 CUs (round 5's
+// review: every threshold had been measured on one 256-CU box).
+enum CallKind { KIND_CHUNK = 1, KIND_LONE, KIND_TEAM, KIND_TABLE /* one-table / split */, KIND_FUSED, KIND_GENERIC };   // (irec_plan_detail.kind)
+enum DeferredPass { DEFER_NONE, DEFER_FAST /* the fused-Philox encoder */, DEFER_GENERIC };
+struct CallPlan : Plan {
+  int kind = 0;             // CallKind
   int grid = 0;             // workgroups of the block kernel
   int teams = 1;            // teams (scratch slabs) per workgroup
   int W = 0;                // cooperative width: teams per shared row / workgroups per block / members per gang; 0 = nothing is shared
@@ -877,34 +866,71 @@ struct CallDetail {
   int64_t n_slots = 0;      // hand-out slots of the call (whole rows + W per shared row)
   int placed = 0;           // team encoder: rows dealt by cost (EncArgs::row_cost)
   int split_blocks = 0;     // blocks whose exchange granules the preparation kernel zeroes
+  bool margins = false;     // IREC_FLAG_MARGINS: the call returns top-B margins ...
+  bool margin_build = false;   // ... from a margin build of the team encoder (irec_team_margin.hip), not from the generic kernel
+  bool ten = false;         // encode_ten_kernel<teams> (irec_ten.hip): a plain team call of at most ten beams
+  int deferred = DEFER_NONE, deferred_grid = 0;   // second pass over the blocks whose K lies beyond the table window
+  size_t ws_bytes = 0;      // what this layout occupies: the workspace must hold it
+  size_t ws_bytes_call = 0; // what THIS call indexes of it (irec_encode_workspace_bytes_for)
 };
-CallDetail call_detail(const irec_context *ctx, const Plan &pl, const irec_params *p, int64_t n_blocks, int32_t max_block_dim, bool margins) {
-  CallDetail d;
-  const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
+
+CallPlan plan_call(int n_cu, const irec_params *p, int64_t n_blocks, int32_t max_block_dim, int32_t max_K, size_t workspace_bytes /* 0: the device-wide size */) {
+  irec_params pm = *p;
+  p = &pm;
+  CallPlan d;
+  Plan &pl = d;
+  d.margins = (pm.flags & IREC_FLAG_MARGINS) != 0;
+  if (d.margins) pm.flags |= IREC_FLAG_NO_SPLIT;   // (no block is shared under the flag: the cooperative forms have no margin builds)
+  const int B = p->n_beams, S = p->n_samples;
+  pl = make_plan(n_cu, p, max_block_dim, max_K);
+  if (workspace_bytes && workspace_bytes < plan_ws_bytes(pl) && pl.chunk && !d.margins) {
+    // blocks beyond 1024 dims: a workspace sized for THIS call (irec_encode_workspace_bytes_for) -- or any size in between -- holds fewer
+    // slabs than the device has team slots; the call then launches no more teams than it has slabs (smaller gangs, same results)
+    const int teams = std::max(std::max(1, irec::chunk_teams(B, S)), std::max(1, irec::chunk_gang_teams(B, S)));
+    const size_t fixed = plan_fixed_bytes(pl);
+    const size_t fit = workspace_bytes > fixed ? (workspace_bytes - fixed) / pl.ws_per_wg : 0;
+    if (fit >= (size_t)teams) pl.grid_cap = (int)std::min<size_t>((size_t)pl.grid_cap, fit / teams * teams);
+  }
+  d.ws_bytes = d.ws_bytes_call = plan_ws_bytes(pl);
+  // top-B margins: a margin build of the team encoder where one serves the call's shape (whatever the call's size), else the generic
+  // kernel, which draws in the kernel: no tables
+  const int mshape = d.margins ? margin_team_shape(n_cu, pl, p, n_blocks) : -1;
+  d.margin_build = mshape >= 0;
+  if (d.margins && !d.margin_build) { pl.table = false; pl.team = false; pl.lone = false; pl.chunk = false; pl.fast = false; pl.team_only = false; pl.n_tab = 0; pl.K_tab = 0; }
+  pl.team = d.margin_build || team_for_call(n_cu, pl, p, n_blocks);
+  if (d.margin_build) pl.shape = mshape;
+  else if (pl.team) pl.shape = shape_for_call(n_cu, pl, p, n_blocks);
+  const int margin_generic_grid = (int)std::min<int64_t>(n_blocks, std::min(pl.grid_cap, 2 * n_cu));   // (the generic kernel under the flag)
   d.n_slots = n_blocks;
-  if (pl.table && !pl.team && split_width(ctx, pl, p, n_blocks) >= 2) d.split_blocks = (int)n_blocks;   // (pl.team: of THIS call)
-  int share_grid = 0;
-  const int share_W = (pl.table && pl.team) ? team_share_width(ctx, pl, p, n_blocks, pl.shape, &d.share_first, &share_grid) : 0;
-  if (share_W >= 2) d.split_blocks = (int)(n_blocks - d.share_first);
-  if (pl.chunk && gang_width(ctx, pl, p, n_blocks, max_block_dim, nullptr, nullptr) >= 2) d.split_blocks = (int)n_blocks;   // (their granules' first words: the gangs' arrival counters)
-  if (pl.table && pl.chunk) {
-    d.kind = 1;
-    d.teams = std::max(1, irec::chunk_teams(p->n_beams, p->n_samples));
-    d.grid = chunk_grid(ctx, pl, p, n_blocks);
-    int ggrid = 0, gchunks = 0;
-    if (const int G = gang_width(ctx, pl, p, n_blocks, max_block_dim, &ggrid, &gchunks)) {
+  if (pl.table && pl.chunk) {   // one workgroup per CU, a block of any dim count per team; steps beyond the table window are drawn in the kernel: no second pass
+    d.kind = KIND_CHUNK;
+    const int teams = std::max(1, irec::chunk_teams(B, S));
+    d.teams = teams;
+    d.grid = chunk_grid(n_cu, pl, p, n_blocks);
+    int slab_teams = teams, ggrid = 0, gchunks = 0;
+    if (const int G = gang_width(n_cu, pl, p, n_blocks, max_block_dim, &ggrid, &gchunks)) {
       d.W = G; d.gang_chunks = gchunks; d.grid = ggrid; d.n_slots = n_blocks * G;
-      d.teams = std::max(1, irec::chunk_gang_teams(p->n_beams, p->n_samples));
+      d.teams = std::max(1, irec::chunk_gang_teams(B, S));
+      d.split_blocks = (int)n_blocks;   // (their granules' first words: the gangs' arrival counters)
+      slab_teams = std::max(slab_teams, d.teams);
     }
-  } else if (pl.table && pl.team && pl.lone) {
-    d.kind = 2; d.grid = batch_grid(n_blocks, n_cu); d.teams = irec::lone_waves();
-  } else if (pl.table && pl.team) {
-    d.kind = 3;
-    d.teams = call_teams(p, pl.shape, share_W, margins);
+    // the chunked encoder indexes the slabs of the workgroups it launches: their count is what this call needs of the workspace
+    if (n_blocks > 0) d.ws_bytes_call = plan_fixed_bytes(pl) + (size_t)std::min(pl.grid_cap, std::max(teams, d.grid * slab_teams)) * pl.ws_per_wg;
+  } else if (pl.table && pl.team && pl.lone) {   // one workgroup per CU, a block per wave
+    d.kind = KIND_LONE; d.grid = batch_grid(n_blocks, n_cu); d.teams = irec::lone_waves();
+  } else if (pl.table && pl.team) {   // grid_cap counts teams (= scratch slabs)
+    d.kind = KIND_TEAM;
+    int share_grid = 0;
+    const int share_W = team_share_width(n_cu, pl, p, n_blocks, pl.shape, &d.share_first, &share_grid);
+    // teams per workgroup of the kernel a team call of this shape runs: encode_ten_kernel's (irec_ten.hip) for plain calls of at most ten beams
+    const int tt = (share_W >= 2 || d.margins || (p->flags & IREC_FLAG_NO_TEN)) ? 0 : irec::team_ten_teams(B, S, pl.shape);
+    d.ten = tt != 0;
+    d.teams = tt ? tt : irec::team_count_for(B, S, pl.shape);
     // one workgroup per CU as soon as there is a block for it: team k of workgroup w starts on block k * grid + w
     d.grid = batch_grid(n_blocks, std::min(pl.grid_cap / d.teams, n_cu));
     if (share_W >= 2) {   // rows [share_first, n_blocks) are coded by share_W teams each; the static round deals every slot
       d.W = share_W; d.grid = share_grid; d.n_slots = d.share_first + (n_blocks - d.share_first) * share_W;
+      d.split_blocks = (int)(n_blocks - d.share_first);
     }
     // Cost-ordered hand-out (calls of more rows than workgroups whose slots the static round deals completely -- one to TEAMS rows per
     // CU): the preparation kernel also writes K * dims of every row, and the teams take their rows by cost rank (irec_team.hip).
@@ -912,25 +938,163 @@ CallDetail call_detail(const irec_context *ctx, const Plan &pl, const irec_param
     //  steps of half the length, nor on the three-team build.
     //  Round 6: encode_ten_kernel<2> with its two-row workgroups on the cheapest rows gains 5 us of 190 on one tensor of 302 blocks and loses
     //  1.5 - 11 us on calls of many tensors, whose layout lists the small blocks last anyway: not taken, profiles/r06end/.)
-    if (!pl.lone && !pl.chunk && !(p->flags & IREC_FLAG_LISTED_ORDER) && n_blocks <= irec::COST_MAX_ROWS) {
-      const int n_teams = irec::team_count_for(p->n_beams, p->n_samples, pl.shape);
+    if (!(p->flags & IREC_FLAG_LISTED_ORDER) && n_blocks <= irec::COST_MAX_ROWS) {
+      const int n_teams = irec::team_count_for(B, S, pl.shape);
       const int64_t tg = share_W >= 2 ? share_grid : batch_grid(n_blocks, std::min(pl.grid_cap / n_teams, n_cu));
-      if (n_blocks > tg && d.n_slots <= tg * n_teams && n_teams == 2 && p->n_beams > 10 && irec::team_placeable(p->n_beams, p->n_samples, pl.shape)) d.placed = 1;
+      if (n_blocks > tg && d.n_slots <= tg * n_teams && n_teams == 2 && B > 10 && irec::team_placeable(B, S, pl.shape)) d.placed = 1;
     }
   } else if (pl.table) {
-    d.kind = 4;
+    d.kind = KIND_TABLE;
     d.grid = (int)std::min<int64_t>(n_blocks, pl.one_grid_cap);
-    int W = split_width(ctx, pl, p, n_blocks);
+    int W = split_width(n_cu, pl, p, n_blocks);
     if (const int wb = split_beam_width(p, W)) { W = wb; d.coop_beams = 1; }
-    if (W >= 2) { d.W = W; d.grid = (int)(n_blocks * W); d.n_slots = n_blocks * W; }
+    if (W >= 2) { d.W = W; d.grid = (int)(n_blocks * W); d.n_slots = n_blocks * W; d.split_blocks = (int)n_blocks; }
   } else if (pl.fast) {
-    d.kind = 5; d.grid = (int)std::min<int64_t>(n_blocks, pl.one_grid_cap);
+    d.kind = KIND_FUSED; d.grid = (int)std::min<int64_t>(n_blocks, pl.one_grid_cap);
   } else {
-    d.kind = 6;
-    d.grid = margins ? (int)std::min<int64_t>(n_blocks, std::min(pl.grid_cap, 2 * n_cu)) : (int)std::min<int64_t>(n_blocks, pl.grid_cap);
+    d.kind = KIND_GENERIC;
+    d.grid = d.margins ? margin_generic_grid : (int)std::min<int64_t>(n_blocks, pl.grid_cap);
+  }
+  // second pass (only when the window is shorter than max_K): the fused-Philox encoder -- the generic kernel where the call has none -- codes
+  // the blocks whose K lies beyond the table window; it returns at once when the first pass deferred nothing
+  if ((d.kind == KIND_LONE || d.kind == KIND_TEAM || d.kind == KIND_TABLE) && pl.K_tab < max_K) {
+    d.deferred = (d.margin_build || pl.team_only) ? DEFER_GENERIC : DEFER_FAST;
+    d.deferred_grid = d.margin_build ? margin_generic_grid : (int)std::min<int64_t>(n_blocks, pl.fast_grid_cap);
   }
   return d;
 }
+
+// The settled plan in the words of irec_plan_info: names and numbers from the plan and the kernels' capability queries, no decisions.
+void describe(const CallPlan &cp, int B, int S, irec_plan_info *out) {
+  std::memset(out, 0, sizeof(*out));
+  const bool beam_split = cp.W >= 2 && cp.coop_beams;
+  const char *tables = "";
+  out->waves_per_wg = 4; out->teams_per_wg = 1;
+  switch (cp.kind) {
+  case KIND_CHUNK:
+    std::snprintf(out->kernel, sizeof out->kernel, "%s", cp.W >= 2 ? irec::chunk_gang_kernel_name(B, S) : irec::chunk_kernel_name(B, S));
+    tables = "prep_kernel (copy bits)";
+    out->teams_per_wg = cp.teams; out->waves_per_wg = cp.teams * 4;
+    out->lds_bytes = (int32_t)(cp.W >= 2 ? irec::chunk_gang_lds_for(B, S) : irec::chunk_lds_for(B, S));
+    break;
+  case KIND_LONE:
+    std::snprintf(out->kernel, sizeof out->kernel, "%s", irec::lone_kernel_name());
+    tables = "prep_kernel (copy bits)";
+    out->waves_per_wg = out->teams_per_wg = irec::lone_waves();       // every wave codes its own block
+    out->lds_bytes = (int32_t)irec::lone_lds_bytes();
+    break;
+  case KIND_TEAM: {
+    std::string nm = irec::team_kernel_name(B, S, cp.shape);
+    if (cp.margin_build) nm.insert(nm.size() - 1, ",margins");
+    if (cp.ten) nm = "encode_ten_kernel<" + std::to_string(cp.teams) + ">";
+    std::snprintf(out->kernel, sizeof out->kernel, "%s", nm.c_str());
+    tables = "prep_kernel (copy bits)";
+    out->teams_per_wg = cp.teams;
+    out->waves_per_wg = cp.ten ? 4 * cp.teams : irec::team_waves_for(B, S, cp.shape);
+    out->lds_bytes = (int32_t)(cp.ten ? irec::ten_lds_for(cp.teams) : irec::team_lds_for(B, S, cp.shape));
+    break;
+  }
+  case KIND_TABLE:
+  case KIND_FUSED:
+    std::snprintf(out->kernel, sizeof out->kernel, "%s", irec::fast_kernel_name(B, S, cp.table));
+    // (the split forms are builds of their own: <NB,4,true,1> shares a block's samples, <NB,4|8,true,2> its beams -- 8 waves for 20 beams)
+    if (cp.W >= 2) std::snprintf(out->kernel, sizeof out->kernel, "encode_fast_kernel<%d,%d,true,%d>", irec::fast_nb_for(B),
+                                 beam_split ? irec::fast_split_beam_waves(B) : 4, beam_split ? 2 : 1);
+    if (cp.table) tables = "prep_kernel (plain rows)";
+    out->waves_per_wg = beam_split ? irec::fast_split_beam_waves(B) : irec::fast_waves_for(B, S, cp.table);
+    out->lds_bytes = (int32_t)irec::fast_lds_for(B, S, cp.table) + (beam_split ? 40024 : 0);   // (beam split: two table copies of 10 006 floats)
+    break;
+  default:
+    std::snprintf(out->kernel, sizeof out->kernel, "%s", cp.margins ? "encode_generic_kernel (margins)" : "encode_generic_kernel");
+    out->lds_bytes = (int32_t)irec::generic_lds_bytes();
+  }
+  std::snprintf(out->table_kernel, sizeof out->table_kernel, "%s", tables);
+  out->grid = cp.grid; out->split = cp.W; out->split_beams = cp.coop_beams;
+  out->table_steps = cp.K_tab; out->n_tables = cp.n_tab;
+  out->table_bytes = cp.table ? (int64_t)cp.tab_bytes : 0;   // (a call without tables lays its slabs behind the area all the same)
+  out->workspace_bytes = (int64_t)cp.ws_bytes;
+}
+
+#ifdef IREC_HOST_STAMPS   // the stamps build only (make stamps): synchronous read-back of the phase stamps of the call just enqueued, to stderr
+// diagnostic build (-DIREC_LONE_STAMPS): per-wave phase cycles of the one-beam encoder
+irec_status print_lone_stamps(const irec_context *ctx, const CallPlan &cp, hipStream_t st) {
+  const int lgrid = cp.grid, nwv = cp.teams;
+  std::vector<unsigned long long> h((size_t)lgrid * nwv * 16);
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(h.data(), ctx->d_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  static const char *nm[6] = {"prologue (fetch, KL)", "step constants", "scoring", "selection", "update", "epilogue"};
+  double sum[6] = {0}, tot = 0;
+  for (size_t w = 0; w < (size_t)lgrid * nwv; ++w) for (int k = 0; k < 6; ++k) { sum[k] += (double)h[w * 16 + k]; tot += (double)h[w * 16 + k]; }
+  fprintf(stderr, "[irec lone stamps] share of wave time:\n");
+  for (int k = 0; k < 6; ++k) fprintf(stderr, "  %-22s %5.1f%%\n", nm[k], 100 * sum[k] / tot);
+  fprintf(stderr, "  cycles per wave: %.0f\n", tot / (lgrid * nwv));
+  return IREC_OK;
+}
+// diagnostic build (-DIREC_TEAM_STAMPS) only: per-wave phase cycles, wave 0 of a team vs the others
+irec_status print_team_stamps(const irec_context *ctx, const CallPlan &cp, int B, int S, hipStream_t st) {
+  const int tgrid = cp.grid, n_teams = cp.teams;
+  const int nwv = cp.ten ? 4 * n_teams : irec::team_waves_for(B, S, cp.shape);
+  std::vector<unsigned long long> h((size_t)tgrid * nwv * 16);
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(h.data(), ctx->d_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  static const char *nm[12] = {"fetch", "prologue", "scoring", "wait-score", "combine", "select", "update-tail", "wait-update", "epilogue",
+                               "upd:sel+issue+consts", "upd:batches", "-"};
+  // (waves of teams that coded no block -- a mid-size call leaves team slots empty -- are left out of the averages)
+  const int nwt = nwv / n_teams;   // waves per team
+  double w0[12] = {0}, wo[12] = {0}, t0 = 0, to = 0;
+  int n0 = 0, no = 0;
+  for (int w = 0; w < tgrid * nwv; ++w) {
+    if (h[(size_t)w * 16 + 1] == 0ull) continue;   // no prologue: no block
+    if ((w % nwt) == 0) ++n0; else ++no;
+    for (int k = 0; k < 12; ++k) { const double v = (double)h[(size_t)w * 16 + k]; if ((w % nwt) == 0) { w0[k] += v; t0 += v; } else { wo[k] += v; to += v; } }
+  }
+  fprintf(stderr, "[irec team stamps] %d of %d teams coded blocks; share of wave time (cycles per wave), wave 0 of a team | the others:\n", n0, tgrid * n_teams);
+  t0 -= w0[11]; to -= wo[11];   // (slot 11 counts block-steps, not cycles)
+  for (int k = 0; k < 11; ++k) fprintf(stderr, "  %-20s %5.1f%% (%8.0f) | %5.1f%% (%8.0f)\n", nm[k], 100 * w0[k] / t0, w0[k] / (n0 ? n0 : 1), 100 * wo[k] / to, wo[k] / (no ? no : 1));
+  fprintf(stderr, "  cycles per wave: %.0f | %.0f;  block-steps per wave: %.2f;  cycles per block-step: %.0f\n", t0 / (n0 ? n0 : 1), to / (no ? no : 1),
+          w0[11] / (n0 ? n0 : 1), w0[11] > 0 ? t0 / w0[11] : 0.0);
+  {   // idle tail of the persistent grid: wave-time between a wave's exit and the last wave's (slot 12 = a wave's lifetime)
+    double life_max = 0, life_sum = 0, life_min = 1e300;
+    int nlife = 0;
+    for (int w = 0; w < tgrid * nwv; ++w) {
+      const double v = (double)h[(size_t)w * 16 + 12];
+      if (v <= 0) continue;
+      life_max = std::max(life_max, v); life_min = std::min(life_min, v); life_sum += v; ++nlife;
+    }
+    if (nlife) fprintf(stderr, "  idle tail: %.1f%% of the grid's wave-time lies behind a wave's exit (first exit at %.1f%% of the longest lifetime)\n",
+                       100.0 * (1.0 - life_sum / (nlife * life_max)), 100.0 * life_min / life_max);
+  }
+  if (h[13]) fprintf(stderr, "  shader clock of workgroup 0, wave 0: %.0f MHz over %.3f ms (s_memtime / s_memrealtime)\n",
+                     100.0 * (double)h[12] / (double)h[13], (double)h[13] / 1e5);
+  return IREC_OK;
+}
+// the one-workgroup-per-block encoders (one-table / split, fused, generic): the stamps of every workgroup
+irec_status print_one_wg_stamps(const irec_context *ctx, const CallPlan &cp, int B, int S, hipStream_t st) {
+  const int grid = cp.grid;
+  std::vector<unsigned long long> h((size_t)grid * 16);
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(h.data(), ctx->d_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  double sum[16] = {0};
+  for (int w = 0; w < grid; ++w) for (int k = 0; k < 16; ++k) sum[k] += (double)h[(size_t)w * 16 + k];
+  const double tot = sum[0] + sum[1] + sum[2] + sum[3];
+  {
+    int zero = 0; unsigned long long t0 = ~0ull, late = 0;
+    for (int w = 0; w < grid; ++w) { if (h[(size_t)w * 16 + 4] == 0) ++zero; else if (h[(size_t)w * 16 + 5] < t0) t0 = h[(size_t)w * 16 + 5]; }
+    for (int w = 0; w < grid; ++w) if (h[(size_t)w * 16 + 4] && h[(size_t)w * 16 + 5] - t0 > 100000ull) ++late; // > 1 ms at 100 MHz
+    fprintf(stderr, "[irec stamps] census: %d of %d workgroups coded no block, %llu started > 1 ms after the first\n", zero, grid, late);
+  }
+  fprintf(stderr, "[irec stamps] top-B detail cycles/WG: combine %.0f, wait-for-keys barrier %.0f, wave-0 select %.0f, closing barrier %.0f\n",
+          sum[11] / grid, sum[8] / grid, sum[9] / grid, sum[10] / grid);
+  if (sum[12] + sum[13] + sum[14] > 0)
+    fprintf(stderr, "[irec stamps] split exchange cycles/WG: publish %.0f, wait for partners %.0f, read back %.0f\n",
+            sum[12] / grid, sum[13] / grid, sum[14] / grid);
+  fprintf(stderr, "[irec stamps] waves/workgroup %d, LDS %zu B\n", irec::fast_waves_for(B, S, cp.table), irec::fast_lds_for(B, S, cp.table));
+  fprintf(stderr, "[irec stamps] %s grid=%d cycles/WG: prologue %.0f (%.1f%%) scoring %.0f (%.1f%%) select %.0f (%.1f%%) update %.0f (%.1f%%)\n",
+          cp.table ? "table" : cp.fast ? "fused" : "generic", grid, sum[0] / grid, 100 * sum[0] / tot, sum[1] / grid,
+          100 * sum[1] / tot, sum[2] / grid, 100 * sum[2] / tot, sum[3] / grid, 100 * sum[3] / tot);
+  return IREC_OK;
+}
+#endif
 
 } // namespace
 
@@ -938,8 +1102,7 @@ extern "C" {
 
 size_t irec_encode_workspace_bytes(const irec_context *ctx, const irec_params *p, int32_t max_dim, int32_t max_K) {
   if (!ctx || check_params(p) != IREC_OK || max_dim < 1 || max_K < 0) return 0;
-  const Plan pl = make_plan(ctx, p, max_dim, max_K);
-  return plan_ws_bytes(pl);
+  return plan_ws_bytes(make_plan(irec::context_cus(ctx), p, max_dim, max_K));   // (no block count: the layout alone)
 }
 
 // Scratch of ONE call (round 6; review r05: irec_encode_workspace_bytes sizes a call of blocks beyond 1024 dims for the whole device -- a slab
@@ -947,17 +1110,7 @@ size_t irec_encode_workspace_bytes(const irec_context *ctx, const irec_params *p
 // encoder indexes the slabs of the workgroups it launches: their count is what this call needs.  Every other plan: irec_encode_workspace_bytes.
 size_t irec_encode_workspace_bytes_for(const irec_context *ctx, const irec_params *p, int64_t n_blocks, int32_t max_dim, int32_t max_K) {
   if (!ctx || check_params(p) != IREC_OK || max_dim < 1 || max_K < 0 || n_blocks < 0) return 0;
-  irec_params pm = *p;
-  if (pm.flags & IREC_FLAG_MARGINS) pm.flags |= IREC_FLAG_NO_SPLIT;
-  Plan pl = make_plan(ctx, &pm, max_dim, max_K);
-  if (pl.chunk && !(pm.flags & IREC_FLAG_MARGINS) && n_blocks > 0) {
-    const int teams = std::max(1, irec::chunk_teams(pm.n_beams, pm.n_samples));
-    int grid = chunk_grid(ctx, pl, &pm, n_blocks), ggrid = 0;
-    int gteams = teams;
-    if (gang_width(ctx, pl, &pm, n_blocks, max_dim, &ggrid, nullptr) >= 2) { grid = ggrid; gteams = std::max(1, irec::chunk_gang_teams(pm.n_beams, pm.n_samples)); }
-    pl.grid_cap = std::min(pl.grid_cap, std::max(teams, grid * std::max(teams, gteams)));
-  }
-  return plan_ws_bytes(pl);
+  return plan_call(irec::context_cus(ctx), p, n_blocks, max_dim, max_K, 0).ws_bytes_call;
 }
 
 irec_status irec_encode_plan(const irec_context *ctx, const irec_params *p, int64_t n_blocks, int32_t max_block_dim,
@@ -965,138 +1118,37 @@ irec_status irec_encode_plan(const irec_context *ctx, const irec_params *p, int6
   if (!ctx || !out) return fail(IREC_E_INVALID, "irec_encode_plan: null argument");
   if (irec_status s = check_params(p)) return s;
   if (n_blocks < 0 || max_block_dim < 1 || max_K < 0) return fail(IREC_E_INVALID, "irec_encode_plan: bad sizes");
-  irec_params pm = *p;
-  if (pm.flags & IREC_FLAG_MARGINS) { pm.flags |= IREC_FLAG_NO_SPLIT; p = &pm; }
-  const Plan pl = make_plan(ctx, p, max_block_dim, max_K);
-  const bool team = team_for_call(ctx, pl, p, n_blocks);
-  std::memset(out, 0, sizeof(*out));
-  const int B = p->n_beams, S = p->n_samples;
-  if (p->flags & IREC_FLAG_MARGINS) {   // irec_beam_encode_ex: a margin build of the team encoder, or the generic kernel
-    const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
-    const int mshape = margin_team_shape(ctx, pl, p, n_blocks);
-    if (mshape >= 0) {
-      const int n_teams = irec::team_count_for(B, S, mshape);
-      std::string nm = irec::team_kernel_name(B, S, mshape);
-      nm.insert(nm.size() - 1, ",margins");
-      std::snprintf(out->kernel, sizeof out->kernel, "%s", nm.c_str());
-      std::snprintf(out->table_kernel, sizeof out->table_kernel, "prep_kernel (copy bits)");
-      out->grid = batch_grid(n_blocks, std::min(pl.grid_cap / n_teams, n_cu));
-      out->waves_per_wg = irec::team_waves_for(B, S, mshape);
-      out->teams_per_wg = n_teams;
-      out->lds_bytes = (int32_t)irec::team_lds_for(B, S, mshape);
-      out->table_steps = pl.K_tab; out->n_tables = pl.n_tab; out->table_bytes = (int64_t)pl.tab_bytes;
-    } else {
-      std::snprintf(out->kernel, sizeof out->kernel, "encode_generic_kernel (margins)");
-      out->grid = (int32_t)std::min<int64_t>(n_blocks, std::min(pl.grid_cap, 2 * n_cu));
-      out->waves_per_wg = 4; out->teams_per_wg = 1;
-      out->lds_bytes = (int32_t)irec::generic_lds_bytes();
-    }
-    out->n_cu = ctx->n_cu; out->clock_mhz = ctx->clock_mhz;
-    out->workspace_bytes = (int64_t)plan_ws_bytes(pl);
-    return IREC_OK;
-  }
-  if (pl.chunk) {
-    std::snprintf(out->kernel, sizeof out->kernel, "%s", irec::chunk_kernel_name(B, S));
-    std::snprintf(out->table_kernel, sizeof out->table_kernel, "prep_kernel (copy bits)");
-    out->grid = chunk_grid(ctx, pl, p, n_blocks);
-    {
-      int ggrid = 0;
-      out->split = gang_width(ctx, pl, p, n_blocks, max_block_dim, &ggrid, nullptr);   // teams that code each block together
-      if (out->split >= 2) out->grid = ggrid;
-    }
-    out->waves_per_wg = irec::chunk_teams(B, S) * 4;
-    out->teams_per_wg = irec::chunk_teams(B, S);
-    out->lds_bytes = (int32_t)irec::chunk_lds_for(B, S);
-    if (out->split >= 2) {
-      std::snprintf(out->kernel, sizeof out->kernel, "%s", irec::chunk_gang_kernel_name(B, S));
-      out->teams_per_wg = irec::chunk_gang_teams(B, S); out->waves_per_wg = out->teams_per_wg * 4;
-      out->lds_bytes = (int32_t)irec::chunk_gang_lds_for(B, S);
-    }
-  } else if (team && pl.lone) {
-    const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
-    std::snprintf(out->kernel, sizeof out->kernel, "%s", irec::lone_kernel_name());
-    std::snprintf(out->table_kernel, sizeof out->table_kernel, "prep_kernel (copy bits)");
-    out->grid = batch_grid(n_blocks, n_cu);
-    out->waves_per_wg = irec::lone_waves();
-    out->teams_per_wg = irec::lone_waves();       // every wave codes its own block
-    out->lds_bytes = (int32_t)irec::lone_lds_bytes();
-  } else if (team) {
-    const int shape = shape_for_call(ctx, pl, p, n_blocks);
-    const int n_teams = irec::team_count_for(B, S, shape);
-    const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
-    std::snprintf(out->kernel, sizeof out->kernel, "%s", irec::team_kernel_name(B, S, shape));
-    std::snprintf(out->table_kernel, sizeof out->table_kernel, "prep_kernel (copy bits)");
-    out->grid = batch_grid(n_blocks, std::min(pl.grid_cap / n_teams, n_cu));
-    {
-      int sgrid = 0;
-      out->split = team_share_width(ctx, pl, p, n_blocks, shape, nullptr, &sgrid);   // teams that code each shared row
-      if (out->split >= 2) out->grid = sgrid;
-    }
-    out->waves_per_wg = irec::team_waves_for(B, S, shape);
-    out->teams_per_wg = n_teams;
-    out->lds_bytes = (int32_t)irec::team_lds_for(B, S, shape);
-    if (const int tt = irec::team_ten_teams(B, S, shape); tt && out->split < 2 && !(p->flags & IREC_FLAG_NO_TEN)) {   // plain call of at most ten beams
-      std::snprintf(out->kernel, sizeof out->kernel, "encode_ten_kernel<%d>", tt);
-      out->lds_bytes = (int32_t)irec::ten_lds_for(tt);
-      out->teams_per_wg = tt; out->waves_per_wg = 4 * tt;
-      out->grid = batch_grid(n_blocks, std::min(pl.grid_cap / tt, n_cu));
-    }
-  } else if (pl.fast) {
-    std::snprintf(out->kernel, sizeof out->kernel, "%s", irec::fast_kernel_name(B, S, pl.table));
-    if (pl.table) std::snprintf(out->table_kernel, sizeof out->table_kernel, "prep_kernel (plain rows)");
-    out->grid = (int32_t)std::min<int64_t>(n_blocks, pl.one_grid_cap);
-    out->split = split_width(ctx, pl, p, n_blocks);
-    if (const int wb = split_beam_width(p, out->split)) { out->split = wb; out->split_beams = 1; }
-    if (out->split >= 2) {
-      out->grid = (int32_t)(n_blocks * out->split);
-      // (the split forms are builds of their own: <NB,4,true,1> shares a block's samples, <NB,4|8,true,2> its beams -- 8 waves for 20 beams)
-      std::snprintf(out->kernel, sizeof out->kernel, "encode_fast_kernel<%d,%d,true,%d>", irec::fast_nb_for(B),
-                    out->split_beams ? irec::fast_split_beam_waves(B) : 4, out->split_beams ? 2 : 1);
-    }
-    out->waves_per_wg = (out->split >= 2 && out->split_beams) ? irec::fast_split_beam_waves(B) : irec::fast_waves_for(B, S, pl.table);
-    out->teams_per_wg = 1;
-    out->lds_bytes = (int32_t)irec::fast_lds_for(B, S, pl.table) + (out->split >= 2 && out->split_beams ? 40024 : 0);   // (beam split: two table copies of 10 006 floats)
-  } else {
-    std::snprintf(out->kernel, sizeof out->kernel, "encode_generic_kernel");
-    out->grid = (int32_t)std::min<int64_t>(n_blocks, pl.grid_cap);
-    out->waves_per_wg = 4;
-    out->teams_per_wg = 1;
-    out->lds_bytes = (int32_t)irec::generic_lds_bytes();
-  }
-  out->table_steps = pl.K_tab;
-  out->n_tables = pl.n_tab;
-  out->n_cu = ctx->n_cu;
-  out->clock_mhz = ctx->clock_mhz;
-  out->table_bytes = (int64_t)pl.tab_bytes;
-  out->workspace_bytes = (int64_t)plan_ws_bytes(pl);
+  describe(plan_call(irec::context_cus(ctx), p, n_blocks, max_block_dim, max_K, 0), p->n_beams, p->n_samples, out);
+  out->n_cu = ctx->n_cu; out->clock_mhz = ctx->clock_mhz;
   return IREC_OK;
 }
 
-// Test hook (csrc/irec_internal.h): the plan and the launch numbers of a call on a device of `n_cu` compute units -- no device is touched.
-irec_status irec_test_plan(int32_t n_cu, int32_t clock_mhz, const irec_params *p, int64_t n_blocks, int32_t max_block_dim, int32_t max_K,
-                           irec_plan_info *info, irec_plan_detail *detail) {
-  if (!info || !detail || n_cu < 1) return fail(IREC_E_INVALID, "irec_test_plan: bad argument");
-  irec_context fake;
-  fake.n_cu = n_cu; fake.clock_mhz = clock_mhz;
-  if (irec_status st = irec_encode_plan(&fake, p, n_blocks, max_block_dim, max_K, info)) return st;
-  const bool margins = (p->flags & IREC_FLAG_MARGINS) != 0;
-  irec_params pm = *p;
-  if (margins) pm.flags |= IREC_FLAG_NO_SPLIT;
-  Plan pl = make_plan(&fake, &pm, max_block_dim, max_K);   // ... and then exactly what irec_beam_encode_ex does with it
-  const int mshape = margins ? margin_team_shape(&fake, pl, &pm, n_blocks) : -1;
-  if (margins && mshape < 0) { pl.table = false; pl.team = false; pl.lone = false; pl.chunk = false; pl.fast = false; pl.team_only = false; pl.n_tab = 0; pl.K_tab = 0; }
-  pl.team = mshape >= 0 ? true : team_for_call(&fake, pl, &pm, n_blocks);
-  if (mshape >= 0) pl.shape = mshape;
-  else if (pl.team) pl.shape = shape_for_call(&fake, pl, &pm, n_blocks);
-  const CallDetail cd = call_detail(&fake, pl, &pm, n_blocks, max_block_dim, margins);
+// Test hooks (csrc/irec_internal.h): the settled plan of a call on a device of `n_cu` compute units, as irec_encode_plan words it and in the
+// launch's numbers -- no device is touched.  workspace_bytes: what the caller hands irec_beam_encode (0: the device-wide size, -1: the size
+// irec_encode_workspace_bytes_for gives the call); a workspace the launch would refuse is refused here.
+irec_status irec_test_plan_ws(int32_t n_cu, int32_t clock_mhz, const irec_params *p, int64_t n_blocks, int32_t max_block_dim, int32_t max_K,
+                              int64_t workspace_bytes, irec_plan_info *info, irec_plan_detail *detail) {
+  if (!info || !detail || n_cu < 1 || workspace_bytes < -1) return fail(IREC_E_INVALID, "irec_test_plan: bad argument");
+  if (irec_status s = check_params(p)) return s;
+  if (n_blocks < 0 || max_block_dim < 1 || max_K < 0) return fail(IREC_E_INVALID, "irec_encode_plan: bad sizes");
+  if (workspace_bytes < 0) workspace_bytes = (int64_t)plan_call(n_cu, p, n_blocks, max_block_dim, max_K, 0).ws_bytes_call;
+  const CallPlan cp = plan_call(n_cu, p, n_blocks, max_block_dim, max_K, (size_t)workspace_bytes);
+  if (workspace_bytes > 0 && (size_t)workspace_bytes < cp.ws_bytes)
+    return fail(IREC_E_WORKSPACE, "irec_test_plan: workspace %zu bytes < required %zu", (size_t)workspace_bytes, cp.ws_bytes);
+  describe(cp, p->n_beams, p->n_samples, info);
+  info->n_cu = n_cu; info->clock_mhz = clock_mhz;
   std::memset(detail, 0, sizeof(*detail));
-  detail->kind = cd.kind; detail->grid = cd.grid; detail->teams_per_wg = cd.teams; detail->coop_width = cd.W; detail->coop_beams = cd.coop_beams;
-  detail->gang_chunks = cd.gang_chunks; detail->placed = cd.placed; detail->split_blocks = cd.split_blocks;
-  detail->share_first = cd.share_first; detail->n_slots = cd.n_slots;
-  detail->slabs_in_workspace = pl.grid_cap; detail->slab_bytes = (int64_t)pl.ws_per_wg;
-  detail->fixed_bytes = (int64_t)(irec::WS_HEAD_BYTES + pl.tab_bytes + pl.gang_bytes);
+  detail->kind = cp.kind; detail->grid = cp.grid; detail->teams_per_wg = cp.teams; detail->coop_width = cp.W; detail->coop_beams = cp.coop_beams;
+  detail->gang_chunks = cp.gang_chunks; detail->placed = cp.placed; detail->split_blocks = cp.split_blocks;
+  detail->share_first = cp.share_first; detail->n_slots = cp.n_slots;
+  detail->slabs_in_workspace = cp.grid_cap; detail->slab_bytes = (int64_t)cp.ws_per_wg;
+  detail->fixed_bytes = (int64_t)plan_fixed_bytes(cp);
   detail->exchange_rows = irec::COOP_MAX_BLOCKS; detail->exchange_keys = irec::COOP_KEYS;
   return IREC_OK;
+}
+irec_status irec_test_plan(int32_t n_cu, int32_t clock_mhz, const irec_params *p, int64_t n_blocks, int32_t max_block_dim, int32_t max_K,
+                           irec_plan_info *info, irec_plan_detail *detail) {
+  return irec_test_plan_ws(n_cu, clock_mhz, p, n_blocks, max_block_dim, max_K, 0, info, detail);
 }
 
 irec_status irec_block_kl(irec_context *ctx, const irec_params *p, int64_t n_blocks, const int64_t *block_base,
@@ -1139,8 +1191,6 @@ irec_status irec_beam_encode_ex(irec_context *ctx, const irec_params *p, int64_t
   if (irec_status s = check_params(p)) return s;
   if (((p->flags & IREC_FLAG_MARGINS) != 0) != (out_margin != nullptr))
     return fail(IREC_E_INVALID, "irec_beam_encode_ex: out_margin and IREC_FLAG_MARGINS go together (the flag sizes the workspace)");
-  irec_params pm = *p;
-  if (out_margin) { pm.flags |= IREC_FLAG_NO_SPLIT; p = &pm; }   // (no block is shared under the flag: the cooperative forms have no margin builds)
   if (n_blocks < 0) return fail(IREC_E_INVALID, "irec_beam_encode: n_blocks < 0");
   if (n_blocks > 0x7FFF0000ll) return fail(IREC_E_INVALID, "irec_beam_encode: more than 2^31 - 65536 blocks in one call");   // (block rows are int32 in the kernels)
   if (n_blocks == 0) return IREC_OK;
@@ -1149,23 +1199,10 @@ irec_status irec_beam_encode_ex(irec_context *ctx, const irec_params *p, int64_t
   if (max_K < 0 || max_K > IREC_MAX_PARTITIONS) return fail(IREC_E_INVALID, "irec_beam_encode: max_K %d out of range", max_K);
   if (max_K > 0 && !out_indices) return fail(IREC_E_INVALID, "irec_beam_encode: null out_indices");
   if (max_block_dim < 1 || max_block_dim > (1 << 22)) return fail(IREC_E_INVALID, "irec_beam_encode: max_block_dim %d out of range", max_block_dim);
-  Plan pl = make_plan(ctx, p, max_block_dim, max_K);
-  size_t need = plan_ws_bytes(pl);
-  if (workspace && workspace_bytes < need && pl.chunk && !out_margin) {
-    // blocks beyond 1024 dims: a workspace sized for THIS call (irec_encode_workspace_bytes_for) -- or any size in between -- holds fewer
-    // slabs than the device has team slots; the call then launches no more teams than it has slabs (smaller gangs, same results)
-    const int teams = std::max(std::max(1, irec::chunk_teams(p->n_beams, p->n_samples)), std::max(1, irec::chunk_gang_teams(p->n_beams, p->n_samples)));
-    const size_t fixed = irec::WS_HEAD_BYTES + pl.tab_bytes + pl.gang_bytes;
-    const size_t fit = workspace_bytes > fixed ? (workspace_bytes - fixed) / pl.ws_per_wg : 0;
-    if (fit >= (size_t)teams) { pl.grid_cap = (int)std::min<size_t>((size_t)pl.grid_cap, fit / teams * teams); need = plan_ws_bytes(pl); }
-  }
-  if (!workspace || workspace_bytes < need)
-    return fail(IREC_E_WORKSPACE, "irec_beam_encode: workspace %zu bytes < required %zu", workspace_bytes, need);
-  // top-B margins: a margin build of the team encoder where one serves the call's shape (whatever the call's size), else the generic
-  // kernel, which draws in the kernel: no tables
-  const int mshape = out_margin ? margin_team_shape(ctx, pl, p, n_blocks) : -1;
-  if (out_margin && mshape < 0) { pl.table = false; pl.team = false; pl.lone = false; pl.chunk = false; pl.fast = false; pl.team_only = false; pl.n_tab = 0; pl.K_tab = 0; }
-  pl.team = mshape >= 0 ? true : team_for_call(ctx, pl, p, n_blocks);
+  // every decision of the call: the kernel, its grid and widths, the workspace layout, the deferred pass
+  const CallPlan cp = plan_call(irec::context_cus(ctx), p, n_blocks, max_block_dim, max_K, workspace ? workspace_bytes : 0);
+  if (!workspace || workspace_bytes < cp.ws_bytes)
+    return fail(IREC_E_WORKSPACE, "irec_beam_encode: workspace %zu bytes < required %zu", workspace_bytes, cp.ws_bytes);
   if (((uintptr_t)workspace & 255) != 0) return fail(IREC_E_WORKSPACE, "irec_beam_encode: workspace must be 256-byte aligned");
   IREC_ON_DEVICE(ctx->device);
   hipStream_t st = (hipStream_t)hip_stream;
@@ -1183,199 +1220,99 @@ irec_status irec_beam_encode_ex(irec_context *ctx, const irec_params *p, int64_t
   A.counter = (unsigned int *)workspace;
   A.xcd_counter = (unsigned int *)workspace + irec::WS_XCD_WORD;
   A.defer_count = (unsigned int *)workspace + 1;
-  if (mshape >= 0) pl.shape = mshape;
-  else if (pl.team) pl.shape = shape_for_call(ctx, pl, p, n_blocks);
-  A.K_tab = pl.K_tab; A.deferred_pass = 0; A.shape_override = pl.shape; A.no_ten = (p->flags & IREC_FLAG_NO_TEN) ? 1 : 0;
+  A.K_tab = cp.K_tab; A.deferred_pass = 0; A.shape_override = cp.shape; A.no_ten = (p->flags & IREC_FLAG_NO_TEN) ? 1 : 0;
   A.coop_W = 1; A.coop_err = (unsigned int *)workspace + 3; A.coop_arrive = (unsigned int *)workspace + 64;
   A.coop_xch = (uint32_t *)((char *)workspace + irec::WS_COUNTER_BYTES);
-  A.ws = (char *)workspace + irec::WS_HEAD_BYTES + pl.tab_bytes;
-  A.ws_per_wg = pl.ws_per_wg;
-  A.max_dim_pad = pl.dpad;
+  A.ws = (char *)workspace + irec::WS_HEAD_BYTES + cp.tab_bytes;
+  A.ws_per_wg = cp.ws_per_wg;
+  A.max_dim_pad = cp.dpad;
   A.out_margin = out_margin;
   // table bookkeeping (IREC_FLAG_REUSE_TABLES): the key of every proposal table this call needs -- what it is a function
   // of (seed, S, D, window), which kernel writes it (the team encoder's rows carry copy bits) and where it lies -- is
   // compared with the slot's stamp ON THE DEVICE by the preparation kernel; a slot the call does not use is stamped with zeros,
   // so a call without tables (whose slabs may lie over the table area) invalidates what was there
   irec::TableStamps stamps{};
-  if (pl.table)
-    for (int q = 0; q < pl.n_tab; ++q) {
+  if (cp.table)
+    for (int q = 0; q < cp.n_tab; ++q) {
       uint32_t *w = stamps.w[q];
-      w[0] = 0x7ab1e000u | ((pl.team || pl.chunk) ? 1u : 2u);   // (rows with copy bits / plain byte offsets)
+      w[0] = 0x7ab1e000u | ((cp.team || cp.chunk) ? 1u : 2u);   // (rows with copy bits / plain byte offsets)
       w[1] = (uint32_t)(uint64_t)seed; w[2] = (uint32_t)((uint64_t)seed >> 32);
-      w[3] = (uint32_t)p->n_samples; w[4] = (uint32_t)pl.tab_dim[q]; w[5] = (uint32_t)pl.K_tab;
-      w[6] = (uint32_t)pl.tab_off[q];
+      w[3] = (uint32_t)p->n_samples; w[4] = (uint32_t)cp.tab_dim[q]; w[5] = (uint32_t)cp.K_tab;
+      w[6] = (uint32_t)cp.tab_off[q];
       w[7] = ~(w[1] ^ w[2] ^ w[3] ^ w[4] ^ w[5] ^ w[6]);
     }
   stamps.reuse = (p->flags & IREC_FLAG_REUSE_TABLES) ? 1 : 0;
-  // the call in numbers (grid, teams per workgroup, cooperative width, cost-ordered hand-out): call_detail, also behind irec_test_plan
-  const CallDetail cd = call_detail(ctx, pl, p, n_blocks, max_block_dim, out_margin != nullptr);
-  const int split_blocks = cd.split_blocks;   // a cooperative call: the preparation kernel also zeroes the exchange granules of its blocks
-  if (cd.placed) A.row_cost = (const uint32_t *)((char *)workspace + irec::WS_COUNTER_BYTES + irec::WS_XCH_BYTES);
-  int grid = (int)std::min<int64_t>(n_blocks, pl.one_grid_cap);
+  if (cp.placed) A.row_cost = (const uint32_t *)((char *)workspace + irec::WS_COUNTER_BYTES + irec::WS_XCH_BYTES);
   A.dbg = nullptr;
 #ifdef IREC_HOST_STAMPS
   A.dbg = ctx->d_dbg;
   if (ctx->d_dbg) HIP_TRY(hipMemsetAsync(ctx->d_dbg, 0, 4096 * 16 * sizeof(unsigned long long), st));
 #endif
-  // ONE preparation kernel per call: books, exchange granules, row costs and the proposal tables (irec_kernels.h)
+  // ONE preparation kernel per call: books, exchange granules (a cooperative call: those of its blocks), row costs and the proposal tables (irec_kernels.h)
   irec::PrepArgs P{};
   P.head = (uint32_t *)workspace; P.ts = stamps;
-  P.n_granule = irec::IREC_COOP_GRANULES_ON && split_blocks > 0 ? std::min(split_blocks, irec::COOP_MAX_BLOCKS) : 0;
+  P.n_granule = irec::IREC_COOP_GRANULES_ON && cp.split_blocks > 0 ? std::min(cp.split_blocks, irec::COOP_MAX_BLOCKS) : 0;
   P.n_cost = A.row_cost ? (int32_t)n_blocks : 0;
   P.cost = const_cast<uint32_t *>(A.row_cost);
-  P.seed = seed; P.S = p->n_samples; P.K_tab = pl.K_tab; P.dlog4r = ctx->d_dlog4r;
+  P.seed = seed; P.S = p->n_samples; P.K_tab = cp.K_tab; P.dlog4r = ctx->d_dlog4r;
   A.ws_head = (uint32_t *)workspace;
   for (int q = 0; q < 4; ++q) { A.tab[q] = nullptr; A.tab_dim[q] = -1; }
-  if (pl.table) {
-    for (int q = 0; q < pl.n_tab; ++q) {
-      uint16_t *tab = (uint16_t *)((char *)workspace + irec::WS_HEAD_BYTES + pl.tab_off[q]);
-      A.tab[q] = tab; A.tab_dim[q] = pl.tab_dim[q];
+  if (cp.table) {
+    for (int q = 0; q < cp.n_tab; ++q) {
+      uint16_t *tab = (uint16_t *)((char *)workspace + irec::WS_HEAD_BYTES + cp.tab_off[q]);
+      A.tab[q] = tab; A.tab_dim[q] = cp.tab_dim[q];
       P.jobs.tab[q] = tab; P.jobs.keep[q] = nullptr;
     }
-    if (pl.n_tab > 0 && !(p->flags & IREC_FLAG_TABLES_PRESENT)) {   // (TABLES_PRESENT: the caller's previous call on this workspace built exactly these)
-      P.table_kind = (pl.team || pl.chunk) ? 1 : 2;                  // rows with copy bits / plain rows
-      P.n_table_wgs = (int32_t)irec::prep_table_wgs(P.table_kind, p->n_samples, pl.K_tab, pl.n_tab, pl.tab_dim, &P.jobs);
+    if (cp.n_tab > 0 && !(p->flags & IREC_FLAG_TABLES_PRESENT)) {   // (TABLES_PRESENT: the caller's previous call on this workspace built exactly these)
+      P.table_kind = (cp.team || cp.chunk) ? 1 : 2;                  // rows with copy bits / plain rows
+      P.n_table_wgs = (int32_t)irec::prep_table_wgs(P.table_kind, p->n_samples, cp.K_tab, cp.n_tab, cp.tab_dim, &P.jobs);
     }
   }
   HIP_TRY(irec::launch_prep(P, A, st));
-  if (pl.table) {
-    // second pass (only when the window is shorter than max_K): the fused-Philox encoder codes the blocks whose K lies
-    // beyond the table window; it returns at once when the first pass deferred nothing
-    auto deferred_pass = [&]() -> irec_status {
-      if (pl.K_tab >= max_K) return IREC_OK;
-      irec::EncArgs A2 = A;
-      A2.deferred_pass = 1; A2.coop_W = 1;
-      A2.counter = (unsigned int *)workspace + 2;
-      for (int q = 0; q < 4; ++q) { A2.tab[q] = nullptr; A2.tab_dim[q] = -1; }
-      if (out_margin) HIP_TRY(irec::launch_encode_generic(A2, (int)std::min<int64_t>(n_blocks, std::min(pl.grid_cap, 2 * (ctx->n_cu > 0 ? ctx->n_cu : 256))), st));
-      else if (pl.team_only || pl.chunk) HIP_TRY(irec::launch_encode_generic(A2, (int)std::min<int64_t>(n_blocks, pl.fast_grid_cap), st));
-      else HIP_TRY(irec::launch_encode_fast(A2, false, (int)std::min<int64_t>(n_blocks, pl.fast_grid_cap), st));
-      return IREC_OK;
-    };
-    if (pl.chunk) {   // one workgroup per CU, a block of any dim count per team; steps beyond the table window are drawn in the kernel: no second pass
-      const int cgrid = cd.grid;
-      if (cd.W >= 2) {
-        A.coop_W = cd.W; A.gang_chunks = cd.gang_chunks;
-        A.gang_xch = (char *)workspace + irec::WS_HEAD_BYTES + pl.tab_bytes + (size_t)pl.grid_cap * pl.ws_per_wg;
-        A.gang_stride = pl.gang_stride;
-        A.coop_test_orphan = (p->flags & IREC_FLAG_TEST_SPLIT_ORPHAN) ? 1 : 0;
-      }
-      HIP_TRY(irec::launch_encode_chunk(A, cgrid, st));
-    } else if (pl.team && pl.lone) { // one workgroup per CU, a block per wave
-      HIP_TRY(irec::launch_encode_lone(A, cd.grid, st));
-      if (irec_status s2 = deferred_pass()) return s2;
-#ifdef IREC_HOST_STAMPS
-      if (ctx->d_dbg) {   // diagnostic build (-DIREC_LONE_STAMPS): per-wave phase cycles of the one-beam encoder
-        const int lgrid = batch_grid(n_blocks, ctx->n_cu > 0 ? ctx->n_cu : 256), nwv = irec::lone_waves();
-        std::vector<unsigned long long> h((size_t)lgrid * nwv * 16);
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(h.data(), ctx->d_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        static const char *nm[6] = {"prologue (fetch, KL)", "step constants", "scoring", "selection", "update", "epilogue"};
-        double sum[6] = {0}, tot = 0;
-        for (size_t w = 0; w < (size_t)lgrid * nwv; ++w) for (int k = 0; k < 6; ++k) { sum[k] += (double)h[w * 16 + k]; tot += (double)h[w * 16 + k]; }
-        fprintf(stderr, "[irec lone stamps] share of wave time:\n");
-        for (int k = 0; k < 6; ++k) fprintf(stderr, "  %-22s %5.1f%%\n", nm[k], 100 * sum[k] / tot);
-        fprintf(stderr, "  cycles per wave: %.0f\n", tot / (lgrid * nwv));
-        return IREC_OK;
-      }
-#endif
-    } else if (pl.team) { // grid_cap counts teams (= scratch slabs): two per workgroup, one workgroup per CU
-      const int tgrid = cd.grid;
-#ifdef IREC_HOST_STAMPS
-      const int n_teams = cd.teams;
-#endif
-      if (cd.W >= 2) {   // rows [share_first, n_blocks) are coded by W teams each; the static round deals every slot
-        A.coop_W = cd.W; A.tsplit_first = cd.share_first;
-        A.coop_test_orphan = (p->flags & IREC_FLAG_TEST_SPLIT_ORPHAN) ? 1 : 0;
-      }
-      if (out_margin) HIP_TRY(irec::launch_encode_team_margin(A, tgrid, st));
-      else HIP_TRY(irec::launch_encode_team(A, tgrid, st));
-#ifndef IREC_HOST_STAMPS
-      if (irec_status s2 = deferred_pass()) return s2;
-#else
-      if (!ctx->d_dbg) { if (irec_status s2 = deferred_pass()) return s2; }
-      if (ctx->d_dbg) { // diagnostic build (-DIREC_TEAM_STAMPS) only: per-wave phase cycles, wave 0 of a team vs the others
-        const bool ten_call = !cd.W && !out_margin && !(p->flags & IREC_FLAG_NO_TEN) && irec::team_ten_teams(p->n_beams, p->n_samples, pl.shape) != 0;
-        const int nwv = ten_call ? 4 * n_teams : irec::team_waves_for(p->n_beams, p->n_samples, pl.shape);
-        std::vector<unsigned long long> h((size_t)tgrid * nwv * 16);
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(h.data(), ctx->d_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        static const char *nm[12] = {"fetch", "prologue", "scoring", "wait-score", "combine", "select", "update-tail", "wait-update", "epilogue",
-                                     "upd:sel+issue+consts", "upd:batches", "-"};
-        // (waves of teams that coded no block -- a mid-size call leaves team slots empty -- are left out of the averages)
-        const int nwt = nwv / n_teams;   // waves per team
-        double w0[12] = {0}, wo[12] = {0}, t0 = 0, to = 0;
-        int n0 = 0, no = 0;
-        for (int w = 0; w < tgrid * nwv; ++w) {
-          if (h[(size_t)w * 16 + 1] == 0ull) continue;   // no prologue: no block
-          if ((w % nwt) == 0) ++n0; else ++no;
-          for (int k = 0; k < 12; ++k) { const double v = (double)h[(size_t)w * 16 + k]; if ((w % nwt) == 0) { w0[k] += v; t0 += v; } else { wo[k] += v; to += v; } }
-        }
-        fprintf(stderr, "[irec team stamps] %d of %d teams coded blocks; share of wave time (cycles per wave), wave 0 of a team | the others:\n", n0, tgrid * n_teams);
-        t0 -= w0[11]; to -= wo[11];   // (slot 11 counts block-steps, not cycles)
-        for (int k = 0; k < 11; ++k) fprintf(stderr, "  %-20s %5.1f%% (%8.0f) | %5.1f%% (%8.0f)\n", nm[k], 100 * w0[k] / t0, w0[k] / (n0 ? n0 : 1), 100 * wo[k] / to, wo[k] / (no ? no : 1));
-        fprintf(stderr, "  cycles per wave: %.0f | %.0f;  block-steps per wave: %.2f;  cycles per block-step: %.0f\n", t0 / (n0 ? n0 : 1), to / (no ? no : 1),
-                w0[11] / (n0 ? n0 : 1), w0[11] > 0 ? t0 / w0[11] : 0.0);
-        {   // idle tail of the persistent grid: wave-time between a wave's exit and the last wave's (slot 12 = a wave's lifetime)
-          double life_max = 0, life_sum = 0, life_min = 1e300;
-          int nlife = 0;
-          for (int w = 0; w < tgrid * nwv; ++w) {
-            const double v = (double)h[(size_t)w * 16 + 12];
-            if (v <= 0) continue;
-            life_max = std::max(life_max, v); life_min = std::min(life_min, v); life_sum += v; ++nlife;
-          }
-          if (nlife) fprintf(stderr, "  idle tail: %.1f%% of the grid's wave-time lies behind a wave's exit (first exit at %.1f%% of the longest lifetime)\n",
-                             100.0 * (1.0 - life_sum / (nlife * life_max)), 100.0 * life_min / life_max);
-        }
-        if (h[13]) fprintf(stderr, "  shader clock of workgroup 0, wave 0: %.0f MHz over %.3f ms (s_memtime / s_memrealtime)\n",
-                           100.0 * (double)h[12] / (double)h[13], (double)h[13] / 1e5);
-        return IREC_OK;
-      }
-#endif
-    } else {
-      const int W = cd.W;
-      A.coop_beams = cd.coop_beams;
-      if (W >= 2) {
-        A.coop_W = W;
-        A.coop_test_orphan = (p->flags & IREC_FLAG_TEST_SPLIT_ORPHAN) ? 1 : 0;
-        HIP_TRY(irec::launch_encode_fast(A, true, cd.grid, st));
-#ifdef IREC_HOST_STAMPS
-        if (ctx->d_dbg) grid = cd.grid;   // (diagnostics below: the stamps of every workgroup)
-#endif
-      } else HIP_TRY(irec::launch_encode_fast(A, true, grid, st));
-      if (irec_status s2 = deferred_pass()) return s2;
+  if (cp.W >= 2) {   // gang members per block / teams per shared row / workgroups per block
+    A.coop_W = cp.W;
+    A.coop_test_orphan = (p->flags & IREC_FLAG_TEST_SPLIT_ORPHAN) ? 1 : 0;
+  }
+  switch (cp.kind) {
+  case KIND_CHUNK:
+    if (cp.W >= 2) {
+      A.gang_chunks = cp.gang_chunks;
+      A.gang_xch = (char *)workspace + irec::WS_HEAD_BYTES + cp.tab_bytes + (size_t)cp.grid_cap * cp.ws_per_wg;
+      A.gang_stride = cp.gang_stride;
     }
-  } else if (pl.fast) {
-    HIP_TRY(irec::launch_encode_fast(A, false, grid, st));
-  } else {
-    if (out_margin) grid = (int)std::min<int64_t>(n_blocks, std::min(pl.grid_cap, 2 * (ctx->n_cu > 0 ? ctx->n_cu : 256)));
-    HIP_TRY(irec::launch_encode_generic(A, grid, st));
+    HIP_TRY(irec::launch_encode_chunk(A, cp.grid, st));
+    break;
+  case KIND_LONE:
+    HIP_TRY(irec::launch_encode_lone(A, cp.grid, st));
+    break;
+  case KIND_TEAM:
+    if (cp.W >= 2) A.tsplit_first = cp.share_first;
+    if (cp.margin_build) HIP_TRY(irec::launch_encode_team_margin(A, cp.grid, st));
+    else HIP_TRY(irec::launch_encode_team(A, cp.grid, st));
+    break;
+  case KIND_TABLE:
+    A.coop_beams = cp.coop_beams;
+    HIP_TRY(irec::launch_encode_fast(A, true, cp.grid, st));
+    break;
+  case KIND_FUSED:
+    HIP_TRY(irec::launch_encode_fast(A, false, cp.grid, st));
+    break;
+  default:
+    HIP_TRY(irec::launch_encode_generic(A, cp.grid, st));
   }
 #ifdef IREC_HOST_STAMPS
-  if (ctx->d_dbg) { // diagnostic build only: synchronous read-back of the phase stamps
-    std::vector<unsigned long long> h((size_t)grid * 16);
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipMemcpy(h.data(), ctx->d_dbg, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    double sum[16] = {0};
-    for (int w = 0; w < grid; ++w) for (int k = 0; k < 16; ++k) sum[k] += (double)h[(size_t)w * 16 + k];
-    const double tot = sum[0] + sum[1] + sum[2] + sum[3];
-    {
-      int zero = 0; unsigned long long t0 = ~0ull, late = 0;
-      for (int w = 0; w < grid; ++w) { if (h[(size_t)w * 16 + 4] == 0) ++zero; else if (h[(size_t)w * 16 + 5] < t0) t0 = h[(size_t)w * 16 + 5]; }
-      for (int w = 0; w < grid; ++w) if (h[(size_t)w * 16 + 4] && h[(size_t)w * 16 + 5] - t0 > 100000ull) ++late; // > 1 ms at 100 MHz
-      fprintf(stderr, "[irec stamps] census: %d of %d workgroups coded no block, %llu started > 1 ms after the first\n", zero, grid, late);
-    }
-    fprintf(stderr, "[irec stamps] top-B detail cycles/WG: combine %.0f, wait-for-keys barrier %.0f, wave-0 select %.0f, closing barrier %.0f\n",
-            sum[11] / grid, sum[8] / grid, sum[9] / grid, sum[10] / grid);
-    if (sum[12] + sum[13] + sum[14] > 0)
-      fprintf(stderr, "[irec stamps] split exchange cycles/WG: publish %.0f, wait for partners %.0f, read back %.0f\n",
-              sum[12] / grid, sum[13] / grid, sum[14] / grid);
-    fprintf(stderr, "[irec stamps] waves/workgroup %d, LDS %zu B\n",
-            irec::fast_waves_for(p->n_beams, p->n_samples, pl.table), irec::fast_lds_for(p->n_beams, p->n_samples, pl.table));
-    fprintf(stderr, "[irec stamps] %s grid=%d cycles/WG: prologue %.0f (%.1f%%) scoring %.0f (%.1f%%) select %.0f (%.1f%%) update %.0f (%.1f%%)\n",
-            pl.table ? "table" : pl.fast ? "fused" : "generic", grid, sum[0] / grid, 100 * sum[0] / tot, sum[1] / grid,
-            100 * sum[1] / tot, sum[2] / grid, 100 * sum[2] / tot, sum[3] / grid, 100 * sum[3] / tot);
+  if (ctx->d_dbg && cp.kind == KIND_TEAM) return print_team_stamps(ctx, cp, p->n_beams, p->n_samples, st);   // (without the deferred pass)
+#endif
+  if (cp.deferred != DEFER_NONE) {   // the same arguments without tables, on a block counter of its own
+    A.deferred_pass = 1; A.coop_W = 1;
+    A.counter = (unsigned int *)workspace + 2;
+    for (int q = 0; q < 4; ++q) { A.tab[q] = nullptr; A.tab_dim[q] = -1; }
+    if (cp.deferred == DEFER_GENERIC) HIP_TRY(irec::launch_encode_generic(A, cp.deferred_grid, st));
+    else HIP_TRY(irec::launch_encode_fast(A, false, cp.deferred_grid, st));
   }
+#ifdef IREC_HOST_STAMPS
+  if (ctx->d_dbg && cp.kind == KIND_LONE) return print_lone_stamps(ctx, cp, st);
+  if (ctx->d_dbg && cp.kind != KIND_CHUNK) return print_one_wg_stamps(ctx, cp, p->n_beams, p->n_samples, st);
 #endif
   return IREC_OK;
 }
@@ -1448,7 +1385,7 @@ static irec_status beam_decode_impl(irec_context *ctx, const irec_params *p, int
     A.n_tensors = tens->n_tensors; A.tn = tens->n; A.tbs = tens->bs; A.tbpt = (tens->n + tens->bs - 1) / tens->bs;
     A.block_row = tens->block_row;
   }
-  HIP_TRY(irec::launch_decode(A, ctx->n_cu > 0 ? ctx->n_cu : 256, st));
+  HIP_TRY(irec::launch_decode(A, irec::context_cus(ctx), st));
   return IREC_OK;
 }
 

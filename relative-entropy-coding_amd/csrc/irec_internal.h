@@ -41,9 +41,10 @@ extern "C" {
 
 
 /* ---- test hooks (host memory) -------------------------------------------------------------------------------------------- */
-/* The launch of irec_beam_encode(p, n_blocks, max_block_dim, max_K) on a device of n_cu compute units, in numbers -- the same code the
- * launch runs (irec_host.cpp: call_detail), no device touched: the planner's invariants are tested host-only at other CU counts than the
- * one box everything was measured on (MI355X partition modes expose 32 / 64 / 128 CUs).
+/* The launch of irec_beam_encode(p, n_blocks, max_block_dim, max_K) on a device of n_cu compute units, in numbers -- the settled plan the
+ * launch itself runs from (irec_host.cpp: plan_call; `info` is that plan as irec_encode_plan words it), no device touched: the planner's
+ * invariants are tested host-only at other CU counts than the one box everything was measured on (MI355X partition modes expose 32 / 64 /
+ * 128 CUs).
  *   kind 1 chunked, 2 one-beam, 3 team (encode_team_kernel / encode_ten_kernel), 4 one-table / split, 5 fused-Philox fast, 6 generic */
 typedef struct {
   int32_t kind, grid, teams_per_wg;   /* workgroups; teams (= scratch slabs) per workgroup: slab index < grid * teams_per_wg           */
@@ -52,11 +53,17 @@ typedef struct {
   int32_t placed;                     /* team encoder: rows dealt by cost -- the kernel requires the static round to deal EVERY slot  */
   int32_t split_blocks;               /* blocks whose exchange granules the preparation kernel zeroes                                 */
   int64_t share_first, n_slots;       /* first shared row; hand-out slots (whole rows + coop_width per shared row / block)             */
-  int64_t slabs_in_workspace, slab_bytes, fixed_bytes;   /* what irec_encode_workspace_bytes sizes: fixed + slabs * slab_bytes        */
+  int64_t slabs_in_workspace, slab_bytes, fixed_bytes;   /* the layout of the call's workspace: fixed + slabs * slab_bytes           */
   int32_t exchange_rows, exchange_keys;                  /* key exchange: shared blocks per call, sort keys per step, at most          */
 } irec_plan_detail;
 irec_status irec_test_plan(int32_t n_cu, int32_t clock_mhz, const irec_params *p, int64_t n_blocks, int32_t max_block_dim, int32_t max_K,
                            irec_plan_info *info, irec_plan_detail *detail);
+/* The same for a call that hands irec_beam_encode a workspace of workspace_bytes: 0 = the device-wide size (irec_encode_workspace_bytes; what
+ * irec_test_plan passes), -1 = the size irec_encode_workspace_bytes_for gives this call.  Blocks of more than 1024 dims: a workspace between the
+ * two sizes holds fewer slabs than the device has team slots, and the call launches no more teams than it has slabs.  IREC_E_WORKSPACE where the
+ * launch would refuse the workspace. */
+irec_status irec_test_plan_ws(int32_t n_cu, int32_t clock_mhz, const irec_params *p, int64_t n_blocks, int32_t max_block_dim, int32_t max_K,
+                              int64_t workspace_bytes, irec_plan_info *info, irec_plan_detail *detail);
 /* out[e] = element e of tf.random.normal([count]) after tf.random.set_seed(seed) -- the stream behind
  * tfd.Normal.sample.  Host memory; test hook. */
 irec_status irec_tf_random_normal(int64_t seed, int64_t count, float *out);

@@ -1,8 +1,12 @@
 """The planner at other CU counts than the one box everything was measured on (round 5's review, Weak #6 / Next #5): MI355X exposes
-32 / 64 / 128 CUs in its partition modes, and grids, cooperative widths and slab counts all derive from n_cu.  Host-only: irec_test_plan
-(csrc/irec_internal.h) runs the code of the launch itself (irec_host.cpp: make_plan -> shape_for_call -> call_detail) for a context of any CU
-count without touching a device, and the tests assert the invariants the kernels trap on or would wait 100 ms for."""
+32 / 64 / 128 CUs in its partition modes, and grids, cooperative widths and slab counts all derive from n_cu.  Host-only: irec_test_plan and
+irec_test_plan_ws (csrc/irec_internal.h) return the settled plan the launch itself runs from (irec_host.cpp: plan_call -- one CallPlan per call,
+which irec_beam_encode_ex launches and irec_encode_plan words) for any CU count and workspace size without touching a device, and the tests
+assert the invariants the kernels trap on or would wait 100 ms for.  tests/golden/plan_snapshot.json pins the plans of CALLS
+(scripts/plan_dump.py --golden): an intended retune shows as a diff of that file."""
 import ctypes
+import json
+import os
 
 import pytest
 
@@ -32,15 +36,24 @@ CALLS = [
 ]
 
 
-def _plan(n_cu, B, S, n_blocks, max_dim, dims, max_K, flags=0):
+def _plan(n_cu, B, S, n_blocks, max_dim, dims, max_K, flags=0, workspace_bytes=None):
+    """workspace_bytes: None = irec_test_plan; else irec_test_plan_ws (0: the device-wide size, -1: the size of this call)."""
     from irec import _lib
     from irec.engine import Engine
     lib = _lib.load()
     p = Engine.params(3.0, S, B, flags, list(dims))
     info, det = _lib.IrecPlanInfo(), _lib.IrecPlanDetail()
-    st = lib.irec_test_plan(n_cu, 2400, ctypes.byref(p), n_blocks, max_dim, max_K, ctypes.byref(info), ctypes.byref(det))
+    if workspace_bytes is None:
+        st = lib.irec_test_plan(n_cu, 2400, ctypes.byref(p), n_blocks, max_dim, max_K, ctypes.byref(info), ctypes.byref(det))
+    else:
+        st = lib.irec_test_plan_ws(n_cu, 2400, ctypes.byref(p), n_blocks, max_dim, max_K, workspace_bytes, ctypes.byref(info), ctypes.byref(det))
     assert st == 0, lib.irec_last_error()
     return info.as_dict(), det.as_dict()
+
+
+def _flag_sets(max_dim):
+    from irec import _lib
+    return (0, _lib.IREC_FLAG_NO_SPLIT, _lib.IREC_FLAG_TEAM, _lib.IREC_FLAG_MARGINS if max_dim <= 1024 else 0)
 
 
 @pytest.mark.parametrize("n_cu", N_CU)
@@ -115,3 +128,46 @@ def test_thresholds_scale_with_the_cu_count():
         for n_blocks in (n_cu + 1, n_cu + n_cu // 5, 2 * n_cu - 1):
             ten, d_ten = _plan(n_cu, 10, 20, n_blocks, 1000, (1000, 192), 32)
             assert ten["kernel"] == "encode_ten_kernel<2>" and not d_ten["placed"], (n_cu, n_blocks, ten, d_ten)
+
+
+def test_plans_match_the_pinned_snapshot():
+    """Every field of irec_plan_info and irec_plan_detail for CALLS x N_CU x the four flag sets against tests/golden/plan_snapshot.json."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_snapshot.json")) as f:
+        pinned = {(r["call"], r["n_cu"], r["flags"]): r for r in json.load(f)}
+    seen = set()
+    for name, B, S, n_blocks, max_dim, dims, max_K in CALLS:
+        for n_cu in N_CU:
+            for flags in _flag_sets(max_dim):
+                info, d = _plan(n_cu, B, S, n_blocks, max_dim, dims, max_K, flags)
+                want = pinned[(name, n_cu, flags)]
+                for got, exp, what in ((info, want["info"], "info"), (d, want["detail"], "detail")):
+                    assert got.keys() == exp.keys(), (name, n_cu, flags, what)
+                    for k in exp:
+                        assert got[k] == exp[k], (name, n_cu, flags, what, k, got[k], exp[k])
+                seen.add((name, n_cu, flags))
+    assert seen == set(pinned), "the snapshot holds calls this test no longer plans"
+
+
+@pytest.mark.parametrize("n_cu", N_CU)
+@pytest.mark.parametrize("call", [c for c in CALLS if c[4] > 1024], ids=[c[0] for c in CALLS if c[4] > 1024])
+def test_workspace_limited_plans(n_cu, call):
+    """Blocks of more than 1024 dims on a workspace smaller than the device-wide one (the size irec_encode_workspace_bytes_for gives the call,
+    and one halfway to the device-wide size): the call launches no more teams than the workspace has slabs."""
+    from irec import _lib
+    name, B, S, n_blocks, max_dim, dims, max_K = call
+    for flags in (0, _lib.IREC_FLAG_NO_SPLIT):
+        wide_info, wide_d = _plan(n_cu, B, S, n_blocks, max_dim, dims, max_K, flags)
+        assert (wide_info, wide_d) == _plan(n_cu, B, S, n_blocks, max_dim, dims, max_K, flags, 0), (name, n_cu, flags)
+        wide = wide_info["workspace_bytes"]
+        own_info, _ = _plan(n_cu, B, S, n_blocks, max_dim, dims, max_K, flags, -1)
+        own = own_info["workspace_bytes"]
+        for ws in (-1, (own + (wide - own) // 2) // 256 * 256):
+            info, d = _plan(n_cu, B, S, n_blocks, max_dim, dims, max_K, flags, ws)
+            ctx = (name, n_cu, flags, ws, own, wide, info, d)
+            assert d["grid"] >= 1 and d["grid"] * d["teams_per_wg"] <= d["slabs_in_workspace"], ctx
+            assert d["fixed_bytes"] + d["slabs_in_workspace"] * d["slab_bytes"] == info["workspace_bytes"] <= wide, ctx
+            if ws > 0:
+                assert info["workspace_bytes"] <= ws, ctx
+            assert d["coop_width"] == 0 or d["coop_width"] >= 2, ctx
+            if d["coop_width"]:
+                assert d["n_slots"] == n_blocks * d["coop_width"] <= d["grid"] * d["teams_per_wg"], ctx
