@@ -433,11 +433,16 @@ static float normal_log_prob_literal(float x, float loc, float scale) {
 typedef struct { uint32_t key; int32_t flat; } cand;
 
 /* tf.argsort(DESCENDING) == top_k: value descending, ties by ascending index.  NaN sorts last. */
+static int g_wrong_ties = 0, g_wrong_nan = 0;
+/* TEST-ONLY: deliberately WRONG orderings, for tests that must prove an input would expose a kernel that has them
+ * (tests/test_tie_breaking.py).  ties_to_higher: exact ties of numbers go to the HIGHER flat index; nan_first: a NaN sorts BEFORE
+ * every number.  (0, 0) is the contract. */
+void irec_oracle_set_wrong_order(int ties_to_higher, int nan_first) { g_wrong_ties = ties_to_higher; g_wrong_nan = nan_first; }
 static int cand_before(float va, int32_t fa, float vb, int32_t fb) {
   int na = isnan(va), nb = isnan(vb);
-  if (na || nb) { if (na != nb) return nb; return fa < fb; }
+  if (na || nb) { if (na != nb) return g_wrong_nan ? na : nb; return fa < fb; }
   if (va != vb) return va > vb;
-  return fa < fb;
+  return g_wrong_ties ? fa > fb : fa < fb;
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -56,6 +56,8 @@ def lib():
         L.irec_oracle_ndtri_f32.restype = ctypes.c_float
         L.irec_oracle_build_lut.argtypes = [f32p]
         L.irec_oracle_set_lut.argtypes = [f32p]
+        L.irec_oracle_set_wrong_order.argtypes = [ctypes.c_int, ctypes.c_int]
+        L.irec_oracle_set_wrong_order.restype = None
         L.irec_oracle_py_first_randint31.argtypes = [ctypes.c_int64]
         L.irec_oracle_py_first_randint31.restype = ctypes.c_int64
         L.irec_oracle_py_randint31_nth.argtypes = [ctypes.c_int64, ctypes.c_int64]
@@ -152,6 +154,13 @@ def set_lut(lut=None):
     a = np.ascontiguousarray(lut, dtype=np.float32)
     assert a.shape == (P,), a.shape
     lib().irec_oracle_set_lut(_p(a, ctypes.c_float))
+
+
+def set_wrong_order(ties_to_higher=False, nan_first=False):
+    """TEST-ONLY: makes the coder functions order candidates WRONGLY -- exact ties to the higher flat index, a NaN before every
+    number -- so that a test can prove its inputs would expose a kernel that does (tests/test_tie_breaking.py).  No arguments: the
+    contract."""
+    lib().irec_oracle_set_wrong_order(int(bool(ties_to_higher)), int(bool(nan_first)))
 
 
 def py_first_randint31(seed):

@@ -78,8 +78,23 @@ def flag_sets(_lib):
             sh["team"] | _lib.IREC_FLAG_TEAM, sh["3"] | _lib.IREC_FLAG_NO_TEN)
 
 
-def enumerate_plans(n_cu=256, dims=DIMS, blocks=BLOCKS):
-    """canonical kernel name -> the cheapest call of the grid that launches it: dict(B, S, n_blocks, dim, max_K, flags, plan)."""
+def case_inputs(oracle, case, seed=7):
+    """The host arrays (mq, sq, mp, sp), each [n_blocks, dim], that the tests of a planner case code: one synthetic latent a block."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    stats = [oracle.synthetic_latent(3000 + int(rng.integers(1 << 20)), case["dim"]) for _ in range(case["n_blocks"])]
+    return [np.stack([s[j] for s in stats]) for j in range(4)]
+
+
+def rejects_by_step_two(B, S):
+    """A call of B beams and S samples rejects a candidate in its first or second step (S > B, or S * min(B, S) > B): its top-B
+    selection has something to decide on every block of two or more partitions."""
+    return S > B or S * min(B, S) > B
+
+
+def enumerate_plans(n_cu=256, dims=DIMS, blocks=BLOCKS, accept=None):
+    """canonical kernel name -> the cheapest call of the grid that launches it: dict(B, S, n_blocks, dim, max_K, flags, plan).
+    accept(B, S): only calls of these beams and samples count (tests/test_tie_breaking.py: calls whose selection rejects a candidate)."""
     import sys
     for p in (ROOT, os.path.join(ROOT, "relative-entropy-coding_amd")):
         if p not in sys.path:
@@ -91,7 +106,7 @@ def enumerate_plans(n_cu=256, dims=DIMS, blocks=BLOCKS):
     best = {}
     for B in BEAMS:
         for S in SAMPLES:
-            if S * B >= 1 << 24:
+            if S * B >= 1 << 24 or (accept is not None and not accept(B, S)):
                 continue
             for dim, max_K in dims:
                 for flags in flag_sets(_lib):

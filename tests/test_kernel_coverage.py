@@ -49,9 +49,7 @@ def test_every_planned_kernel_matches_the_oracle(engine, oracle, name):
     ex = _plans(engine.plan(engine.params(3.0, 36, 20), engine.layout(1, 192, 192, 42), 8)["n_cu"])[name]
     B, S, n_blocks, dim, max_K, flags = ex["B"], ex["S"], ex["n_blocks"], ex["dim"], ex["max_K"], ex["flags"]
     margins = bool(flags & _lib.IREC_FLAG_MARGINS)
-    rng = np.random.default_rng(7)
-    stats = [oracle.synthetic_latent(3000 + int(rng.integers(1 << 20)), dim) for _ in range(n_blocks)]
-    host = [np.stack([s[j] for s in stats]) for j in range(4)]
+    host = kn.case_inputs(oracle, ex)
     ql, qs, pl, ps = (torch.from_numpy(a).cuda().contiguous() for a in host)
     lay = engine.layout(n_blocks, dim, dim, 42)                       # one block per tensor, shuffled (coder.py:62-83)
     assert lay.n_blocks == n_blocks and lay.max_dim == dim
