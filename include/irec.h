@@ -446,6 +446,47 @@ irec_status irec_rec_decode_files(const uint8_t *bytes, const int64_t *offsets, 
                                   int32_t blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
                                   int32_t n_threads);
 
+/* The same two calls on the device (csrc/irec_rec.hip over csrc/irec_rec_core.h): the files of a batch built from, and read into,
+ * device memory, one lane per stream, so that no index crosses to the host between a batch and its bytes.  Every pointer but
+ * `workspace`'s size is a device pointer.  Asynchronous on hip_stream like every device entry point here: no allocation, no
+ * synchronisation, no copy to the host inside; argument errors the host can see return IREC_E_INVALID.  Default symbol models only.
+ * irec_rec_encode_files_device: block b = (i R + r) bpt + j has its count at K[b k_stride] and its row at idx[b idx_stride + t] --
+ *   the packed arrays (k_stride 1, idx_stride max_K) or one joined [rows][1 + width] tensor (K in column 0, both strides
+ *   1 + width).  offsets [n_images + 1] and status [n_images] are always written; a file with a nonzero status has no bytes.
+ *   The bytes are written only if offsets[n_images] <= cap (else nothing at all: call again with that much room).
+ * irec_rec_decode_files_device: headers [n][9], K [n][R][bpt], idx [n][R][bpt][max_K] as irec_rec_decode_files gives them; an image
+ *   with a nonzero status has all three zeroed, and no read leaves its [offsets[i], offsets[i + 1]). */
+typedef enum {
+  IREC_REC_OK = 0,
+  IREC_REC_E_K_RANGE = 1,           /* encode: a partition count outside [0, max_K]                                       */
+  IREC_REC_E_INDEX_RANGE = 2,       /* encode: an index outside [0, max_index)                                            */
+  IREC_REC_E_MODEL_RANGE = 3,       /* encode: the model's total exceeds 2^30 (max_index above ~1.07 million)             */
+  IREC_REC_E_TRUNCATED_HEADER = 4,  /* decode: fewer bytes than the static or the dynamic header                          */
+  IREC_REC_E_COUNT_FILES = 5,       /* decode: the file uses empirical count tables                                       */
+  IREC_REC_E_MAX_INDEX = 6,         /* decode: max_index outside [1, 2^24]                                                */
+  IREC_REC_E_BLOCK_COUNTS = 7,      /* decode: max_part above IREC_MAX_PARTITIONS, or more blocks than the count stream holds */
+  IREC_REC_E_TRUNCATED_STREAMS = 8, /* decode: a stream ends past the file                                                */
+  IREC_REC_E_COUNT_MARKER = 9,      /* decode: a count stream without its marker bit                                      */
+  IREC_REC_E_COUNT_CORRUPT = 10,    /* decode: a count stream with target < 0 or width <= 0                               */
+  IREC_REC_E_COUNT_BUDGET = 11,     /* decode: a count stream whose renormalisation budget ran out (no terminator)        */
+  IREC_REC_E_INDEX_MODEL = 12,      /* decode: the header's max_index gives a model total above 2^30                      */
+  IREC_REC_E_INDEX_MARKER = 13,     /* decode: an index stream without its marker bit                                     */
+  IREC_REC_E_INDEX_CORRUPT = 14,    /* decode: an index stream with target < 0 or width <= 0                              */
+  IREC_REC_E_INDEX_BUDGET = 15,     /* decode: an index stream whose renormalisation budget ran out (no terminator)       */
+  IREC_REC_E_MISMATCH = 16,         /* decode: counts or indices do not match the header (also: more values than allowed) */
+  IREC_REC_E_STRUCTURE = 17,        /* decode: not n_res_blocks residual blocks of blocks_per_res blocks each             */
+  IREC_REC_E_MAX_K = 18             /* decode: a block with more partitions than max_K                                    */
+} irec_rec_status;
+size_t irec_rec_device_workspace_bytes(int32_t n_images, int32_t n_res_blocks);
+irec_status irec_rec_encode_files_device(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                         uint32_t channels, int32_t n_images, int32_t n_res_blocks, int32_t blocks_per_res, int32_t max_K,
+                                         const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride,
+                                         uint8_t *out, int64_t cap, int64_t *offsets /*[n_images + 1]*/, int32_t *status /*[n_images]*/,
+                                         void *workspace, size_t workspace_bytes, void *hip_stream);
+irec_status irec_rec_decode_files_device(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                         int32_t blocks_per_res, int32_t max_K, uint32_t *headers /*[n][9]*/, int32_t *K, int32_t *idx,
+                                         int32_t *status, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,6 +77,17 @@ irec_status irec_tf_stateless_normal(int64_t seed0, int64_t seed1, int64_t count
 int32_t irec_test_fit_chunk(int32_t chunk);
 irec_status irec_test_det_exp(const double *in, int64_t n, double *out);
 
+/* The device .rec coder's core (csrc/irec_rec_core.h) over HOST memory, lane after lane in a plain loop: irec_rec_encode_files_device /
+ * irec_rec_decode_files_device without workspace and stream, so that the core is checked against irec_io.cpp where there is no GPU, and
+ * every file the device is given in a test has been through the same code on a CPU first. */
+irec_status irec_rec_test_core_encode_files(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                            uint32_t channels, int32_t n_images, int32_t n_res_blocks, int32_t blocks_per_res, int32_t max_K,
+                                            const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride,
+                                            uint8_t *out, int64_t cap, int64_t *offsets, int32_t *status);
+irec_status irec_rec_test_core_decode_files(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                            int32_t blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
+                                            int32_t *status);
+
 /* ---- hand-offs of the RVAE model shim (device pointers, asynchronous; rec/models/resnet_vae.py:372-497) -------------------------
  * What lies between the convolutions of BidirectionalResidualBlock.call on the compression path, one launch each instead of
  * ~10 elementwise PyTorch launches per residual block and pass.  Activations NCHW float32 contiguous; statistics / latent NHWC.

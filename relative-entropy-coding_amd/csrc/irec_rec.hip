@@ -1,0 +1,202 @@
+// irec_rec.hip -- the .rec container on the device: a batch's files built from, and read into, device memory (include/irec.h:
+// irec_rec_encode_files_device / irec_rec_decode_files_device).  The coder itself is csrc/irec_rec_core.h, which the host hooks at the
+// end of this file run over host memory in a plain loop; the kernels here only deal its lane functions out.
+//
+// One lane per stream, 2 N R streams per call, index streams first and count streams after them, so that a wave holds streams of one
+// kind.  256-lane workgroups, plain launches, no atomics: every store goes into a byte range that only its lane owns.
+//   encode:  rec_size_kernel (bits of every stream, input checks) -> rec_layout_kernel (bytes per file, exclusive scan: offsets, status)
+//            -> rec_write_kernel (headers, streams; nothing at all if the files do not fit cap)
+//   decode:  rec_decode_counts_kernel (header checks, K) -> rec_decode_indices_kernel (index rows by that K)
+//            -> rec_decode_status_kernel (one status per image; the outputs of an image with an error zeroed)
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <exception>
+#include <vector>
+
+#include "irec_internal.h"
+#include "irec_rec_core.h"
+
+namespace irec {
+irec_status set_last_error(irec_status code, const char *who, const char *what);   // irec_host.cpp
+
+namespace {
+constexpr int REC_NT = 256;
+
+__global__ __launch_bounds__(REC_NT) void rec_size_kernel(irec_rec::EncodeCall c) {
+  const int64_t lane = (int64_t)blockIdx.x * REC_NT + threadIdx.x;
+  if (lane < 2 * (int64_t)c.N * c.R) irec_rec::encode_size_lane(c, lane);
+}
+
+// One workgroup: lane t takes the images [t * per, (t + 1) * per), so any N is covered; the 256 partial sums are scanned in LDS.
+__global__ __launch_bounds__(REC_NT) void rec_layout_kernel(irec_rec::EncodeCall c) {
+  __shared__ int64_t part[REC_NT];
+  const int t = threadIdx.x;
+  const int64_t per = ((int64_t)c.N + REC_NT - 1) / REC_NT, lo = t * per, hi = lo + per < c.N ? lo + per : c.N;
+  int64_t sum = 0;
+  for (int64_t i = lo; i < hi; ++i) sum += irec_rec::encode_image_bytes(c, i);   // (also leaves status[i])
+  part[t] = sum;
+  __syncthreads();
+  for (int d = 1; d < REC_NT; d *= 2) {
+    const int64_t add = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  int64_t at = part[t] - sum;                                                    // exclusive
+  // the sizes once more, from the statuses just written by this very lane
+  for (int64_t i = lo; i < hi; ++i) { c.offsets[i] = at; at += irec_rec::encode_image_bytes(c, i); }
+  if (t == REC_NT - 1) c.offsets[c.N] = part[t];
+}
+
+__global__ __launch_bounds__(REC_NT) void rec_write_kernel(irec_rec::EncodeCall c) {
+  const int64_t lane = (int64_t)blockIdx.x * REC_NT + threadIdx.x;
+  if (lane < 2 * (int64_t)c.N * c.R + c.N) irec_rec::encode_write_lane(c, lane);
+}
+
+__global__ __launch_bounds__(REC_NT) void rec_decode_counts_kernel(irec_rec::DecodeCall c) {
+  const int64_t lane = (int64_t)blockIdx.x * REC_NT + threadIdx.x;
+  if (lane < (int64_t)c.N * c.R) irec_rec::decode_counts_lane(c, lane);
+}
+
+__global__ __launch_bounds__(REC_NT) void rec_decode_indices_kernel(irec_rec::DecodeCall c) {
+  const int64_t lane = (int64_t)blockIdx.x * REC_NT + threadIdx.x;
+  if (lane < (int64_t)c.N * c.R) irec_rec::decode_indices_lane(c, lane);
+}
+
+// One workgroup per image: the first cause among its residual blocks, and zeroed outputs if there is one.
+__global__ __launch_bounds__(REC_NT) void rec_decode_status_kernel(irec_rec::DecodeCall c) {
+  __shared__ int32_t first[REC_NT];
+  const int t = threadIdx.x;
+  for (int64_t i = blockIdx.x; i < c.N; i += gridDim.x) {
+    int32_t mine = 0x7fffffff;                                                   // (r << 8 | status) of the first failing block this lane saw
+    for (int32_t r = t; r < c.R; r += REC_NT) {
+      const int32_t st = irec_rec::decode_block_status(c, i * c.R + r);
+      if (st && mine == 0x7fffffff) mine = (r << 8) | st;
+    }
+    first[t] = mine;
+    __syncthreads();
+    for (int d = REC_NT / 2; d > 0; d /= 2) {
+      if (t < d && first[t + d] < first[t]) first[t] = first[t + d];
+      __syncthreads();
+    }
+    const int32_t st = first[0] == 0x7fffffff ? 0 : (first[0] & 0xff);
+    __syncthreads();
+    if (t == 0) c.status[i] = st;
+    if (st) {
+      const int64_t nK = (int64_t)c.R * c.bpt, nI = nK * c.max_K;
+      if (t < 9) c.headers[9 * i + t] = 0;
+      for (int64_t e = t; e < nK; e += REC_NT) c.K[i * nK + e] = 0;
+      for (int64_t e = t; e < nI; e += REC_NT) c.idx[i * nI + e] = 0;
+    }
+  }
+}
+
+int rec_grid(int64_t lanes) { const int64_t g = (lanes + REC_NT - 1) / REC_NT; return (int)(g < 1 ? 1 : g); }
+
+bool encode_args_ok(uint32_t height, uint32_t width, uint32_t channels, int32_t N, int32_t R, int32_t bpt, int32_t max_K, const int32_t *K,
+                    int64_t k_stride, const int32_t *idx, int64_t idx_stride, const uint8_t *out, int64_t cap, const int64_t *offsets,
+                    const int32_t *status) {
+  return N >= 0 && R >= 1 && R <= 65535 && bpt >= 1 && max_K >= 0 && K && (max_K == 0 || idx) && offsets && (N == 0 || status) && cap >= 0 &&
+         (cap == 0 || out) && k_stride >= 1 && idx_stride >= max_K && height <= 65535 && width <= 65535 && channels <= 65535 &&
+         (2 * (int64_t)N * R + N) / REC_NT < 0x7fffffff;
+}
+bool decode_args_ok(const uint8_t *bytes, const int64_t *offsets, int32_t N, int32_t R, int32_t bpt, int32_t max_K, const uint32_t *headers,
+                    const int32_t *K, const int32_t *idx, const int32_t *status) {
+  return bytes && offsets && N >= 0 && R >= 1 && R <= 65535 && bpt >= 1 && max_K >= 0 && (N == 0 || (headers && K && status)) &&
+         (N == 0 || max_K == 0 || idx) && ((int64_t)N * R) / REC_NT < 0x7fffffff;
+}
+} // namespace
+} // namespace irec
+
+#define REC_HIP(expr)                                                                                   \
+  do {                                                                                                  \
+    hipError_t e_ = (expr);                                                                             \
+    if (e_ != hipSuccess) return irec::set_last_error(IREC_E_HIP, #expr, hipGetErrorString(e_));         \
+  } while (0)
+
+extern "C" {
+
+size_t irec_rec_device_workspace_bytes(int32_t n_images, int32_t n_res_blocks) {
+  if (n_images < 0 || n_res_blocks < 1) return 0;
+  const int64_t e = irec_rec::encode_workspace_bytes(n_images, n_res_blocks), d = irec_rec::decode_workspace_bytes(n_images, n_res_blocks);
+  return (size_t)((e > d ? e : d) + 256);
+}
+
+irec_status irec_rec_encode_files_device(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                         uint32_t channels, int32_t n_images, int32_t n_res_blocks, int32_t blocks_per_res, int32_t max_K,
+                                         const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride, uint8_t *out, int64_t cap,
+                                         int64_t *offsets, int32_t *status, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  using namespace irec;
+  if (!encode_args_ok(height, width, channels, n_images, n_res_blocks, blocks_per_res, max_K, K, k_stride, idx, idx_stride, out, cap, offsets, status))
+    return set_last_error(IREC_E_INVALID, "irec_rec_encode_files_device", "bad arguments");
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < irec_rec_device_workspace_bytes(n_images, n_res_blocks))
+    return set_last_error(IREC_E_WORKSPACE, "irec_rec_encode_files_device", "workspace too small (irec_rec_device_workspace_bytes) or not 8-byte aligned");
+  irec_rec::EncodeCall c{seed, block_size, max_index, height, width, channels, n_images, n_res_blocks, blocks_per_res, max_K,
+                         K, k_stride, idx, idx_stride, out, cap, offsets, status, nullptr, nullptr, nullptr};
+  irec_rec::encode_bind_workspace(c, workspace);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int64_t streams = 2 * (int64_t)n_images * n_res_blocks;
+  if (streams > 0) {
+    hipLaunchKernelGGL(rec_size_kernel, dim3(rec_grid(streams)), dim3(REC_NT), 0, st, c);
+    REC_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(rec_layout_kernel, dim3(1), dim3(REC_NT), 0, st, c);
+  REC_HIP(hipGetLastError());
+  if (streams > 0) {
+    hipLaunchKernelGGL(rec_write_kernel, dim3(rec_grid(streams + n_images)), dim3(REC_NT), 0, st, c);
+    REC_HIP(hipGetLastError());
+  }
+  return IREC_OK;
+}
+
+irec_status irec_rec_decode_files_device(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                         int32_t blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx, int32_t *status,
+                                         void *workspace, size_t workspace_bytes, void *hip_stream) {
+  using namespace irec;
+  if (!decode_args_ok(bytes, offsets, n_images, n_res_blocks, blocks_per_res, max_K, headers, K, idx, status))
+    return set_last_error(IREC_E_INVALID, "irec_rec_decode_files_device", "bad arguments");
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < irec_rec_device_workspace_bytes(n_images, n_res_blocks))
+    return set_last_error(IREC_E_WORKSPACE, "irec_rec_decode_files_device", "workspace too small (irec_rec_device_workspace_bytes) or not 8-byte aligned");
+  if (n_images == 0) return IREC_OK;
+  irec_rec::DecodeCall c{bytes, offsets, n_images, n_res_blocks, blocks_per_res, max_K, headers, K, idx, status, (int32_t *)workspace};
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int64_t lanes = (int64_t)n_images * n_res_blocks;
+  hipLaunchKernelGGL(rec_decode_counts_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c);
+  REC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(rec_decode_indices_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c);
+  REC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(rec_decode_status_kernel, dim3(n_images < 65536 ? n_images : 65536), dim3(REC_NT), 0, st, c);
+  REC_HIP(hipGetLastError());
+  return IREC_OK;
+}
+
+// ---- the same lane functions over host memory, in a plain loop (csrc/irec_internal.h) ------------------------------------------------
+irec_status irec_rec_test_core_encode_files(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                            uint32_t channels, int32_t n_images, int32_t n_res_blocks, int32_t blocks_per_res, int32_t max_K,
+                                            const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride, uint8_t *out, int64_t cap,
+                                            int64_t *offsets, int32_t *status) try {
+  using namespace irec;
+  if (!encode_args_ok(height, width, channels, n_images, n_res_blocks, blocks_per_res, max_K, K, k_stride, idx, idx_stride, out, cap, offsets, status))
+    return set_last_error(IREC_E_INVALID, "irec_rec_test_core_encode_files", "bad arguments");
+  std::vector<int64_t> ws((size_t)(irec_rec_device_workspace_bytes(n_images, n_res_blocks) / 8 + 1));
+  irec_rec::EncodeCall c{seed, block_size, max_index, height, width, channels, n_images, n_res_blocks, blocks_per_res, max_K,
+                         K, k_stride, idx, idx_stride, out, cap, offsets, status, nullptr, nullptr, nullptr};
+  irec_rec::encode_bind_workspace(c, ws.data());
+  irec_rec::encode_call_host(c);
+  return IREC_OK;
+} catch (const std::exception &e) { return irec::set_last_error(IREC_E_INVALID, "irec_rec_test_core_encode_files", e.what()); }
+
+irec_status irec_rec_test_core_decode_files(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                            int32_t blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
+                                            int32_t *status) try {
+  using namespace irec;
+  if (!decode_args_ok(bytes, offsets, n_images, n_res_blocks, blocks_per_res, max_K, headers, K, idx, status))
+    return set_last_error(IREC_E_INVALID, "irec_rec_test_core_decode_files", "bad arguments");
+  std::vector<int32_t> ws((size_t)(2 * (int64_t)n_images * n_res_blocks + 1));
+  irec_rec::DecodeCall c{bytes, offsets, n_images, n_res_blocks, blocks_per_res, max_K, headers, K, idx, status, ws.data()};
+  irec_rec::decode_call_host(c);
+  return IREC_OK;
+} catch (const std::exception &e) { return irec::set_last_error(IREC_E_INVALID, "irec_rec_test_core_decode_files", e.what()); }
+
+} // extern "C"

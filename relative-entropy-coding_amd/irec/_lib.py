@@ -146,6 +146,12 @@ SIGNATURES = {
     "irec_rec_decode_file": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64]),
     "irec_rec_encode_files": (_i64, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i32]),
     "irec_rec_decode_files": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32]),
+    "irec_rec_device_workspace_bytes": (ctypes.c_size_t, [_i32, _i32]),
+    "irec_rec_encode_files_device": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
+                                                    _vp, ctypes.c_size_t, _vp]),
+    "irec_rec_decode_files_device": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_rec_test_core_encode_files": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "irec_rec_test_core_decode_files": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "irec_device_uniform_int": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "irec_shim_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "irec_shim_cat_elu": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),

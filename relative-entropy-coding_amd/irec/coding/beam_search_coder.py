@@ -93,10 +93,8 @@ class PendingCode:
         return self._lists(both[:, 0], both[:, 1:])
 
     @staticmethod
-    def gather_packed(pendings):
-        """Indices of R calls on the SAME layout (the residual blocks of a batched model pass) as packed arrays, image-major:
-        K [N, R, bpt] int32, idx [N, R, bpt, max_K] int32 (numpy; rows are valid up to K) -- ONE gather on the device and ONE
-        device-to-host copy, no per-index Python object.  irec.io.encode_files takes them as they are."""
+    def _joined_packed(pendings):
+        """The rows of R calls on the SAME layout as ONE device tensor [N, R, bpt, 1 + width], image-major, K in column 0."""
         lay = pendings[0].lay
         same = all((p.lay.n_tensors, p.lay.n, p.lay.block_size, p.lay.n_blocks) == (lay.n_tensors, lay.n, lay.block_size, lay.n_blocks)
                    and (p.lay.block_size is None or p.lay.seed == lay.seed) for p in pendings)
@@ -111,8 +109,11 @@ class PendingCode:
             rows.append(r)
         n, bpt, R = lay.n_tensors, lay.blocks_per_tensor, len(pendings)
         sel = lay.packed_index(R)                                             # row of (image i, residual block r, block j)
-        both = torch.cat(rows, dim=0).index_select(0, sel).cpu().numpy().reshape(n, R, bpt, width + 1)
-        K, idx = both[..., 0], both[..., 1:]
+        return torch.cat(rows, dim=0).index_select(0, sel).reshape(n, R, bpt, width + 1)
+
+    @staticmethod
+    def _check_packed(pendings, K):
+        """The checks of every call of a pass on its share of the partition counts read back, K [N, R, bpt] (numpy)."""
         retry, split_failed = None, False
         for r, p in enumerate(pendings):
             try:
@@ -126,9 +127,29 @@ class PendingCode:
             PendingCode._all_gave_up(pendings)
         if retry is not None:
             raise retry
+
+    @staticmethod
+    def gather_packed(pendings):
+        """Indices of R calls on the SAME layout (the residual blocks of a batched model pass) as packed arrays, image-major:
+        K [N, R, bpt] int32, idx [N, R, bpt, max_K] int32 (numpy; rows are valid up to K) -- ONE gather on the device and ONE
+        device-to-host copy, no per-index Python object.  irec.io.encode_files takes them as they are."""
+        both = PendingCode._joined_packed(pendings).cpu().numpy()
+        K, idx = both[..., 0], both[..., 1:]
+        PendingCode._check_packed(pendings, K)
         if pendings[0].min_indices:
             K = np.maximum(K, pendings[0].min_indices)
         return np.ascontiguousarray(K), np.ascontiguousarray(idx)
+
+    @staticmethod
+    def gather_packed_device(pendings):
+        """gather_packed with the indices left on the device: the K [N, R, bpt] and idx [N, R, bpt, max_K] VIEWS of the one joined
+        tensor, which irec.io.encode_files_device takes as they are (strided).  Only K is read back, for the same checks
+        (SplitNotResident, MorePartitionsNeeded, the hints, min_indices)."""
+        both = PendingCode._joined_packed(pendings)
+        PendingCode._check_packed(pendings, both[..., 0].cpu().numpy())
+        if pendings[0].min_indices:
+            both[..., 0].clamp_(min=pendings[0].min_indices)
+        return both[..., 0], both[..., 1:]
 
     @staticmethod
     def _all_gave_up(pendings):

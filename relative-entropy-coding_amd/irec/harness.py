@@ -20,7 +20,7 @@ import torch
 
 from . import sharding
 from .coding import CodingError
-from .io import decode_files, encode_files, read_compressed_code, write_compressed_code
+from .io import decode_files, decode_files_device, encode_files, read_compressed_code, write_compressed_code
 
 
 def _host_leg(chunk_shape, names, seed, block_size, out_dir, S, K, idx, t_compress):
@@ -50,17 +50,60 @@ def _host_leg(chunk_shape, names, seed, block_size, out_dir, S, K, idx, t_compre
             for i in range(n)]
 
 
-def compress_images(model, images, names, seed, block_size, out_dir, batch=None, packed=True):
+def _device_leg(model, chunk, names, seed, block_size, out_dir, S):
+    """_host_leg with the files built and checked on the device: the batch's files come from model.compress_rec (the arithmetic coder
+    runs on the device), are written, read back, decoded on the device (irec_rec_decode_files_device) and compared there with the
+    indices that compress_rec's coders left.  The rows carry the same keys."""
+    n, _, h, w = chunk.shape
+    t0 = time.perf_counter()
+    (blob, off, _), pendings = model.compress_rec(chunk, seed=seed, update_sampler=False, block_size=block_size, return_pendings=True)
+    t_compress = time.perf_counter() - t0
+    t1 = time.perf_counter()
+    K, idx = pendings                                             # views of the joined device tensor the files were built from
+    host, off_host = blob.cpu().numpy(), off.cpu().numpy()
+    paths = [os.path.join(out_dir, f"{nm}.rec") for nm in names]
+    mv = memoryview(host)
+    for i, path in enumerate(paths):
+        with open(path, "wb") as fh:
+            fh.write(mv[off_host[i]:off_host[i + 1]])
+    back = [open(path, "rb").read() for path in paths]
+    sizes = np.array([len(b) for b in back], dtype=np.int64)
+    off2 = np.concatenate([[0], np.cumsum(sizes)])
+    blob2 = torch.from_numpy(np.frombuffer(b"".join(back), dtype=np.uint8).copy()).to(blob.device)
+    hdr, K2, idx2 = decode_files_device(blob2, off2, K.shape[1], K.shape[2], idx.shape[3])
+    live = torch.arange(idx.shape[3], device=idx.device)[None, None, None, :] < K[..., None]
+    want = torch.tensor([seed, block_size, h, w, 3], dtype=torch.int64, device=hdr.device)
+    same = ((K2 == K).all(dim=2).all(dim=1) & ((idx2 == idx) | ~live).all(dim=3).all(dim=2).all(dim=1) &
+            (hdr[:, [0, 1, 3, 4, 5]] == want).all(dim=1)).cpu().numpy()
+    n_idx = K.sum(dim=(1, 2)).cpu().numpy()
+    t_host = (time.perf_counter() - t1) / n
+    return [{"name": names[i], "comp_codelength": int(sizes[i]) * 8, "comp_lossy_bpp": int(sizes[i]) * 8 / (h * w),
+             "comp_code_bpd": int(sizes[i]) * 8 / (h * w * 3), "code_nats": int(n_idx[i]) * float(np.log(S)),
+             "n_indices": int(n_idx[i]), "indices_recovered": bool(same[i]), "comp_time": t_compress / n + t_host}
+            for i in range(n)]
+
+
+def compress_images(model, images, names, seed, block_size, out_dir, batch=None, packed=True, rec_on_device=False):
     """images: [n, 3, H, W] in [-0.5, 0.5] on the model's device.  Returns one dict per image (reference CSV columns where
     they apply: comp_codelength, comp_lossy_bpp, comp_time) plus `indices_recovered`, `code_nats`.
     packed (default): the indices stay packed arrays from the device to the files (model.compress_packed, irec.io.encode_files
     / decode_files), and the host leg of a batch runs on a worker thread while the device codes the next batch; packed=False is
-    the per-image form with the reference's write_compressed_code / read_compressed_code on nested lists."""
+    the per-image form with the reference's write_compressed_code / read_compressed_code on nested lists.
+    rec_on_device: a batch's files are built on the device (model.compress_rec) and the read-back check runs there
+    (irec.io.decode_files_device); same rows, byte-identical files.  The default stays the host leg."""
     os.makedirs(out_dir, exist_ok=True)
     n = images.shape[0]
     batch = n if not batch else int(batch)
     S = model.residual_blocks[0].coder.n_samples
     rows = []
+    if rec_on_device:
+        for lo in range(0, n, batch):
+            chunk = images[lo:lo + batch]
+            try:
+                rows += _device_leg(model, chunk, names[lo:lo + chunk.shape[0]], seed, block_size, out_dir, S)
+            except CodingError as e:                     # compression_performance.py:375-377: log and move on
+                rows += [{"name": names[lo + i], "error": str(e)} for i in range(chunk.shape[0])]
+        return rows
     if packed and hasattr(model, "compress_packed"):
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=1) as pool:

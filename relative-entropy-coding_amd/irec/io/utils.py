@@ -184,6 +184,142 @@ def decode_files(blob, offsets, n_res_blocks, blocks_per_res, max_K, n_threads=0
     return hdr, K, idx[..., :max_K]
 
 
+# ---- the same two calls on the device (csrc/irec_rec.hip: one lane per stream over csrc/irec_rec_core.h) -----------------------------
+# irec_rec_status of include/irec.h -> the text the host coder gives for that cause
+_REC_STATUS_TEXT = {
+    1: "irec_rec_encode_files: K out of range",
+    2: "irec_rec_encode_file: an index does not fit max_index (or max_index exceeds what the 32-bit coder's range holds, ~1.07 million)",
+    3: "irec_rec_encode_file: an index does not fit max_index (or max_index exceeds what the 32-bit coder's range holds, ~1.07 million)",
+    4: "irec_rec_decode_file: truncated header",
+    5: "irec_rec_decode_file: file uses empirical count tables (not the default models)",
+    6: "irec_rec_decode_file: max_index out of range (damaged header?)",
+    7: "irec_rec_decode_file: partition / block counts out of range (damaged header?)",
+    8: "irec_rec_decode_file: truncated streams",
+    9: "irec_rec_decode_file: corrupt count stream", 10: "irec_rec_decode_file: corrupt count stream",
+    11: "irec_rec_decode_file: corrupt count stream",
+    12: "irec_rec_decode_file: corrupt index stream", 13: "irec_rec_decode_file: corrupt index stream",
+    14: "irec_rec_decode_file: corrupt index stream", 15: "irec_rec_decode_file: corrupt index stream",
+    16: "irec_rec_decode_file: streams do not match the header",
+    17: "irec_rec_decode_files: block structure differs",
+    18: "irec_rec_decode_files: more partitions than max_K",
+}
+
+
+def _raise_first_status(status):
+    """ValueError with the host's text and its "(image i)" suffix for the first image whose status is nonzero."""
+    bad = np.flatnonzero(status)
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"{_REC_STATUS_TEXT.get(int(status[i]), 'irec_rec: status %d' % int(status[i]))} (image {i})")
+
+
+def _block_strides(K, idx):
+    """(K, k_stride, idx, idx_stride) of include/irec.h: block b = (i R + r) bpt + j at K[b k_stride], idx[b idx_stride + t].  Views of
+    the packed arrays and of one joined [rows][1 + width] tensor pass as they are; anything else is made contiguous."""
+    n, r, bpt = K.shape
+    max_K = idx.shape[3]
+    ks = K.stride(2) if K.numel() else 1
+    if K.numel() and (ks < 1 or K.stride() != (r * bpt * ks, bpt * ks, ks)):
+        K, ks = K.contiguous(), 1
+    ist = idx.stride(2) if idx.numel() else max(max_K, 1)
+    if idx.numel() and (ist < max_K or idx.stride(3) != 1 or idx.stride()[:2] != (r * bpt * ist, bpt * ist)):
+        idx, ist = idx.contiguous(), max_K
+    return K, int(ks), idx, int(ist)
+
+
+def _encode_files_device_launch(seed, image_shape, block_size, K, idx, max_index, out):
+    """One irec_rec_encode_files_device call on the current stream, nothing read back: (offsets int64 [N + 1], status int32 [N], both views
+    of `both`, which one copy fetches).  The bytes are in `out` only if offsets[N] <= out.numel()."""
+    import torch
+    lib = _lib.load()
+    n, r, bpt = K.shape
+    max_K = idx.shape[3]
+    h, w, c = (int(v) for v in image_shape)
+    K, ks, idx, ist = _block_strides(K, idx)
+    dev = K.device
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.irec_rec_device_workspace_bytes(n, r), dtype=torch.uint8, device=dev)
+        both = torch.empty(n + 1 + (n + 1) // 2, dtype=torch.int64, device=dev)          # offsets, then status: one read-back
+        offsets, status = both[:n + 1], both[n + 1:].view(torch.int32)[:n]
+        st = lib.irec_rec_encode_files_device(int(seed), int(block_size), int(max_index), h, w, c, n, r, bpt, max_K, K.data_ptr(), ks,
+                                              idx.data_ptr() if idx.numel() else None, ist, out.data_ptr() if out.numel() else None,
+                                              out.numel(), offsets.data_ptr(), status.data_ptr() if n else None, ws.data_ptr(), ws.numel(),
+                                              torch.cuda.current_stream().cuda_stream)
+    if st == _lib.IREC_E_INVALID:
+        raise ValueError(lib.irec_last_error().decode())
+    _lib.check(st, "irec_rec_encode_files_device")
+    return offsets, status, both
+
+
+def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=None):
+    """encode_files on the device (irec_rec_encode_files_device): K [N, R, bpt], idx [N, R, bpt, max_K] int32 CUDA tensors, contiguous
+    or views of one joined [rows][1 + width] tensor (PendingCode.gather_packed_device).  Returns (blob uint8, offsets int64 [N + 1]) as
+    CUDA tensors, byte for byte what encode_files gives; the only host synchronisation is ONE read-back of offsets and status.
+    out: a CUDA uint8 buffer to write into (a short one costs a second run at the size the first one reports)."""
+    import torch
+    if not (K.is_cuda and idx.is_cuda and K.dtype == torch.int32 and idx.dtype == torch.int32):
+        raise ValueError("encode_files_device takes CUDA int32 tensors")
+    if K.dim() != 3 or idx.dim() != 4 or tuple(idx.shape[:3]) != tuple(K.shape):
+        raise ValueError(f"encode_files_device: K {tuple(K.shape)} and idx {tuple(idx.shape)} are not [N, R, bpt] and [N, R, bpt, max_K]")
+    n, r, bpt = K.shape
+    max_K = idx.shape[3]
+    if out is None:
+        # irec_io.cpp's own first allowance: 64 + 40 bits per symbol and terminator, per stream
+        cap = n * (28 + 16 * r + r * ((64 + 40 * (bpt + 1)) // 8 + 1 + (64 + 40 * (bpt * max_K + 1)) // 8 + 1))
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=K.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == K.device):
+        raise ValueError("encode_files_device: out must be a contiguous CUDA uint8 tensor on the indices' device")
+    for _attempt in range(2):
+        offsets, _, both = _encode_files_device_launch(seed, image_shape, block_size, K, idx, max_index, out)
+        host = both.cpu().numpy()
+        _raise_first_status(host[n + 1:].view(np.int32)[:n])
+        total = int(host[n])
+        if total <= out.numel():
+            return out[:total], offsets
+        out = torch.empty(total, dtype=torch.uint8, device=K.device)                       # exactly what the first run asked for
+    raise ValueError("irec_rec_encode_files_device: the files did not fit the size the call itself reported")
+
+
+def _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K):
+    """One irec_rec_decode_files_device call on the current stream: (headers int32 [N, 9] holding the uint32 words, K, idx, status int32 [N])
+    on the device, nothing read back but `offsets` (checked against the blob before any kernel sees them)."""
+    import torch
+    lib = _lib.load()
+    if not (blob.is_cuda and blob.dtype == torch.uint8):
+        raise ValueError("decode_files_device takes a CUDA uint8 tensor")
+    blob = blob.contiguous()
+    dev = blob.device
+    off_host = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
+    n = off_host.size - 1
+    # the kernels read no byte outside [offsets[i], offsets[i + 1]): those ranges must lie inside the blob
+    if n < 0 or off_host[0] < 0 or (np.diff(off_host) < 0).any() or off_host[-1] > blob.numel():
+        raise ValueError("decode_files_device: offsets must be non-decreasing and end inside the blob")
+    r, bpt, max_K = int(n_res_blocks), int(blocks_per_res), int(max_K)
+    with torch.cuda.device(dev):
+        offsets = torch.from_numpy(off_host.copy()).to(dev)                    # (a copy: the caller's array may be read-only)
+        ws = torch.empty(lib.irec_rec_device_workspace_bytes(n, r), dtype=torch.uint8, device=dev)
+        hdr = torch.zeros((n, 9), dtype=torch.int32, device=dev)
+        K = torch.empty((n, r, bpt), dtype=torch.int32, device=dev)
+        idx = torch.empty((n, r, bpt, max_K), dtype=torch.int32, device=dev)
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        st = lib.irec_rec_decode_files_device(blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, r, bpt, max_K,
+                                              hdr.data_ptr(), K.data_ptr(), idx.data_ptr() if idx.numel() else None, status.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    if st == _lib.IREC_E_INVALID:
+        raise ValueError(lib.irec_last_error().decode())
+    _lib.check(st, "irec_rec_decode_files_device")
+    return hdr, K, idx, status[:n]
+
+
+def decode_files_device(blob, offsets, n_res_blocks, blocks_per_res, max_K):
+    """decode_files on the device (irec_rec_decode_files_device): blob uint8 CUDA tensor, offsets [N + 1] (CUDA, CPU or numpy).
+    Returns CUDA tensors (headers [N, 9] int64 -- seed, block_size, max_index, height, width, channels, two flags, R --,
+    K [N, R, bpt] int32, idx [N, R, bpt, max_K] int32 with rows zero-filled past K); ValueError naming the first damaged file."""
+    import torch
+    hdr, K, idx, status = _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K)
+    _raise_first_status(status.cpu().numpy())
+    return hdr.to(torch.int64) & 0xFFFFFFFF, K, idx
+
 def write_compressed_code(file_path, seed, image_shape, block_size, block_indices, max_index,
                           num_aux_var_counts_file=None, index_counts_file=None):
     """Same signature as rec/io/utils.py:7.  block_indices[r][k] = sample indices of coded block k of residual block r.

@@ -394,6 +394,27 @@ class BidirectionalResNetVAE(nn.Module):
                 continue
         raise MorePartitionsNeeded(max(b.coder._max_K_hint for b in self.residual_blocks) + 1)
 
+    @torch.no_grad()
+    def compress_rec(self, image, seed, update_sampler=False, block_size=None, return_pendings=False):
+        """`compress_packed` with the indices never leaving the device: (blob uint8, offsets int64 [N + 1], reconstruction), CUDA tensors
+        -- image i's .rec file is blob[offsets[i]:offsets[i + 1]], byte for byte what irec.io.encode_files makes of compress_packed's
+        arrays (irec.io.encode_files_device: the arithmetic coder runs on the device, one lane per stream).  Only the partition counts
+        and the files' offsets are read back.  block_size: the header's block-size word (default: the coders' own).
+        return_pendings: also the device K / idx views the files were built from, ((blob, offsets, reconstruction), (K, idx))."""
+        from ..io import encode_files_device
+        _, _, height, width = image.shape
+        for _attempt in range(6):
+            pendings, reconstruction = self._compress_device(image, seed, update_sampler)
+            try:
+                K, idx = PendingCode.gather_packed_device(pendings)
+            except (MorePartitionsNeeded, SplitNotResident):
+                continue
+            coder = self.residual_blocks[0].coder
+            blob, offsets = encode_files_device(seed, (height, width, 3), coder.block_size if block_size is None else block_size, K, idx,
+                                                max_index=coder.n_samples)
+            return ((blob, offsets, reconstruction), (K, idx)) if return_pendings else (blob, offsets, reconstruction)
+        raise MorePartitionsNeeded(max(b.coder._max_K_hint for b in self.residual_blocks) + 1)
+
     def _compress_device(self, image, seed, update_sampler=False):
         """Everything of `compress` that runs on the device, with no host synchronisation: (PendingCode per residual
         block, reconstruction).  Capturable in a HIP graph (GraphedCompress)."""
