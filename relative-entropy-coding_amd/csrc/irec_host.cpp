@@ -601,7 +601,7 @@ Plan make_plan(int n_cu, const irec_params *p, int32_t max_dim, int32_t max_K) {
   }
   if (!pl.table) pl.team_only = false;
   // Blocks of more than 1024 dims -- Coder.__init__ takes any block_size, None (the whole tensor as one block) included,
-  // coder.py:29-36,415-419 -- are walked in chunks of 1024 by encode_chunk_kernel (irec_team.hip); its second pass and
+  // coder.py:29-36,415-419 -- are walked in chunks of 1024 by encode_chunk_kernel (irec_chunk.h); its second pass and
   // everything it does not serve (B > 20, more samples than one pass holds, no dim hints) is the generic kernel's.
   pl.chunk = !pl.fast && !pl.team_only && !(p->flags & (IREC_FLAG_FORCE_GENERIC | IREC_FLAG_FUSED_PHILOX | IREC_FLAG_ONE_TABLE)) &&
              p->table_dims[0] > 0 && irec::chunk_applies(B, S, max_dim);
@@ -682,7 +682,7 @@ static int chunk_grid(int n_cu, const Plan &pl, const irec_params *p, int64_t n_
   const int teams = std::max(1, irec::chunk_teams(p->n_beams, p->n_samples));
   return batch_grid(n_blocks, std::min(n_cu, std::max(1, pl.grid_cap / teams)));
 }
-// Gangs of the chunked encoder (irec_team.hip, "Gangs"): a call of fewer blocks than team slots -- block_size = None on one image's
+// Gangs of the chunked encoder (irec_chunk.h, "Gangs"): a call of fewer blocks than team slots -- block_size = None on one image's
 // latents -- has G teams code each block together, a chunk of 1024 dims (or several) per member.  All n_blocks * G teams must be resident
 // at once (one static hand-out slot each; they wait for each other twice per step).  Returns G (0: every block on one team) and the
 // grid that puts the members on CUs of their own as far as the CUs go.

@@ -56,7 +56,7 @@ struct EncArgs {
   // head of the workspace (nullptr: no table books, e.g. irec_block_kl): every encode kernel's first workgroup commits the table
   // stamps the call's preparation kernel left pending (commit_table_stamps, irec_fast_common.h)
   uint32_t *ws_head;
-  // Gangs of the chunked encoder (irec_team.hip, round 5): calls of so few blocks of more than 1024 dims that most CUs would idle --
+  // Gangs of the chunked encoder (irec_chunk.h, round 5): calls of so few blocks of more than 1024 dims that most CUs would idle --
   // block_size = None on one image's latents.  coop_W teams code a block together, each the chunks c = member (mod coop_W) of it; per step
   // they hand the group sums of their chunks over through gang_xch (gang_stride bytes per block: gang_xch_bytes) behind an arrival
   // counter (first word of the block's granules in coop_xch), and every canonical sum is formed from all of its group sums in group order.
@@ -128,13 +128,13 @@ bool ten_applies(int B, int S);
 size_t ten_lds_for(int teams);
 hipError_t launch_encode_ten(const EncArgs &A, int teams, int grid, hipStream_t st);
 int team_ten_teams(int B, int S, int shape_override);   // teams per workgroup of encode_ten_kernel when a plain call of this shape takes it, else 0
-// blocks of more than 1024 dims: a team walks the block in chunks of 1024 over the team encoder's tables (irec_team.hip, encode_chunk_kernel)
+// blocks of more than 1024 dims: a team walks the block in chunks of 1024 over the team encoder's tables (irec_chunk.h, encode_chunk_kernel)
 bool chunk_applies(int B, int S, int max_dim);          // B <= 60, max_dim > 1024, a step's partials and running scores fit the LDS next to the tables
 int chunk_teams(int B, int S);                           // teams (= scratch slabs) per workgroup of the build that serves the call: 2, 1, or 0 = none
 size_t chunk_lds_for(int B, int S);
 size_t chunk_ws_for(int B, int dpad, int max_K);         // scratch slab of one team
 const char *chunk_kernel_name(int B, int S);
-// gang builds of the chunked encoder (irec_team_gang.hip): teams per workgroup (0 = none), beam slots, LDS, name
+// gang builds of the chunked encoder (irec_chunk_gang.hip): teams per workgroup (0 = none), beam slots, LDS, name
 int chunk_gang_teams(int B, int S);
 int chunk_gang_nb(int B, int S);
 size_t chunk_gang_lds_for(int B, int S);

@@ -1,5 +1,5 @@
 """Diagnostic: latency of calls of FEW blocks of more than 1024 dims -- the reference's default block_size=None on one image's latents --
-coded by gangs of teams (irec_team.hip, "Gangs") against every block on one team (IREC_FLAG_NO_SPLIT).
+coded by gangs of teams (irec_chunk.h, "Gangs") against every block on one team (IREC_FLAG_NO_SPLIT).
 Usage: python scripts/gang_latency.py [--huge] [--stripes] | python scripts/with_lib.py gang_ablN scripts/gang_latency.py --ablate   (--huge: also ONE block of 301 056 dims, Kodak level 1 whole: ~2 200 partitions)"""
 import os, sys, time
 import numpy as np, torch

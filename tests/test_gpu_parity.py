@@ -406,7 +406,7 @@ def test_blocks_of_any_size_stay_off_the_generic_kernel(engine, oracle):
                                               (5000, None, 30, 1.34, 1)])
 def test_gangs_of_teams_code_the_blocks_of_a_small_call(engine, oracle, n, bs, B, eps1, n_t):
     """Round 5: the reference's default `block_size=None` on ONE image's latents is one block of 8192 dims -- on one team of one CU
-    40 ms, 255 CUs idle.  A call of fewer blocks than team slots is coded by GANGS (irec_team.hip): G teams per block, a chunk of 1024
+    40 ms, 255 CUs idle.  A call of fewer blocks than team slots is coded by GANGS (irec_chunk.h): G teams per block, a chunk of 1024
     dims (or several) each, group sums exchanged through HBM and added in group order.  Same bits as the one-team form (NO_SPLIT) and as
     the oracle; ragged blocks (two table dims), beam passes (B = 30), sample stripes (one block: 8 chunk owners x 9 stripes).
     Gang builds: three teams per workgroup for B <= 30 where the LDS holds them, else one team (B = 32 ... 60, S = 122, B = 30 at S = 56)."""
