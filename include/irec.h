@@ -487,6 +487,25 @@ irec_status irec_rec_decode_files_device(const uint8_t *bytes, const int64_t *of
                                          int32_t blocks_per_res, int32_t max_K, uint32_t *headers /*[n][9]*/, int32_t *K, int32_t *idx,
                                          int32_t *status, void *workspace, size_t workspace_bytes, void *hip_stream);
 
+/* The verdict on the rows a decode call is about to read, on the device (csrc/irec_rows.hip over csrc/irec_rows_core.h).  The decode
+ * entry points above answer a row they cannot decode with p_loc, silently; a caller whose rows never leave the device (the output of
+ * irec_rec_decode_files_device) gets the cause here, per image, without a copy to the host.
+ * A group is one image's blocks in one residual block: blocks j < blocks_per_group, block j at row b = block_row[g * blocks_per_group + j]
+ * (device int32; NULL: g * blocks_per_group + j), its count at K[b * k_stride], its indices at idx[b * idx_stride + t] -- the stride
+ * conventions of irec_rec_encode_files_device: the packed arrays or one joined [rows][1 + width] tensor pass unchanged.
+ * status[g] becomes the first cause of the group's LOWEST failing block:
+ *   K < min_K or K > max_K: IREC_ROWS_E_K_RANGE (min_K: 0 for the beam-search coder, 1 for the sequential one);
+ *   K > k_limit: IREC_ROWS_E_RATIO_TABLE (k_limit: the length of the fitted ratio table, INT32_MAX with extrapolated ratios);
+ *   an index outside [0, n_samples) among the first K: IREC_ROWS_E_INDEX_RANGE.
+ * A nonzero status[g] already present is kept: the launches of successive residual blocks on one stream accumulate the first cause per
+ * image (one workgroup per group, one lane reads and writes status[g]; no atomics).  No read goes past idx[b * idx_stride + max_K - 1],
+ * whatever K holds.  Asynchronous on hip_stream: no allocation, no synchronisation. */
+typedef enum { IREC_ROWS_OK = 0, IREC_ROWS_E_K_RANGE = 1, IREC_ROWS_E_INDEX_RANGE = 2, IREC_ROWS_E_RATIO_TABLE = 3 } irec_rows_status;
+irec_status irec_decode_rows_status(int64_t n_groups, int32_t blocks_per_group, const int32_t *block_row /* NULL: g * bpg + j */,
+                                    const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride, int32_t max_K,
+                                    int32_t min_K, int32_t k_limit, int32_t n_samples, int32_t *status /* [n_groups] */,
+                                    void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,10 @@ irec_status irec_rec_test_core_encode_files(uint32_t seed, uint32_t block_size, 
 irec_status irec_rec_test_core_decode_files(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
                                             int32_t blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
                                             int32_t *status);
+/* irec_decode_rows_status (csrc/irec_rows_core.h) over HOST memory: the same lane function, group after group in a plain loop. */
+irec_status irec_test_rows_status_host(int64_t n_groups, int32_t blocks_per_group, const int32_t *block_row, const int32_t *K,
+                                       int64_t k_stride, const int32_t *idx, int64_t idx_stride, int32_t max_K, int32_t min_K,
+                                       int32_t k_limit, int32_t n_samples, int32_t *status);
 
 /* ---- hand-offs of the RVAE model shim (device pointers, asynchronous; rec/models/resnet_vae.py:372-497) -------------------------
  * What lies between the convolutions of BidirectionalResidualBlock.call on the compression path, one launch each instead of

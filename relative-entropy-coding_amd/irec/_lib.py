@@ -31,6 +31,9 @@ IREC_NORMAL_TABLE_PAD = 16
 BIG_PRIME = 10007
 MAX_BEAMS = 256
 MAX_PARTITIONS = 65536
+IREC_ROWS_OK, IREC_ROWS_E_K_RANGE, IREC_ROWS_E_INDEX_RANGE, IREC_ROWS_E_RATIO_TABLE = 0, 1, 2, 3   # irec_rows_status
+IREC_REC_E_MAX_K = 18            # irec_rec_status: a block with more partitions than max_K
+INT32_MAX = 2 ** 31 - 1
 
 
 class IrecParams(ctypes.Structure):
@@ -152,6 +155,8 @@ SIGNATURES = {
     "irec_rec_decode_files_device": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "irec_rec_test_core_encode_files": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "irec_rec_test_core_decode_files": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "irec_decode_rows_status": (ctypes.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "irec_test_rows_status_host": (ctypes.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "irec_device_uniform_int": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
     "irec_shim_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "irec_shim_cat_elu": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),

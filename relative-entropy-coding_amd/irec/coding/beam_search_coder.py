@@ -4,6 +4,7 @@ the arithmetic runs in the gfx950 kernels behind include/irec.h (no CPU path).
 Distributions are duck-typed exactly as in the reference (only `.loc` and `.scale` are read, coder.py:427-430),
 e.g. torch.distributions.Normal with CPU or cuda (HIP) float32 tensors.
 """
+import ctypes
 import gc
 
 import numpy as np
@@ -379,6 +380,34 @@ class BeamSearchCoder(GaussianCoder):
                                    torch.from_numpy(idx).to(eng.device))
         return sample.reshape(src.shape).to(src.device)
 
+    MIN_INDICES = 0     # a zero-KL block of the beam-search coder emits no index
+
+    def decode_tensors_device(self, p_loc, p_scale, K, idx, seed, block_size, rows=None, status=None):
+        """decode_tensors for rows that are on the device already (GaussianCoder.decode_tensors_device has the arguments): the row
+        check into `status`, then the decode, with no host copy, no synchronisation and no Python loop over blocks.  Tensors that fit
+        the LDS take irec_beam_decode_tensors with `rows` as its block_row, so packed arrays are read where they lie (a strided view
+        is copied once: that entry point takes contiguous rows); otherwise the rows are gathered into layout order and decoded
+        block-wise (irec_beam_decode_ws)."""
+        src = torch.as_tensor(p_loc)
+        if src.ndim < 2 or src.shape[0] < 1 or src[0].numel() < 1:
+            raise CodingError(f"nothing to decode: coding distribution of shape {tuple(src.shape)} (need [batch >= 1, dims >= 1 ...])")
+        eng = self._engine_for(src)
+        params = self._params()
+        pl, ps = (self._dev(t, eng.device) for t in (p_loc, p_scale))
+        lay = eng.layout(src.shape[0], src[0].numel(), block_size, seed)
+        Kf, ks, If, ist = self._flat_rows(K, idx)
+        self.last_rows_status = self._rows_check(eng, lay, Kf, ks, If, ist, rows, status, self.n_samples)
+        bs_eff = lay.n if lay.block_size is None else int(lay.block_size)
+        if eng.lib.irec_decode_tensors_supported(ctypes.byref(params), lay.n, bs_eff):
+            if ks != 1 or ist != If.shape[1]:
+                Kf, If = Kf.contiguous(), If.contiguous()
+            block_row = rows if rows is not None else lay.identity_rows_dev()
+            sample = eng.decode_blocks(params, lay, pl, ps, seed, Kf, If, mode="tensors", block_row=block_row)
+        else:
+            K_lay, idx_lay = self._rows_in_layout_order(lay, Kf, If, rows)
+            sample = eng.decode_blocks(params, lay, pl, ps, seed, K_lay, idx_lay, mode="tables")
+        return sample.reshape(src.shape).to(src.device)
+
     # ---- reference API -----------------------------------------------------------------------------------------------
     def encode_block(self, target_dist, coding_dist, seed, update_sampler=False, numpy=True):
         """beam_search_coder.py:53-122.  Returns (list of K indices, sample with the shape of loc)."""
@@ -423,8 +452,13 @@ class BeamSearchCoder(GaussianCoder):
         return (idx if batched else idx[0]), sample
 
     def decode(self, coding_dist, indices, seed, **kwargs):
-        """GaussianCoder.decode, coder.py:459-491."""
+        """GaussianCoder.decode, coder.py:459-491.  Extension: `packed=(K, idx, rows)` (and `status=`) -- rows on the device,
+        decode_tensors_device; `indices` is then ignored."""
         batched = kwargs.pop("batched", False)
+        packed, status = kwargs.pop("packed", None), kwargs.pop("status", None)
+        if packed is not None:       # (K, idx, rows) on the device: decode_tensors_device, nothing crosses to the host
+            return self.decode_tensors_device(coding_dist.loc, coding_dist.scale, packed[0], packed[1], seed, self.block_size,
+                                              rows=packed[2], status=status)
         if self.block_size is None and not batched:
             return self.decode_block(coding_dist, indices, seed)
         per_tensor = indices if batched else [indices]

@@ -17,6 +17,11 @@ from .. import _lib
 from ..engine import Engine, FitError, NormalTableTooLarge, fit_aux_ratios_host, get_engine, tf_shuffle_perm
 
 AUX_RATIO_POWER_LAW = -0.7864636765648174  # coder.py:16
+# coder.py:226-230: a partition count beyond the fitted ratio table (table length, count asked for)
+RATIO_TABLE_TEXT = ("KL divergence higher than auxiliary variables can account for. "
+                    "Update auxiliary variable ratios with high-enough KL divergence."
+                    "Maximum possible number of partitions is {}."
+                    "Requested {}")
 
 
 def _det_log(x):
@@ -207,10 +212,7 @@ class GaussianCoder(Coder):
                               "update_auxiliary_variance_ratios() first"
                               " or use extrapolation")
         if index >= self.aux_variable_variance_ratios.shape[0]:
-            raise CodingError("KL divergence higher than auxiliary variables can account for. "
-                              "Update auxiliary variable ratios with high-enough KL divergence."
-                              "Maximum possible number of partitions is {}."
-                              "Requested {}".format(self.aux_variable_variance_ratios.shape[0], index + 1))
+            raise CodingError(RATIO_TABLE_TEXT.format(self.aux_variable_variance_ratios.shape[0], index + 1))
         return self.aux_variable_variance_ratios[index]
 
     def update_auxiliary_variance_ratios(self, target_dist, coding_dist, seed=42, relative_tolerance=1e-4, max_iters=10000,
@@ -377,6 +379,71 @@ class GaussianCoder(Coder):
                                       max(self.table_window(), max_K))
         return sample.reshape(src.shape).to(src.device)
 
+    # ---- rows that never leave the device (the output of irec.io.decode_files_device, PendingCode.gather_packed_device) ----------
+    MIN_INDICES = 1     # indices a decodable row holds at least (the sequential coder's zero-KL block emits one, coder.py:548-557)
+
+    @staticmethod
+    def _flat_rows(K, idx):
+        """(K [rows], k_stride, idx [rows, max_K], idx_stride): K of any shape and idx of that shape + (max_K,) as flat rows, WITHOUT a
+        copy where the strides allow it -- the packed arrays (1, max_K) and the views of one joined [rows][1 + width] tensor
+        (1 + width twice) do; anything else is made contiguous."""
+        if not (K.is_cuda and idx.is_cuda and K.dtype == torch.int32 and idx.dtype == torch.int32):
+            raise CodingError("decode_tensors_device takes CUDA int32 tensors K and idx")
+        if tuple(idx.shape[:-1]) != tuple(K.shape) or idx.dim() != K.dim() + 1:
+            raise CodingError(f"K {tuple(K.shape)} and idx {tuple(idx.shape)} are not [...] and [..., max_K]")
+        max_K = idx.shape[-1]
+        if max_K < 1:
+            raise CodingError("idx holds no index slot (max_K = 0): rows on the device need at least one slot each")
+        Kf, If = K.reshape(-1), idx.reshape(-1, max_K)      # (views where the strides merge, contiguous copies otherwise)
+        ks = Kf.stride(0) if Kf.numel() > 1 else 1
+        ist = If.stride(0) if If.shape[0] > 1 else max(max_K, 1)
+        if ks < 1:
+            Kf, ks = Kf.contiguous(), 1
+        if If.stride(1) != 1 or ist < max_K:
+            If, ist = If.contiguous(), max_K
+        return Kf, int(ks), If, int(ist)
+
+    def _rows_check(self, eng, lay, Kf, ks, If, ist, rows, status, n_samples):
+        """Launch the row check of one call (a group = a tensor's blocks) into `status`; returns status."""
+        if status is None:
+            status = torch.zeros(lay.n_tensors, dtype=torch.int32, device=eng.device)
+        k_limit = _lib.INT32_MAX if self.extrapolate_auxiliary_ratios else int(self.aux_variable_variance_ratios.shape[0])
+        return eng.rows_status(Kf, ks, If, ist, If.shape[1], lay.n_tensors, lay.blocks_per_tensor, rows, self.MIN_INDICES, k_limit,
+                               n_samples, status)
+
+    @staticmethod
+    def _rows_in_layout_order(lay, Kf, If, rows):
+        """The rows of a call gathered into `lay` order: one index_select each for the counts and the index rows (both take strided
+        views), contiguous results.  rows: int32 [n_tensors * bpt] -> row of Kf / If, or None for i * bpt + j."""
+        sel = lay.natural_inverse_dev()
+        if rows is not None:
+            sel = rows.to(torch.int64).index_select(0, sel)
+        return Kf.index_select(0, sel), If.index_select(0, sel)
+
+    def decode_tensors_device(self, p_loc, p_scale, K, idx, seed, block_size, rows=None, status=None):
+        """decode_tensors for rows that are on the device already: K [...] and idx [..., max_K] CUDA int32 (contiguous, or the views of
+        one joined [rows][1 + width] tensor), `rows` (int32 CUDA [n_tensors * bpt], None: i * bpt + j) the row of block j of tensor i.
+        Launches the row check (irec_decode_rows_status) into `status` (int32 CUDA [n_tensors]; a nonzero entry is kept, so the calls of
+        a pass accumulate the first cause per image) and then the decode -- no host copy, no synchronisation, no Python loop over
+        blocks.  A row the check refuses decodes to p_loc, as the kernels promise; the verdict is the caller's to read.  status=None:
+        a fresh one, left in `last_rows_status` (device).  Needs the device path (`_on_device`)."""
+        self._check_sampler()
+        if not self._on_device(p_loc, block_size):
+            raise CodingError("decode_tensors_device needs the device path: an ImportanceSampler with alpha = inf, tensors on the GPU, "
+                              "and proposal tables that fit (IREC_TABLE_BYTES_HARD, IREC_TABLE_STEPS_MAX)")
+        src = torch.as_tensor(p_loc)
+        eng = self._engine_for(src)
+        pl, ps = (self._dev(t, eng.device) for t in (p_loc, p_scale))
+        lay = eng.layout(src.shape[0], src[0].numel(), block_size, seed)
+        Kf, ks, If, ist = self._flat_rows(K, idx)
+        max_K = If.shape[1]
+        S = self.sampler.n_samples()
+        self.last_rows_status = self._rows_check(eng, lay, Kf, ks, If, ist, rows, status, S)
+        K_lay, idx_lay = self._rows_in_layout_order(lay, Kf, If, rows)
+        self.last_path = "device"
+        sample = eng.gc_decode_blocks(lay, pl, ps, seed, S, K_lay, idx_lay, max(self.table_window(), max_K))
+        return sample.reshape(src.shape).to(src.device)
+
     # the reference's loop on the host, any Sampler object.  float32 numpy, one correctly rounded operation per operator of the
     # reference (torch's vectorised CPU sqrt is not correctly rounded, and one ulp in a conditional scale moves the sample)
     @staticmethod
@@ -502,8 +569,12 @@ class GaussianCoder(Coder):
         return [ix for ix, _ in coded], sample
 
     def decode(self, coding_dist, indices, seed, **kwargs):
-        """coder.py:459-491 (`batched=True`: as `encode`)."""
+        """coder.py:459-491 (`batched=True`: as `encode`; `packed=(K, idx, rows)`, `status=`: decode_tensors_device)."""
         batched = kwargs.pop("batched", False)
+        packed, status = kwargs.pop("packed", None), kwargs.pop("status", None)
+        if packed is not None:       # (K, idx, rows) on the device: decode_tensors_device, nothing crosses to the host
+            return self.decode_tensors_device(coding_dist.loc, coding_dist.scale, packed[0], packed[1], seed, self.block_size,
+                                              rows=packed[2], status=status)
         self._check_sampler()
         loc, scale = torch.as_tensor(coding_dist.loc), torch.as_tensor(coding_dist.scale)
         if self._on_device(loc, self.block_size):

@@ -163,6 +163,19 @@ class BlockLayout:
             self._natural_dev = torch.from_numpy(self.natural.astype(np.int32)).to(self.block_base.device)
         return self._natural_dev
 
+    def identity_rows_dev(self):
+        """int32 device [n_tensors * blocks_per_tensor]: i * blocks_per_tensor + j itself (rows kept in (tensor, block) order)."""
+        if getattr(self, "_identity_rows_dev", None) is None:
+            self._identity_rows_dev = torch.arange(self.n_tensors * self.blocks_per_tensor, dtype=torch.int32, device=self.block_base.device)
+        return self._identity_rows_dev
+
+    def natural_inverse_dev(self):
+        """int64 device index: the (tensor, block) position i * blocks_per_tensor + j that row r of this layout holds -- what gathers
+        rows kept in (tensor, block) order into `lay` order with one index_select."""
+        if getattr(self, "_natural_inverse_dev", None) is None:
+            self._natural_inverse_dev = torch.from_numpy(np.argsort(np.asarray(self.natural), kind="stable").astype(np.int64)).to(self.block_base.device)
+        return self._natural_inverse_dev
+
     def packed_index(self, n_calls):
         """int64 device index into the rows of `n_calls` read-backs of this layout stacked call after call: position
         (image i, call r, block j) -> r * n_blocks + natural[i * blocks_per_tensor + j] (PendingCode.gather_packed)."""
@@ -436,8 +449,20 @@ class Engine:
             self._dec_ws[key] = ws
         return ws
 
-    def decode_blocks(self, params, lay, p_loc, p_scale, seed, K, indices, mode="auto"):
-        """Asynchronous.  K / indices rows in `lay` order.  mode:
+    def rows_status(self, K, k_stride, idx, idx_stride, max_K, n_groups, blocks_per_group, block_row, min_K, k_limit, n_samples, status):
+        """irec_decode_rows_status on the current stream: the first cause per group accumulated into `status` (int32 [n_groups], device).
+        K / idx: int32 device tensors whose FIRST element is row 0's; strides in elements (include/irec.h)."""
+        assert K.dtype == torch.int32 and idx.dtype == torch.int32 and status.dtype == torch.int32 and status.is_contiguous()
+        assert status.numel() >= n_groups and (block_row is None or (block_row.dtype == torch.int32 and block_row.is_contiguous()))
+        _lib.check(self.lib.irec_decode_rows_status(int(n_groups), int(blocks_per_group), _ptr(block_row), _ptr(K), int(k_stride),
+                                                    _ptr(idx) if idx.numel() else None, int(idx_stride), int(max_K), int(min_K),
+                                                    int(min(k_limit, _lib.INT32_MAX)), int(n_samples), _ptr(status), self._stream()),
+                   "irec_decode_rows_status")
+        return status
+
+    def decode_blocks(self, params, lay, p_loc, p_scale, seed, K, indices, mode="auto", block_row=None):
+        """Asynchronous.  K / indices rows in `lay` order -- or, on the `tensors` modes with `block_row` (int32 device, [n_tensors *
+        blocks_per_tensor]), wherever block_row[i * blocks_per_tensor + j] says: K / indices may then be larger arrays read in place.  mode:
           "auto"    whole tensors staged in LDS (irec_beam_decode_tensors) when `lay` is a complete layout whose tensors fit,
                     else "tables";
           "tensors" / "tensors_fused"   that entry point, with / without the per-call proposal tables;
@@ -463,11 +488,13 @@ class Engine:
             tparams = self.with_table_dims(params, lay)
             ws = self._decode_ws(tparams, max_K)
             _lib.check(self.lib.irec_beam_decode_tensors(self.ctx, ctypes.byref(tparams), lay.n_tensors, lay.n, bs_eff,
-                                                         _ptr(lay.natural_dev()), _ptr(lay.perm), _ptr(p_loc), _ptr(p_scale),
+                                                         _ptr(lay.natural_dev() if block_row is None else block_row), _ptr(lay.perm), _ptr(p_loc), _ptr(p_scale),
                                                          int(seed), max_K, _ptr(K), _ptr(indices), _ptr(sample), _ptr(ws),
                                                          ws.numel() if ws is not None else 0, self._stream()),
                        "irec_beam_decode_tensors")
             return sample
+        if block_row is not None:
+            raise ValueError("block_row goes with the 'tensors' decode modes only")
         if mode != "tables":
             if mode == "fused":
                 params = self.with_table_dims(params, lay)

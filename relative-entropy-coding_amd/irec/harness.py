@@ -20,7 +20,8 @@ import torch
 
 from . import sharding
 from .coding import CodingError
-from .io import decode_files, decode_files_device, encode_files, read_compressed_code, write_compressed_code
+from .io import decode_files, decode_files_device, encode_files, read_compressed_code, rec_header_words, write_compressed_code
+from .models.resnet_vae import status_text
 
 
 def _host_leg(chunk_shape, names, seed, block_size, out_dir, S, K, idx, t_compress):
@@ -146,6 +147,78 @@ def compress_images(model, images, names, seed, block_size, out_dir, batch=None,
                          "indices_recovered": bool(ok),
                          "comp_time": t_compress / chunk.shape[0] + (time.perf_counter() - t1)})
     return rows
+
+
+def rec_file_groups(datas):
+    """The header grouping of decompress_images, a pure function over the files' bytes: (infos, groups).  infos[i]: the header words of
+    file i (irec.io.rec_header_words: seed, image_shape, block_size, max_index, R, bpt, max_partitions), None for bytes too short to
+    hold their header.  groups: {(seed, image_shape, R, bpt): [file indices, in the order given]} -- the files one decompress_rec call
+    takes together; bpt is the one block count of every residual block, or the tuple of counts of a ragged file (which the device
+    reader does not take)."""
+    infos, groups = [], {}
+    for i, data in enumerate(datas):
+        w = rec_header_words(data)
+        infos.append(w)
+        if w is None:
+            continue
+        bpt = w["bpt"][0] if len(set(w["bpt"])) == 1 else tuple(w["bpt"])
+        groups.setdefault((w["seed"], w["image_shape"], w["R"], bpt), []).append(i)
+    return infos, groups
+
+
+def decompress_images(model, paths, batch=None, strict=True):
+    """The read side of compress_images: .rec files -> (images, rows).  The files are read and their headers parsed on the host
+    (RecHeader over the 28 + 16 R header bytes), files of equal (seed, shape, R, bpt) are grouped, each group's bytes are uploaded
+    once per batch and decoded by model.decompress_rec -- the arithmetic decoder, the row checks and the generative pass on the
+    device, one read-back (the per-image status) per batch.
+    images: [n, 3, H, W] in the order of `paths` -- a list of [3, H, W] tensors when the files hold more than one shape or a file is
+    too short for its header (its entry is None: its shape is not known); rows: one dict per file (name, status, and where the
+    header could be read seed, image_shape, block_size, decomp_time; `error` with the coder's text where status != 0).
+    strict: CodingError for the first file, in the order of `paths`, that cannot be decoded; strict=False reports it in its row and
+    leaves its image zero."""
+    dev = next(model.parameters()).device
+    datas = []
+    for path in paths:
+        with open(path, "rb") as fh:
+            datas.append(fh.read())
+    infos, groups = rec_file_groups(datas)
+    images, rows = [None] * len(paths), [None] * len(paths)
+    for i, w in enumerate(infos):
+        if w is None:
+            rows[i] = {"name": os.path.basename(paths[i]), "status": 4, "error": status_text(4)}     # IREC_REC_E_TRUNCATED_HEADER
+    for (seed, (h, w_, c), R, bpt), members in groups.items():
+        fits = isinstance(bpt, int) and R == model.num_res_blocks and c == 3 and h % 2 == 0 and w_ % 2 == 0 and \
+            bpt == model.blocks_per_tensor((1, c, h, w_))
+        step = len(members) if not batch else int(batch)
+        for lo in range(0, len(members), step):
+            part = members[lo:lo + step]
+            t0 = time.perf_counter()
+            if fits:
+                sizes = np.array([len(datas[i]) for i in part], dtype=np.int64)
+                off = np.concatenate([[0], np.cumsum(sizes)])
+                host = np.frombuffer(b"".join(datas[i] for i in part), dtype=np.uint8)
+                max_K = max([1] + [m for i in part for m in infos[i]["max_partitions"] if m <= 65536])
+                blob = torch.from_numpy(host.copy()).to(dev)
+                rec, status, K = model._decompress_rec_status(blob, off, seed, (len(part), c, h, w_), max_K)
+                texts = [model.status_text(st, K[k]) if st else "" for k, st in enumerate(status)]
+            else:                                                       # IREC_REC_E_STRUCTURE: not this model's block structure
+                rec, status = torch.zeros((len(part), 3, h, w_), device=dev), [17] * len(part)
+                texts = [f"{status_text(17)}: {R} residual blocks of {bpt} blocks for a {h} x {w_} x {c} image do not match the model"] * len(part)
+            dt = (time.perf_counter() - t0) / len(part)
+            for k, i in enumerate(part):
+                images[i] = rec[k] if status[k] == 0 else torch.zeros_like(rec[k])
+                rows[i] = {"name": os.path.basename(paths[i]), "seed": seed, "image_shape": (h, w_, c), "block_size": infos[i]["block_size"],
+                           "status": int(status[k]), "decomp_time": dt}
+                if status[k]:
+                    rows[i]["error"] = texts[k]
+    if strict:
+        for i, row in enumerate(rows):
+            if row["status"]:
+                raise CodingError(f"{row['error']} (image {i})")
+    shapes = {tuple(im.shape) for im in images if im is not None}
+    if len(shapes) == 1 and all(im is not None for im in images):
+        return torch.stack(images, dim=0), rows
+    return images, rows
 
 
 def compress_sharded(model, all_images, seed, block_size, out_dir, rank=0, world=1, dist=None, batch=None):

@@ -1,4 +1,4 @@
 """Mirror of the reference's rec/io package for the index streams the beam-search coder emits."""
 from .entropy_coding import ArithmeticCoder  # noqa: F401
 from .utils import write_compressed_code, read_compressed_code, encode_files, decode_files  # noqa: F401
-from .utils import encode_files_device, decode_files_device  # noqa: F401
+from .utils import encode_files_device, decode_files_device, rec_header_words, rec_files_max_K  # noqa: F401

@@ -280,23 +280,33 @@ def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=No
     raise ValueError("irec_rec_encode_files_device: the files did not fit the size the call itself reported")
 
 
-def _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K):
+def _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K, on_device=False):
     """One irec_rec_decode_files_device call on the current stream: (headers int32 [N, 9] holding the uint32 words, K, idx, status int32 [N])
-    on the device, nothing read back but `offsets` (checked against the blob before any kernel sees them)."""
+    on the device, nothing read back but `offsets` (checked against the blob before any kernel sees them).
+    on_device: offsets that ARE on the device stay there -- instead of the check on the host they are clamped into the blob and made
+    non-decreasing by two small device operations, so that no file's range leaves the blob whatever they hold (a range that was
+    wrong reads as a damaged file); nothing is read back and the call can be captured in a HIP graph."""
     import torch
     lib = _lib.load()
     if not (blob.is_cuda and blob.dtype == torch.uint8):
         raise ValueError("decode_files_device takes a CUDA uint8 tensor")
     blob = blob.contiguous()
     dev = blob.device
-    off_host = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
-    n = off_host.size - 1
-    # the kernels read no byte outside [offsets[i], offsets[i + 1]): those ranges must lie inside the blob
-    if n < 0 or off_host[0] < 0 or (np.diff(off_host) < 0).any() or off_host[-1] > blob.numel():
-        raise ValueError("decode_files_device: offsets must be non-decreasing and end inside the blob")
     r, bpt, max_K = int(n_res_blocks), int(blocks_per_res), int(max_K)
+    off_dev = None
+    if on_device and hasattr(offsets, "is_cuda") and offsets.is_cuda:
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError("decode_files_device: device offsets must be int64 [N + 1]")
+        n = offsets.numel() - 1
+        off_dev = torch.cummax(offsets.to(dev).clamp(0, blob.numel()), dim=0).values.contiguous()
+    else:
+        off_host = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
+        n = off_host.size - 1
+        # the kernels read no byte outside [offsets[i], offsets[i + 1]): those ranges must lie inside the blob
+        if n < 0 or off_host[0] < 0 or (np.diff(off_host) < 0).any() or off_host[-1] > blob.numel():
+            raise ValueError("decode_files_device: offsets must be non-decreasing and end inside the blob")
     with torch.cuda.device(dev):
-        offsets = torch.from_numpy(off_host.copy()).to(dev)                    # (a copy: the caller's array may be read-only)
+        offsets = off_dev if off_dev is not None else torch.from_numpy(off_host.copy()).to(dev)   # (a copy: the caller's array may be read-only)
         ws = torch.empty(lib.irec_rec_device_workspace_bytes(n, r), dtype=torch.uint8, device=dev)
         hdr = torch.zeros((n, 9), dtype=torch.int32, device=dev)
         K = torch.empty((n, r, bpt), dtype=torch.int32, device=dev)
@@ -319,6 +329,39 @@ def decode_files_device(blob, offsets, n_res_blocks, blocks_per_res, max_K):
     hdr, K, idx, status = _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K)
     _raise_first_status(status.cpu().numpy())
     return hdr.to(torch.int64) & 0xFFFFFFFF, K, idx
+
+
+def rec_header_words(data):
+    """The header of one .rec file from its bytes (a pure function: RecHeader over the 28 + 16 R header bytes): a dict of seed,
+    image_shape (h, w, c), block_size, max_index, R, bpt (blocks per residual block, a list), max_partitions (a list), or None for
+    bytes too short to hold their own header."""
+    import io
+    data = bytes(memoryview(np.ascontiguousarray(data)) if isinstance(data, np.ndarray) else data)
+    if len(data) < _STATIC.size:
+        return None
+    r = _STATIC.unpack(data[:_STATIC.size])[8]
+    if len(data) < _STATIC.size + 16 * r:
+        return None
+    try:
+        h = RecHeader.read(io.BytesIO(data[:_STATIC.size + 16 * r]))
+    except (struct.error, ValueError):
+        return None
+    return {"seed": h.seed, "image_shape": tuple(h.image_shape), "block_size": h.block_size, "max_index": h.max_index, "R": r,
+            "bpt": list(h.blocks_per_res_block), "max_partitions": list(h.max_partitions)}
+
+
+def rec_files_max_K(blob, offsets):
+    """Index slots per block that decode the files blob[offsets[i]:offsets[i + 1]] (host bytes): the largest max_partitions word of their
+    headers, at least 1.  A word above IREC_MAX_PARTITIONS does not count: the reader refuses that file whatever max_K is
+    (IREC_REC_E_BLOCK_COUNTS), and a damaged word must not size a buffer."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    need = 1
+    for i in range(len(offsets) - 1):
+        words = rec_header_words(blob[int(offsets[i]):int(offsets[i + 1])])
+        if words is not None:
+            need = max([need] + [m for m in words["max_partitions"] if m <= _lib.MAX_PARTITIONS])
+    return need
+
 
 def write_compressed_code(file_path, seed, image_shape, block_size, block_indices, max_index,
                           num_aux_var_counts_file=None, index_counts_file=None):

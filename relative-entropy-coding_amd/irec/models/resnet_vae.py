@@ -11,16 +11,39 @@ are coded strictly in sequence (the prior of block n+1 depends on the coded late
 arguments (`sampler`, `sampler_args`, `coder_args`, `kl_per_partition`, `encoder_args`, `decoder_args`) keep their
 names and meaning.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..coding import BeamSearchCoder, GaussianCoder, ImportanceSampler
+from .. import _lib
+from ..coding import BeamSearchCoder, CodingError, GaussianCoder, ImportanceSampler
 from ..coding.beam_search_coder import MorePartitionsNeeded, PendingCode, SplitNotResident
 
 
 class ModelError(Exception):
     """rec/models/resnet_vae.py (ModelError)."""
+
+
+# the joined per-image status of decompress_rec / decompress_packed beside irec_rec_status (1 .. 18)
+STATUS_HEADER = 19      # the file's seed, height, width, channels or R differ from the call's
+STATUS_ROWS = 32        # + irec_rows_status (1 K_RANGE, 2 INDEX_RANGE, 3 RATIO_TABLE)
+
+
+def status_text(status, table_length=None, requested=None):
+    """The coder's text for a joined status.  A count beyond the fitted ratio table gets the reference's message when the table's
+    length and the count that was asked for are known."""
+    from ..coding.coder import RATIO_TABLE_TEXT
+    from ..io.utils import _REC_STATUS_TEXT
+    status = int(status)
+    if status == STATUS_ROWS + _lib.IREC_ROWS_E_RATIO_TABLE:
+        if table_length is not None and requested is not None:
+            return RATIO_TABLE_TEXT.format(table_length, requested)
+        return RATIO_TABLE_TEXT.split(".")[0] + "."
+    own = {STATUS_HEADER: "decompress_rec: the file's header (seed, image shape, residual blocks) differs from the arguments",
+           STATUS_ROWS + _lib.IREC_ROWS_E_K_RANGE: "partition count out of range [min_K, max_K]",
+           STATUS_ROWS + _lib.IREC_ROWS_E_INDEX_RANGE: "index out of range [0, n_samples)"}
+    return own.get(status) or _REC_STATUS_TEXT.get(status, f"irec_rec: status {status}")
 
 
 class deterministic_transforms:
@@ -331,6 +354,7 @@ class BidirectionalResNetVAE(nn.Module):
                                        kl_per_partition=kl_per_partition, name=f"resnet_block_{res_block_idx}")
             for res_block_idx in range(num_res_blocks)])
         self._generative_base = nn.Parameter(torch.zeros(deterministic_filters))
+        self._packed_rows_cache, self._header_want_cache = {}, {}   # device constants of the packed decompress path, per batch shape
 
     def generative_base(self, batch_size, height, width):
         """resnet_vae.py:619-623."""
@@ -462,6 +486,225 @@ class BidirectionalResNetVAE(nn.Module):
                     args = {"seed": seed, "indices": [block_indices[i][r] for i in range(batch_size)], "batched": True}
                 tensor = resnet_block(tensor, inference_pass=False, decoder_args=args)
             return self._finish(tensor)
+
+    # ---- the read side on the device: rows that never leave it, one read-back per batch -----------------------------------------
+    def _packed_rows(self, n, R, bpt, device):
+        """Per residual block r the int32 device map (image i, block j) -> row (i R + r) bpt + j of packed K [N, R, bpt] arrays."""
+        cache = self._packed_rows_cache
+        key = (n, R, bpt, str(device))
+        if key not in cache:
+            if len(cache) > 16:
+                cache.clear()
+            i = torch.arange(n, dtype=torch.int32).reshape(n, 1)
+            j = torch.arange(bpt, dtype=torch.int32).reshape(1, bpt)
+            cache[key] = [((i * R + r) * bpt + j).reshape(-1).contiguous().to(device) for r in range(R)]
+        return cache[key]
+
+    def _header_want(self, seed, image_shape, device):
+        """The header words (seed, height, width, channels, R) a file of this call must carry, int64 on the device."""
+        cache = self._header_want_cache
+        key = (int(seed), tuple(int(v) for v in image_shape[1:]), self.num_res_blocks, str(device))
+        if key not in cache:
+            if len(cache) > 16:
+                cache.clear()
+            _, c, h, w = image_shape
+            cache[key] = torch.tensor([int(seed) & 0xFFFFFFFF, int(h), int(w), int(c), self.num_res_blocks], dtype=torch.int64).to(device)
+        return cache[key]
+
+    def blocks_per_tensor(self, image_shape):
+        """Coder blocks per residual block and image (Coder.split, coder.py:69-83) for images of this shape."""
+        _, _, h, w = image_shape
+        n = (h // 2) * (w // 2) * self.stochastic_filters
+        bs = self.residual_blocks[0].coder.block_size
+        return 1 if bs is None else -(-n // int(bs))
+
+    def _decompress_device(self, K, idx, seed, image_shape, status):
+        """The generative pass driven by rows on the device: K [N, R, bpt], idx [N, R, bpt, max_K] int32 (contiguous, or the views of
+        one joined tensor), every residual block's coder reading its rows in place (decoder_args={"packed": ...}) and accumulating
+        its verdict on them into `status` (int32 [N], device).  No host synchronisation: capturable in a HIP graph
+        (GraphedDecompress)."""
+        batch_size, _, height, width = image_shape
+        n, R, bpt = K.shape
+        if n != batch_size or R != self.num_res_blocks or tuple(idx.shape[:3]) != (n, R, bpt):
+            raise ModelError(f"K {tuple(K.shape)} / idx {tuple(idx.shape)} are not [N = {batch_size}, R = {self.num_res_blocks}, bpt] and [N, R, bpt, max_K]")
+        if bpt != self.blocks_per_tensor(image_shape):
+            raise ModelError(f"{bpt} blocks per residual block, but images of shape {tuple(image_shape)} are coded in {self.blocks_per_tensor(image_shape)}")
+        rows = self._packed_rows(n, R, bpt, K.device)
+        with deterministic_transforms():
+            tensor = self.generative_base(batch_size=batch_size, width=width, height=height)
+            for r, resnet_block in enumerate(self.residual_blocks):
+                tensor = resnet_block(tensor, inference_pass=False,
+                                      decoder_args={"seed": seed, "indices": None, "batched": True, "packed": (K, idx, rows[r]),
+                                                    "status": status})
+            return self._finish(tensor)
+
+    def status_text(self, status, K_image=None):
+        """status_text for one image of this model; K_image (its counts [R, bpt], device or numpy): the reference's ratio-table message
+        names the count of the block that set the status -- the first, in coding order, beyond the table."""
+        if int(status) != STATUS_ROWS + _lib.IREC_ROWS_E_RATIO_TABLE or K_image is None:
+            return status_text(status)
+        counts = (K_image.cpu().numpy() if hasattr(K_image, "cpu") else np.asarray(K_image)).reshape(self.num_res_blocks, -1)
+        for r, block in enumerate(self.residual_blocks):
+            if block.coder.extrapolate_auxiliary_ratios:
+                continue
+            length = int(block.coder.aux_variable_variance_ratios.shape[0])
+            beyond = counts[r][counts[r] > length]
+            if beyond.size:
+                return status_text(status, length, int(beyond[0]))
+        return status_text(status)
+
+    def _raise_status(self, status, K=None):
+        """CodingError for the first image with a nonzero joined status (decompress_rec has the encoding), "(image i)" appended."""
+        bad = np.flatnonzero(status)
+        if bad.size:
+            i = int(bad[0])
+            raise CodingError(f"{self.status_text(status[i], None if K is None else K[i])} (image {i})")
+
+    @torch.no_grad()
+    def decompress_packed(self, K, idx, seed, image_shape, strict=True):
+        """`decompress` for packed rows on the device (K [N, R, bpt], idx [N, R, bpt, max_K] int32 CUDA: the arrays of
+        irec.io.decode_files_device, or the views of PendingCode.gather_packed_device): ONE read-back, the per-image status.
+        strict: CodingError naming the first image whose rows cannot be decoded; strict=False: (reconstruction, status int32 numpy
+        [N]) -- 0, or STATUS_ROWS + irec_rows_status; the images with status 0 are what they would be without the others."""
+        status = torch.zeros(int(image_shape[0]), dtype=torch.int32, device=K.device)
+        reconstruction = self._decompress_device(K, idx, seed, image_shape, status)
+        host = status.cpu().numpy()
+        host = np.where(host != 0, host + STATUS_ROWS, 0).astype(np.int32)
+        if strict:
+            self._raise_status(host, K)
+            return reconstruction
+        return reconstruction, host
+
+    def _decompress_rec_device(self, blob, offsets, seed, image_shape, max_K):
+        """Everything of decompress_rec that runs on the device: the three launches of the .rec reader, the header check, the pass,
+        the joined status.  Returns (reconstruction, status int32 [N] on the device, K).  No host synchronisation."""
+        from ..io.utils import _decode_files_device_launch
+        n, R, bpt = int(image_shape[0]), self.num_res_blocks, self.blocks_per_tensor(image_shape)
+        hdr, K, idx, rec_status = _decode_files_device_launch(blob, offsets, R, bpt, max_K, on_device=True)
+        words = hdr.to(torch.int64).bitwise_and_(0xFFFFFFFF)
+        words = torch.cat([words[:, 0:1], words[:, 3:6], words[:, 8:9]], dim=1)      # seed, height, width, channels, R
+        differs = (words != self._header_want(seed, image_shape, K.device)).any(dim=1)
+        rows_status = torch.zeros(n, dtype=torch.int32, device=K.device)
+        reconstruction = self._decompress_device(K, idx, seed, image_shape, rows_status)
+        joined = torch.where(rec_status != 0, rec_status,
+                             torch.where(differs, torch.full_like(rec_status, STATUS_HEADER),
+                                         torch.where(rows_status != 0, rows_status + STATUS_ROWS, rows_status)))
+        return reconstruction, joined, K
+
+    def files_max_K(self, blob, offsets):
+        """Index slots per block that decode the files of a blob on the device: the largest max_partitions word of their headers
+        (irec.io.rec_files_max_K).  Only the 28 + 16 R header bytes of every file are gathered and copied to the host."""
+        from ..io.utils import rec_files_max_K
+        dev, hb = blob.device, 28 + 16 * self.num_res_blocks
+        off = offsets.to(dev) if hasattr(offsets, "is_cuda") else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev)
+        n = off.numel() - 1
+        if n < 1 or blob.numel() < 1:
+            return 1
+        at = (off[:-1, None] + torch.arange(hb, device=dev)).clamp_(0, blob.numel() - 1)
+        whole = (off[1:] - off[:-1] >= hb) & (off[:-1] >= 0) & (off[1:] <= blob.numel())          # a shorter file: a zero header, no words
+        head = blob.reshape(-1)[at] * whole[:, None].to(torch.uint8)
+        return rec_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb)
+
+    @torch.no_grad()
+    def _decompress_rec_status(self, blob, offsets, seed, image_shape, max_K=None):
+        """decompress_rec up to its read-back: (reconstruction, status int32 numpy [N], K on the device)."""
+        if max_K is None:
+            max_K = self.files_max_K(blob, offsets)
+        reconstruction, joined, K = self._decompress_rec_device(blob, offsets, seed, image_shape, int(max_K))
+        return reconstruction, joined.cpu().numpy(), K
+
+    @torch.no_grad()
+    def decompress_rec(self, blob, offsets, seed, image_shape, max_K=None, strict=True):
+        """The inverse of compress_rec: N .rec files (blob uint8 CUDA, file i = blob[offsets[i]:offsets[i + 1]]; offsets [N + 1] on the
+        device or the host) to reconstructions [N, 3, H, W], with the indices never on the host: one launch of the device reader
+        (irec.io.decode_files_device's launch form), the headers checked on the device against seed / image_shape / R, the pass
+        (every coder checks its rows on the device), and ONE read-back -- the per-image status:
+          0 ok;  1 .. 18 irec_rec_status (include/irec.h);  STATUS_HEADER: seed, height, width, channels or R differ from the
+          arguments;  STATUS_ROWS + irec_rows_status: a count or an index the coder cannot decode.  First cause in that order.
+        strict: CodingError with the coder's text for the first such image, "(image i)" appended; strict=False: (reconstruction,
+        status int32 numpy [N]), the images with status 0 being what they would be without the others (a refused image's rows read as
+        zero partitions).  max_K: index slots per block (a file with a longer row: IREC_REC_E_MAX_K); None: the largest
+        max_partitions word of the files' headers (files_max_K) -- a second, small read-back of the header bytes, which a driver that
+        has the bytes on the host already (harness.decompress_images) spares by passing max_K."""
+        reconstruction, host, K = self._decompress_rec_status(blob, offsets, seed, image_shape, max_K)
+        if strict:
+            self._raise_status(host, K)
+            return reconstruction
+        return reconstruction, host
+
+
+class GraphedDecompress:
+    """`model.decompress_rec` for a fixed batch shape as ONE HIP graph on one stream: the three launches of the .rec reader, the
+    header check and the whole generative pass (every convolution, hand-off and decode launch of the sequential residual blocks,
+    each coder's row check included) are captured once and replayed per batch of files.  Static buffers: the files' bytes
+    (blob_bytes), their offsets and the joined status, which is the only read-back.  No parallel branches.  Same outputs as
+    decompress_rec.  A file that needs more index slots than the captured max_K (IREC_REC_E_MAX_K), or a blob larger than the static
+    buffer, is answered by the eager path with the size it needs, and the next call captures again at that size."""
+
+    def __init__(self, model, image_shape, seed, R, bpt, max_K, blob_bytes):
+        self.model, self.image_shape, self.seed = model, tuple(int(v) for v in image_shape), seed
+        self.device = next(model.parameters()).device
+        if int(R) != model.num_res_blocks or int(bpt) != model.blocks_per_tensor(self.image_shape):
+            raise ModelError(f"R = {R}, bpt = {bpt}: the model codes images of shape {self.image_shape} in {model.num_res_blocks} residual "
+                             f"blocks of {model.blocks_per_tensor(self.image_shape)} blocks")
+        self.R, self.bpt, self.max_K, self.blob_bytes = int(R), int(bpt), max(1, int(max_K)), max(1, int(blob_bytes))
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.graph = None
+        self.captures = 0
+
+    @torch.no_grad()
+    def _capture(self):
+        n = self.image_shape[0]
+        self.static_blob = torch.zeros(self.blob_bytes, dtype=torch.uint8, device=self.device)
+        self.static_offsets = torch.zeros(n + 1, dtype=torch.int64, device=self.device)     # N empty files: every image refused, no fault
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):               # warm-up on the graph's stream: caches, ITS scratch, MIOpen
+            for _ in range(2):
+                self.model._decompress_rec_device(self.static_blob, self.static_offsets, self.seed, self.image_shape, self.max_K)
+        cur.wait_stream(self.stream)
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=self.stream):
+            self.reconstruction, self.status, self.K = self.model._decompress_rec_device(self.static_blob, self.static_offsets, self.seed,
+                                                                                         self.image_shape, self.max_K)
+        self.graph = g
+        self.captures += 1
+
+    def _eager(self, blob, offsets, strict):
+        """The eager path at the size this batch needs.  Where that is more than the graph holds (a longer row by the headers' own
+        words, a larger blob) the next call captures at that size; a damaged file that merely reports IREC_REC_E_MAX_K keeps the graph."""
+        need = self.model.files_max_K(blob, offsets)
+        if need > self.max_K or blob.numel() > self.blob_bytes:
+            self.max_K, self.blob_bytes, self.graph = max(self.max_K, need), max(self.blob_bytes, int(blob.numel())), None
+        return self.model.decompress_rec(blob, offsets, self.seed, self.image_shape, max_K=max(self.max_K, need), strict=strict)
+
+    @torch.no_grad()
+    def __call__(self, blob, offsets, strict=True):
+        """blob: uint8 CUDA tensor; offsets: [N + 1] on the host (numpy / list), checked against the blob before any kernel sees them."""
+        n = self.image_shape[0]
+        offsets = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
+        if offsets.size != n + 1 or offsets[0] < 0 or (np.diff(offsets) < 0).any() or offsets[-1] > blob.numel():
+            raise ValueError(f"GraphedDecompress: offsets must be {n + 1} non-decreasing positions that end inside the blob")
+        if blob.numel() > self.blob_bytes:
+            return self._eager(blob, offsets, strict)
+        if self.graph is None:
+            self._capture()
+        self.static_blob[:blob.numel()].copy_(blob.reshape(-1))
+        self.static_offsets.copy_(torch.from_numpy(offsets))
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            self.graph.replay()
+        cur.wait_stream(self.stream)
+        host = self.status.cpu().numpy()
+        if (host == _lib.IREC_REC_E_MAX_K).any():
+            return self._eager(blob, offsets, strict)
+        reconstruction = self.reconstruction.clone()
+        if strict:
+            self.model._raise_status(host, self.K)
+            return reconstruction
+        return reconstruction, host
 
 
 class GraphedCompress:

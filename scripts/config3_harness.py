@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """BASELINE.json configs[2] end to end on this rank's GPU: 300 Cifar10-shaped images through the 24-block RVAE shim
 (random-init weights: no checkpoint exists), image i -> rank i mod G, per-GPU share compressed as ONE batch
-(38 images: one coder launch per residual block), .rec written / read back / compared per image, bits gathered.
+(38 images: one coder launch per residual block), .rec written / read back / compared per image, bits gathered; then the decode
+leg, .rec -> pixels on the device -> compared with the compress pass.
 Also times single-image compression (N = 1: the reference's only mode).  Diagnostic; prints one JSON line on rank 0."""
 import argparse
 import json
@@ -96,6 +97,14 @@ def main():
             lane_times[lanes] = timed_median(lambda: gshare(mine))
             del gshare
         t_graph_share = min(lane_times.values())
+    # the decode leg: this rank's .rec files (written by the passes above) -> pixels on the device (harness.decompress_images: the
+    # arithmetic decoder, every coder's row check and the generative pass on the GPU, one read-back) -> compared with the compress pass
+    rec_paths = [os.path.join(out_dir, f"{r['name']}.rec") for r in rows if "error" not in r]
+    ref_pixels = model.compress_rec(mine_dev, seed=42)[2]
+    dec_pixels, dec_rows = harness.decompress_images(model, rec_paths)
+    decode_diff = float((dec_pixels - ref_pixels).abs().max())
+    decode_ok = all(r["status"] == 0 for r in dec_rows) and decode_diff <= 1e-5      # the bound of batched convolutions (tests/test_models_shim.py)
+    t_decode = timed_median(lambda: harness.decompress_images(model, rec_paths))
     singles = []
     for i in range(args.singles):
         x = images[i:i + 1].to(device)
@@ -128,6 +137,8 @@ def main():
             "latents_per_s_model_compress": share * args.blocks / t_model,
             "model_compress_seconds_share_graph": t_graph_share, "graph_share_equals_eager": graph_share_equal,
             "model_compress_seconds_share_graph_by_lanes": lane_times if not args.no_graph else None,
+            "decode_seconds_share_incl_rec_io": t_decode, "images_per_s_decode_incl_rec_io": share / t_decode,
+            "decode_pixels_equal_compress_pass_1e-5": decode_ok, "decode_pixels_max_abs_diff": decode_diff,
             "single_image_ms": [round(1e3 * s, 2) for s in singles], "single_image_ms_median": 1e3 * sorted(singles)[len(singles) // 2],
             "single_image_graph_ms": [round(1e3 * s, 2) for s in graph_ms], "single_image_graph_ms_median": 1e3 * sorted(graph_ms)[len(graph_ms) // 2],
             "graph_equals_eager": graph_equal,
