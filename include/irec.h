@@ -295,12 +295,15 @@ irec_status irec_beam_decode_tensors(irec_context *ctx, const irec_params *p, in
                                      const int32_t *indices, float *out_sample, void *workspace, size_t workspace_bytes,
                                      void *hip_stream);
 
-/* ---- the sequential importance coder: GaussianCoder(sampler=ImportanceSampler(coding_bits), alpha = inf) -----------------
+/* ---- the sequential importance coder: GaussianCoder(sampler=ImportanceSampler(coding_bits, alpha)), 1 <= alpha <= inf ------
  * GaussianCoder.encode_block / decode_block (rec/coding/coder.py:493-584) driven the way GaussianCoder.encode / decode drive them
  * (coder.py:412-491: the same seed for every block): per block K = ceil(KL / Omega) serial steps -- K - 1 auxiliary variables
  * (ratio get_auxiliary_ratio(i), i = K-1 .. 1), then the block's sample -- each one encode_gaussian_importance_sample
  * (importance_sampling.py:9-79) with seed + step, followed by the conditional update of target and coder (coder.py:157-171).
  * A block emits max(K, 1) indices (a zero-KL block one, coder.py:548-557).  Arithmetic: DESIGN.md §3.
+ * alpha = inf (the reference's default): a step takes the first greatest importance weight -- irec_gc_importance_encode / _ws.
+ * 1 <= alpha < inf: the Gumbel-max over alpha * w + g (importance_sampling.py:67-72) -- irec_gc_importance_encode_gumbel with the
+ * perturbations g as one more table.  The decoder never looks at alpha: irec_gc_importance_decode serves both.
  *
  * The standard-normal proposals of step j are tf.random.normal([S, 1, D]) after tf.random.set_seed(seed + j): they depend on
  * (seed + j, S, D) only, so every block of D dims reads the same S x D numbers at step j.  They pass through libm on the host
@@ -351,6 +354,35 @@ irec_status irec_gc_importance_encode_ws(irec_context *ctx, int64_t n_blocks, co
                                          const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
                                          float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
                                          float *out_sample, void *workspace, size_t workspace_bytes, void *hip_stream);
+/* ---- finite alpha: the Gumbel-max branch (importance_sampling.py:67-72) ----
+ * The perturbations of step j are g = stateless_gumbel_sample([S], seed + j + 1) = -logf(-logf(z)), z = tf.random.stateless_normal([S],
+ * [seed + j + 1, seed + j + 2]) (rec/coding/utils.py:9-12: a NORMAL draw inside the double log, so g is NaN for about two samples in
+ * three -- reproduced as written).  They pass through libm on the host, so they are DATA the kernels read, like the normal tables, and
+ * irec_importance_encode evaluates the same function:
+ *   out[j * S_pad + s] = g[s] of step j,  j < steps, s < n_samples, S_pad as above (the padding is zero, and no lane reads it).
+ * irec_gumbel_table_floats: floats of the table, or 0 (text in irec_last_error) for sizes out of range.  irec_gumbel_table_build: host
+ * memory, n_threads host threads (0: one per core, at most 16). */
+size_t irec_gumbel_table_floats(int32_t n_samples, int32_t steps);
+irec_status irec_gumbel_table_build(int64_t seed, int32_t n_samples, int32_t steps, float *out, int32_t n_threads);
+typedef struct {
+  const float *table;   /* device: irec_gumbel_table_build(seed, n_samples, steps) -- or any numbers of the caller's: they are data */
+  int32_t n_samples;
+  int32_t steps;
+  float alpha;
+} irec_gumbel_table;
+/* irec_gc_importance_encode_ws over v[s] = float32(alpha) * w[s] + g[step][s] (one float32 multiply, then one float32 add): the index of
+ * a step is the first s with the greatest v[s], the accumulator starts at (0, -FLT_MAX) and moves on a strict ">" -- a NaN is never
+ * chosen, +inf can win, -inf never does.  The conditional update and the emitted sample use x[index] as at alpha = inf.
+ *   gumbel == NULL  irec_gc_importance_encode_ws, bit for bit (the same kernels)
+ *   otherwise       gumbel->n_samples and ->steps must equal tables->n_samples and ->steps, and alpha must be finite and >= 1:
+ *                   IREC_E_INVALID otherwise, nothing is launched and the outputs are untouched
+ * Grid rule, workspace and every other argument: as irec_gc_importance_encode_ws. */
+irec_status irec_gc_importance_encode_gumbel(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
+                                             const int32_t *block_dim, const int32_t *perm, const float *q_loc, const float *q_scale,
+                                             const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
+                                             float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
+                                             float *out_sample, void *workspace, size_t workspace_bytes,
+                                             const irec_gumbel_table *gumbel, void *hip_stream);
 /* Decode: K [n_blocks], indices [n_blocks, max_K] in encoder order, max(K, 1) entries per row.  A row with K < 0, K > max_K,
  * K > irec_max_partitions(ctx), an index outside [0, n_samples) or a dim without a table decodes to p_loc, as irec_beam_decode
  * promises; any block dim with a table is served. */

@@ -361,6 +361,18 @@ irec_status irec_tf_stateless_normal(int64_t seed0, int64_t seed1, int64_t count
   return IREC_OK;
 }
 
+// g[s] of stateless_gumbel_sample([S], seed + 1) (rec/coding/utils.py:9-12): -logf(-logf(z[s])), z = stateless_normal([S], [seed + 1,
+// seed + 2]) -- a NORMAL draw inside the double log, as the reference has it: NaN wherever z is outside (0, 1].  THE definition: the host
+// sampler (irec_importance_encode) and the table the kernels read (irec_gumbel_table_build) both call it, so both paths see the same bits.
+static inline float gumbel_element(TfStatelessNormalStream &gst, uint64_t s) { return -std::log(-std::log(gst.element(s))); }
+
+irec_status irec_tf_stateless_gumbel(int64_t seed, int64_t count, float *out) {
+  if (count < 0 || (count > 0 && !out)) return fail(IREC_E_INVALID, "irec_tf_stateless_gumbel: bad arguments");
+  TfStatelessNormalStream gst(seed, seed + 1);
+  for (int64_t e = 0; e < count; ++e) out[e] = gumbel_element(gst, (uint64_t)e);
+  return IREC_OK;
+}
+
 irec_status irec_importance_encode(const float *t_loc, const float *t_scale, const float *p_loc, const float *p_scale,
                                    int64_t n, double coding_bits, double alpha, int64_t seed, int64_t *out_index,
                                    float *out_sample) try {
@@ -378,9 +390,8 @@ irec_status irec_importance_encode(const float *t_loc, const float *t_scale, con
     ln_t[d] = half_log_2pi + std::log(ts[d]);
   }
   TfNormalStream st(seed);
-  // alpha < inf: Gumbel-max over alpha * w + g (:67-71), g = stateless_gumbel_sample([S], seed + 1) =
-  // -log(-log(stateless_normal([S], [seed + 1, seed + 2]))) (rec/coding/utils.py:9-12 -- a NORMAL draw inside the double
-  // log, as the reference has it: g is NaN wherever the draw is outside (0, 1]; tf.argmax never selects a NaN).
+  // alpha < inf: Gumbel-max over alpha * w + g (:67-71), g = stateless_gumbel_sample([S], seed + 1) (gumbel_element above: NaN wherever
+  // the draw is outside (0, 1]; tf.argmax never selects a NaN).
   const bool gumbel = !std::isinf(alpha);
   TfStatelessNormalStream gst(seed + 1, seed + 2);
   float best = -FLT_MAX;   // Eigen's ArgMaxTupleReducer: accumulator starts at (0, lowest()) and moves on a strict ">"
@@ -396,7 +407,7 @@ irec_status irec_importance_encode(const float *t_loc, const float *t_scale, con
       acc += (double)(lp_t - lp_p);
     }
     float w = (float)acc;
-    if (gumbel) w = (float)alpha * w + (-std::log(-std::log(gst.element((uint64_t)s))));
+    if (gumbel) w = (float)alpha * w + gumbel_element(gst, (uint64_t)s);
     if (w > best) { best = w; best_s = s; } // tf.argmax: first maximum; a NaN never compares greater
   }
   *out_index = best_s;
@@ -1573,6 +1584,45 @@ irec_status irec_normal_table_build(int64_t seed, int32_t n_samples, int32_t dim
   return IREC_OK;
 } catch (const std::exception &e) { return fail(IREC_E_INVALID, "irec_normal_table_build: %s", e.what()); }
 
+// The Gumbel perturbations of a call at finite alpha: out[j * S_pad + s] = g[s] of the step seed seed + j (gumbel_element), zero padded.
+size_t irec_gumbel_table_floats(int32_t n_samples, int32_t steps) {
+  if (n_samples < 1 || steps < 1 || steps > IREC_TABLE_STEPS_MAX) {
+    fail(IREC_E_INVALID, "irec_gumbel_table_floats: n_samples %d, steps %d out of range", n_samples, steps);
+    return 0;
+  }
+  const size_t n = (size_t)steps * round_up_sz((size_t)n_samples, IREC_NORMAL_TABLE_PAD);
+  if (n > (size_t)IREC_TABLE_BYTES_HARD / sizeof(float)) {
+    fail(IREC_E_INVALID, "irec_gumbel_table_floats: %d steps of %d samples need %zu bytes, more than IREC_TABLE_BYTES_HARD", steps, n_samples,
+         n * sizeof(float));
+    return 0;
+  }
+  return n;
+}
+
+irec_status irec_gumbel_table_build(int64_t seed, int32_t n_samples, int32_t steps, float *out, int32_t n_threads) try {
+  if (!irec_gumbel_table_floats(n_samples, steps)) return IREC_E_INVALID;
+  if (!out) return fail(IREC_E_INVALID, "irec_gumbel_table_build: null output");
+  const size_t S_pad = round_up_sz((size_t)n_samples, IREC_NORMAL_TABLE_PAD);
+  std::atomic<int64_t> next{0};    // work items: steps (a row is one stream)
+  auto work = [&]() {
+    for (int64_t j = next.fetch_add(1); j < steps; j = next.fetch_add(1)) {
+      TfStatelessNormalStream gst(seed + j + 1, seed + j + 2);
+      float *row = out + (size_t)j * S_pad;
+      for (size_t s = 0; s < S_pad; ++s) row[s] = s < (size_t)n_samples ? gumbel_element(gst, (uint64_t)s) : 0.0f;
+    }
+  };
+  int nt = n_threads > 0 ? n_threads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+  nt = (int)std::min<int64_t>(nt, steps);
+  std::vector<std::thread> pool;
+  pool.reserve((size_t)nt);
+  try {
+    for (int i = 1; i < nt; ++i) pool.emplace_back(work);
+  } catch (const std::exception &) {}   // a thread that could not be started: the ones that exist (and this one) do its share
+  work();
+  for (auto &t : pool) t.join();
+  return IREC_OK;
+} catch (const std::exception &e) { return fail(IREC_E_INVALID, "irec_gumbel_table_build: %s", e.what()); }
+
 static irec_status gc_fill(const char *who, irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
                            const int32_t *block_dim, const irec_normal_tables *tables, int32_t max_K, irec::GcArgs &A) {
   if (!ctx) return fail(IREC_E_INVALID, "%s: null context", who);
@@ -1613,9 +1663,17 @@ static irec_status gc_encode(const char *who, bool ws_entry, irec_context *ctx, 
                              const int32_t *block_pos, const int32_t *block_dim, const int32_t *perm, const float *q_loc,
                              const float *q_scale, const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
                              float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices, float *out_sample,
-                             void *workspace, size_t workspace_bytes, void *hip_stream) {
+                             void *workspace, size_t workspace_bytes, const irec_gumbel_table *gumbel, void *hip_stream) {
   irec::GcArgs G{};
   if (irec_status s = gc_fill(who, ctx, n_blocks, block_base, block_pos, block_dim, tables, max_K, G)) return s;
+  if (gumbel) {   // finite alpha: one perturbation per (step, sample) of the normal tables
+    if (!gumbel->table) return fail(IREC_E_INVALID, "%s: gumbel without a table", who);
+    if (gumbel->n_samples != tables->n_samples || gumbel->steps != tables->steps)
+      return fail(IREC_E_INVALID, "%s: the Gumbel table holds %d samples x %d steps, the normal tables %d x %d", who, gumbel->n_samples,
+                  gumbel->steps, tables->n_samples, tables->steps);
+    if (!(gumbel->alpha >= 1.0f) || std::isinf(gumbel->alpha))   // importance_sampling.py:33-34; alpha = inf: gumbel == NULL
+      return fail(IREC_E_INVALID, "%s: Alpha must be in the range [1, inf), but %g was given!", who, (double)gumbel->alpha);
+  }
   if (!(kl_per_partition > 0.0f)) return fail(IREC_E_INVALID, "%s: kl_per_partition must be positive", who);
   if (n_blocks == 0) return IREC_OK;
   if (!q_loc || !q_scale || !p_loc || !p_scale || !out_K || !out_indices || !out_sample)
@@ -1639,10 +1697,13 @@ static irec_status gc_encode(const char *who, bool ws_entry, irec_context *ctx, 
   G.out_K = out_K; G.out_indices = out_indices; G.out_sample = out_sample;
   if (wide) {
     G.slab = static_cast<float *>(workspace); G.slab_dim = (int32_t)gc_wide_slab_dim(max_dim);
-    HIP_TRY(irec::launch_gc_importance_encode_wide(G, gc_wide_grid(ctx, n_blocks), (hipStream_t)hip_stream));
+    if (gumbel) HIP_TRY(irec::launch_gc_gumbel_encode_wide(G, gumbel->table, gumbel->alpha, gc_wide_grid(ctx, n_blocks), (hipStream_t)hip_stream));
+    else HIP_TRY(irec::launch_gc_importance_encode_wide(G, gc_wide_grid(ctx, n_blocks), (hipStream_t)hip_stream));
     return IREC_OK;
   }
-  HIP_TRY(irec::launch_gc_importance_encode(G, (int)std::min<int64_t>(n_blocks, 16LL * ctx->n_cu), (hipStream_t)hip_stream));
+  const int grid = (int)std::min<int64_t>(n_blocks, 16LL * ctx->n_cu);
+  if (gumbel) HIP_TRY(irec::launch_gc_gumbel_encode(G, gumbel->table, gumbel->alpha, grid, (hipStream_t)hip_stream));
+  else HIP_TRY(irec::launch_gc_importance_encode(G, grid, (hipStream_t)hip_stream));
   return IREC_OK;
 }
 
@@ -1652,7 +1713,7 @@ irec_status irec_gc_importance_encode(irec_context *ctx, int64_t n_blocks, const
                                       float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
                                       float *out_sample, void *hip_stream) {
   return gc_encode("irec_gc_importance_encode", false, ctx, n_blocks, block_base, block_pos, block_dim, perm, q_loc, q_scale, p_loc,
-                   p_scale, tables, kl_per_partition, max_K, out_K, out_indices, out_sample, nullptr, 0, hip_stream);
+                   p_scale, tables, kl_per_partition, max_K, out_K, out_indices, out_sample, nullptr, 0, nullptr, hip_stream);
 }
 
 irec_status irec_gc_importance_encode_ws(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
@@ -1661,7 +1722,17 @@ irec_status irec_gc_importance_encode_ws(irec_context *ctx, int64_t n_blocks, co
                                          float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
                                          float *out_sample, void *workspace, size_t workspace_bytes, void *hip_stream) {
   return gc_encode("irec_gc_importance_encode_ws", true, ctx, n_blocks, block_base, block_pos, block_dim, perm, q_loc, q_scale, p_loc,
-                   p_scale, tables, kl_per_partition, max_K, out_K, out_indices, out_sample, workspace, workspace_bytes, hip_stream);
+                   p_scale, tables, kl_per_partition, max_K, out_K, out_indices, out_sample, workspace, workspace_bytes, nullptr, hip_stream);
+}
+
+irec_status irec_gc_importance_encode_gumbel(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,
+                                             const int32_t *block_dim, const int32_t *perm, const float *q_loc, const float *q_scale,
+                                             const float *p_loc, const float *p_scale, const irec_normal_tables *tables,
+                                             float kl_per_partition, int32_t max_K, int32_t *out_K, int32_t *out_indices,
+                                             float *out_sample, void *workspace, size_t workspace_bytes,
+                                             const irec_gumbel_table *gumbel, void *hip_stream) {
+  return gc_encode("irec_gc_importance_encode_gumbel", true, ctx, n_blocks, block_base, block_pos, block_dim, perm, q_loc, q_scale, p_loc,
+                   p_scale, tables, kl_per_partition, max_K, out_K, out_indices, out_sample, workspace, workspace_bytes, gumbel, hip_stream);
 }
 
 irec_status irec_gc_importance_decode(irec_context *ctx, int64_t n_blocks, const int64_t *block_base, const int32_t *block_pos,

@@ -70,6 +70,9 @@ irec_status irec_tf_random_normal(int64_t seed, int64_t count, float *out);
 /* out[e] = element e of tf.random.stateless_normal([count], seed=[seed0, seed1]) -- the draw inside
  * stateless_gumbel_sample (rec/coding/utils.py:9-12).  Host memory; test hook. */
 irec_status irec_tf_stateless_normal(int64_t seed0, int64_t seed1, int64_t count, float *out);
+/* out[e] = element e of stateless_gumbel_sample([count], seed) (rec/coding/utils.py:9-12): -logf(-logf(z[e])), z the draw above with
+ * [seed, seed + 1] -- the one definition that irec_importance_encode and irec_gumbel_table_build evaluate.  Host memory. */
+irec_status irec_tf_stateless_gumbel(int64_t seed, int64_t count, float *out);
 
 /* The ratio fitter (irec_fit.hip).  irec_test_fit_chunk: launches irec_fit_aux_ratios enqueues between two reads of its `done` word
  * (<= 0: the default, 64); returns the previous value.  Results never depend on it.  irec_test_det_exp: out[i] = det_exp(in[i]), the

@@ -216,7 +216,7 @@ hipError_t launch_shim_cat_elu(const float *y, const float *latent, float *out, 
                                const float *by, hipStream_t st);
 hipError_t launch_shim_residual_elu(const float *inp, const float *t, float alpha, float *out, float *out_elu, int64_t count,
                                     const float *bt, int C, int HW, hipStream_t st);
-// the sequential importance coder (irec_gc.hip): GaussianCoder.encode_block / decode_block over an ImportanceSampler, alpha = inf
+// the sequential importance coder (irec_gc.hip): GaussianCoder.encode_block / decode_block over an ImportanceSampler
 constexpr int GC_MAX_DIM = 1024;    // dims of a block the encoder keeps in LDS; wider blocks: the wide kernel over a slab of the workspace
 constexpr int GC_WIDE_THREADS = 1024;   // lanes of the wide kernel's workgroup = dims of a chunk
 struct GcArgs {
@@ -236,6 +236,9 @@ int gc_encode_threads(int S);
 hipError_t launch_gc_importance_encode(const GcArgs &A, int grid, hipStream_t st);
 hipError_t launch_gc_importance_encode_wide(const GcArgs &A, int grid, hipStream_t st);
 hipError_t launch_gc_importance_decode(const GcArgs &A, int grid, hipStream_t st);
+// finite alpha: the same encoders over alpha * w + gum[step * S_pad + s] (irec_gumbel_table_build)
+hipError_t launch_gc_gumbel_encode(const GcArgs &A, const float *gum, float alpha, int grid, hipStream_t st);
+hipError_t launch_gc_gumbel_encode_wide(const GcArgs &A, const float *gum, float alpha, int grid, hipStream_t st);
 hipError_t launch_dec_sqrt_test(unsigned long long *out, hipStream_t st);
 hipError_t launch_uniform_int(int64_t seed, int64_t n, int32_t *out, hipStream_t st);
 hipError_t launch_select_test(const float *scores, int N, int Bnew, int Bcur, uint32_t *keys, int32_t *sel, bool quick, hipStream_t st);

@@ -51,6 +51,11 @@ class IrecNormalTables(ctypes.Structure):
     _fields_ = [("table", ctypes.c_void_p * 4), ("dim", ctypes.c_int32 * 4), ("n_samples", ctypes.c_int32), ("steps", ctypes.c_int32)]
 
 
+class IrecGumbelTable(ctypes.Structure):
+    """irec_gumbel_table of include/irec.h: the device table of Gumbel perturbations of one call at finite alpha."""
+    _fields_ = [("table", ctypes.c_void_p), ("n_samples", ctypes.c_int32), ("steps", ctypes.c_int32), ("alpha", ctypes.c_float)]
+
+
 class IrecFitParams(ctypes.Structure):
     """irec_fit_params of include/irec.h: the ratio fitter's parameters."""
     _fields_ = [("kl_per_partition", ctypes.c_float), ("relative_tolerance", ctypes.c_double), ("learning_rate", ctypes.c_double),
@@ -97,6 +102,7 @@ SIGNATURES = {
     "irec_importance_encode": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _i64,
                                               ctypes.POINTER(_i64), _vp]),
     "irec_tf_stateless_normal": (ctypes.c_int, [_i64, _i64, _i64, _vp]),
+    "irec_tf_stateless_gumbel": (ctypes.c_int, [_i64, _i64, _vp]),
     "irec_importance_decode": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
     "irec_importance_n_samples": (_i64, [ctypes.c_double]),
     "irec_tf_random_normal": (ctypes.c_int, [_i64, _i64, _vp]),
@@ -129,6 +135,11 @@ SIGNATURES = {
     "irec_gc_encode_workspace_bytes": (ctypes.c_size_t, [_vp, _i64, _i32]),
     "irec_gc_importance_encode_ws": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables),
                                                     ctypes.c_float, _i32, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_gumbel_table_floats": (ctypes.c_size_t, [_i32, _i32]),
+    "irec_gumbel_table_build": (ctypes.c_int, [_i64, _i32, _i32, _vp, _i32]),
+    "irec_gc_importance_encode_gumbel": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables),
+                                                        ctypes.c_float, _i32, _vp, _vp, _vp, _vp, ctypes.c_size_t,
+                                                        ctypes.POINTER(IrecGumbelTable), _vp]),
     "irec_gc_importance_decode": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables), _i32,
                                                  _vp, _vp, _vp, _vp]),
     "irec_fit_workspace_bytes": (ctypes.c_size_t, [_i64, _i32]),

@@ -4,7 +4,7 @@ The block split/merge bookkeeping, the auxiliary-variance ratios -- extrapolated
 as data, or fitted here by update_auxiliary_variance_ratios (coder.py:233-410: the kernels of csrc/irec_fit.hip for GPU tensors,
 their host twin for CPU tensors) -- and the sampler-driven GaussianCoder.encode / decode / encode_block / decode_block
 (coder.py:412-587): the reference's loop on the host for any Sampler object, the gfx950 kernels of csrc/irec_gc.hip for the
-ImportanceSampler at alpha = inf on GPU tensors -- blocks of any dim, block_size=None included; the size of the normal proposal
+ImportanceSampler (alpha = inf, or the Gumbel-max of a finite alpha >= 1) on GPU tensors -- blocks of any dim, block_size=None included; the size of the normal proposal
 tables (IREC_TABLE_BYTES_HARD, IREC_TABLE_STEPS_MAX) is the remaining limit.  The update_sampler branch is out of scope.
 """
 import abc
@@ -274,7 +274,7 @@ class GaussianCoder(Coder):
         self._ratio_engine = None    # the next encode builds a context over the new table
 
     # ---- the sequential coder (coder.py:412-587): any Sampler on the host, the ImportanceSampler of the reference's models
-    #      (alpha = inf) in the gfx950 kernels behind irec_gc_importance_encode / _decode ---------------------------------
+    #      (any alpha >= 1) in the gfx950 kernels behind irec_gc_importance_encode / _decode ---------------------------------
     def get_codelength(self, indicies):
         """coder.py:586-587."""
         return sum([self.sampler.get_codelength(i) for i in indicies])
@@ -284,14 +284,21 @@ class GaussianCoder(Coder):
         return int(self.table_steps) if self.table_steps else _lib.IREC_TABLE_STEPS_DEFAULT
 
     def _on_device(self, loc, block_size):
-        """The kernels take the call: the reference's own ImportanceSampler at alpha = inf, tensors on the GPU, blocks of any dim
-        (the size of the proposal tables is the remaining limit: NormalTableTooLarge sends a call to the host loop).  Everything
-        else runs the reference's loop on the host."""
+        """The kernels take the call: the reference's own ImportanceSampler (any alpha: the encoders check theirs first,
+        `_check_alpha`; a decoder never looks at it, importance_sampling.py:82-103), tensors on the GPU, blocks of any dim (the size of
+        the proposal tables is the remaining limit: NormalTableTooLarge sends a call to the host loop).  Everything else runs the
+        reference's loop on the host."""
         from .samplers import ImportanceSampler
-        if type(self.sampler) is not ImportanceSampler or not (self.sampler.alpha == np.inf):
+        if type(self.sampler) is not ImportanceSampler:
             return False
         t = torch.as_tensor(loc)
         return t.device.type == "cuda" and t.ndim >= 2 and t.shape[0] >= 1 and t[0].numel() >= 1
+
+    def _check_alpha(self):
+        """alpha < 1 or NaN: the reference's text (importance_sampling.py:33-34), before any device work."""
+        from .samplers import ImportanceSampler
+        if type(self.sampler) is ImportanceSampler:
+            self.sampler._check_alpha()
 
     def _engine_for(self, tensor):
         t = torch.as_tensor(tensor)
@@ -313,6 +320,7 @@ class GaussianCoder(Coder):
         """Asynchronous core of the device path: one block-KL and one encode launch for all blocks of all tensors (leading dim
         = independent latent tensors); returns a `PendingCode`, nothing is copied to the host."""
         from .beam_search_coder import PendingCode
+        self._check_alpha()
         src = torch.as_tensor(q_loc)
         shapes = {tuple(torch.as_tensor(t).shape) for t in (q_loc, q_scale, p_loc, p_scale)}
         if len(shapes) != 1:
@@ -324,7 +332,8 @@ class GaussianCoder(Coder):
         max_K = max(1, min(self._max_K_hint if max_K is None else int(max_K), self.DEVICE_MAX_K))
         self.last_path = "device"
         steps = max(int(table_steps) if table_steps else self.table_window(), max_K)
-        K, idx, sample = eng.gc_encode_blocks(lay, ql, qs, pl, ps, seed, self.kl_per_partition, self.sampler.n_samples(), max_K, steps)
+        K, idx, sample = eng.gc_encode_blocks(lay, ql, qs, pl, ps, seed, self.kl_per_partition, self.sampler.n_samples(), max_K, steps,
+                                              alpha=float(self.sampler.alpha))
         pending = PendingCode(self, lay, K, idx, sample.reshape(src.shape).to(src.device), max_K)
         pending.min_indices = 1
         return pending
@@ -429,7 +438,7 @@ class GaussianCoder(Coder):
         a fresh one, left in `last_rows_status` (device).  Needs the device path (`_on_device`)."""
         self._check_sampler()
         if not self._on_device(p_loc, block_size):
-            raise CodingError("decode_tensors_device needs the device path: an ImportanceSampler with alpha = inf, tensors on the GPU, "
+            raise CodingError("decode_tensors_device needs the device path: an ImportanceSampler (any alpha), tensors on the GPU, "
                               "and proposal tables that fit (IREC_TABLE_BYTES_HARD, IREC_TABLE_STEPS_MAX)")
         src = torch.as_tensor(p_loc)
         eng = self._engine_for(src)
@@ -512,6 +521,7 @@ class GaussianCoder(Coder):
         if target_dist.loc.shape[0] != 1:
             raise CodingError("For encoding, batch size must be 1.")
         self._check_sampler(update_sampler)
+        self._check_alpha()
         if self._on_device(target_dist.loc, None):
             try:
                 idx, sample = self.encode_tensors(target_dist.loc, target_dist.scale, coding_dist.loc, coding_dist.scale, seed, None)
@@ -540,6 +550,7 @@ class GaussianCoder(Coder):
         self._check_sampler(kwargs.get("update_sampler", False))
         if target_dist.loc.shape[0] != 1 and not batched:
             raise CodingError("For encoding, batch size must be 1.")
+        self._check_alpha()
         if self._on_device(target_dist.loc, self.block_size):
             args = (target_dist.loc, target_dist.scale, coding_dist.loc, coding_dist.scale, seed, self.block_size)
             try:
@@ -553,7 +564,7 @@ class GaussianCoder(Coder):
             except NormalTableTooLarge:
                 pass
         if defer:
-            raise CodingError("defer=True needs the device path: an ImportanceSampler with alpha = inf, tensors on the GPU, "
+            raise CodingError("defer=True needs the device path: an ImportanceSampler with alpha >= 1, tensors on the GPU, "
                               "and proposal tables that fit (IREC_TABLE_BYTES_HARD, IREC_TABLE_STEPS_MAX)")
         if batched:
             loc, scale = torch.as_tensor(target_dist.loc), torch.as_tensor(target_dist.scale)

@@ -4,7 +4,8 @@
 on the CPU -- e^KL standard-normal proposals from TensorFlow's global Philox stream, an argmax over their importance
 weights (importance_sampling.py:9-103) -- and so does this mirror: it calls the host-side entry points
 `irec_importance_encode / _decode` of libirec_hip.so (include/irec.h), which need no GPU.  It is not on the
-`sampler='beam_search'` hot path and no device kernel is involved.  Both branches are built: `alpha = inf` (the
+`sampler='beam_search'` hot path and no device kernel is involved in these stand-alone calls (GaussianCoder codes GPU tensors
+with the kernels of csrc/irec_gc.hip at either alpha, without going through coded_sample).  Both branches are built: `alpha = inf` (the
 reference's default, the setting its models use: resnet_vae.py:126-131) takes the argmax of the importance weights,
 `1 <= alpha < inf` the Gumbel-max of importance_sampling.py:67-71 over `stateless_gumbel_sample`
 (rec/coding/utils.py:9-12).  The rejection sampler is out of scope.

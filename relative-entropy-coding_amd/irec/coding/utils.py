@@ -8,12 +8,12 @@ from ..errors import CodingError  # noqa: F401
 
 def stateless_gumbel_sample(shape, seed):
     """-log(-log(tf.random.stateless_normal(shape, [seed, seed + 1]))) -- rec/coding/utils.py:9-12, as written (a NORMAL
-    draw inside the double log: NaN wherever it falls outside (0, 1]).  Host numpy float32 of the given shape; the
-    importance sampler's Gumbel-max branch (irec_importance_encode, alpha < inf) evaluates the same stream in C++."""
+    draw inside the double log: NaN wherever it falls outside (0, 1]).  Host numpy float32 of the given shape, evaluated by
+    the library's one definition of g (libm's logf twice: irec_tf_stateless_gumbel) -- the bits that the importance sampler's
+    Gumbel-max branch (irec_importance_encode, alpha < inf) adds to the weights and that irec_gumbel_table_build hands to the
+    kernels.  (numpy's vectorised float32 log is a different function: up to 2 ulp away from logf on this stream.)"""
     from .. import _lib
     n = int(np.prod(shape))
-    z = np.empty(n, dtype=np.float32)
-    _lib.check(_lib.load().irec_tf_stateless_normal(int(seed), int(seed) + 1, n, z.ctypes.data_as(ctypes.c_void_p)),
-               "irec_tf_stateless_normal")
-    with np.errstate(invalid="ignore", divide="ignore"):
-        return (-np.log(-np.log(z))).astype(np.float32).reshape(shape)
+    g = np.empty(n, dtype=np.float32)
+    _lib.check(_lib.load().irec_tf_stateless_gumbel(int(seed), n, g.ctypes.data_as(ctypes.c_void_p)), "irec_tf_stateless_gumbel")
+    return g.reshape(shape)

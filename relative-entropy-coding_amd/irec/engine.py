@@ -60,6 +60,22 @@ def build_normal_table(seed, n_samples, dim, steps, n_threads=0):
     return out
 
 
+def build_gumbel_table(seed, n_samples, steps, n_threads=0):
+    """irec_gumbel_table_build (host): float32 [steps, S_pad], entry [j, s] = element s of stateless_gumbel_sample([n_samples],
+    seed + j + 1) (rec/coding/utils.py:9-12: NaN wherever the normal draw inside the double log is outside (0, 1]); S_pad as for the
+    normal tables, zero padded."""
+    lib = _lib.load()
+    n = lib.irec_gumbel_table_floats(int(n_samples), int(steps))
+    if not n:
+        raise NormalTableTooLarge("irec_gumbel_table_floats: " + lib.irec_last_error().decode())
+    s_pad = -(-int(n_samples) // _lib.IREC_NORMAL_TABLE_PAD) * _lib.IREC_NORMAL_TABLE_PAD
+    out = np.empty((int(steps), s_pad), dtype=np.float32)
+    assert out.size == n
+    _lib.check(lib.irec_gumbel_table_build(int(seed), int(n_samples), int(steps), out.ctypes.data_as(ctypes.c_void_p), int(n_threads)),
+               "irec_gumbel_table_build")
+    return out
+
+
 class FitError(_lib.IrecLibraryError):
     """The ratio fit cannot run on these rows (an infinite KL, more partitions than the build supports, a table that does not fit)."""
 
@@ -257,6 +273,7 @@ class Engine:
         self._dec_ws = {}  # decode scratch (proposal tables of a call) per HIP stream
         self._normal_tables = {}   # (seed, S, dim, steps) -> device table of the sequential importance coder
         self._normal_tables_lock = threading.Lock()
+        self._gumbel_tables = {}   # (seed, S, steps) -> device table of Gumbel perturbations (finite alpha); same lock
 
     def __del__(self):
         try:
@@ -546,18 +563,39 @@ class Engine:
         c.n_samples, c.steps = int(n_samples), int(steps)
         return c, tabs
 
+    def gumbel_table(self, seed, n_samples, steps, alpha):
+        """irec_gumbel_table of a call at finite alpha: built on the host, uploaded and cached per (seed, S, steps) beside the normal
+        tables (same lock; steps x S_pad floats each, emptied wholesale beyond NORMAL_TABLE_CACHE_BYTES of their own)."""
+        key = (int(seed), int(n_samples), int(steps))
+        with self._normal_tables_lock:
+            t = self._gumbel_tables.get(key)
+            if t is None:
+                host = torch.from_numpy(build_gumbel_table(seed, n_samples, steps))
+                if sum(v.numel() * 4 for v in self._gumbel_tables.values()) + host.numel() * 4 > self.NORMAL_TABLE_CACHE_BYTES:
+                    self._gumbel_tables.clear()
+                t = host.to(self.device)
+                self._gumbel_tables[key] = t
+        c = _lib.IrecGumbelTable()
+        c.table, c.n_samples, c.steps, c.alpha = t.data_ptr(), int(n_samples), int(steps), float(alpha)
+        return c, t
+
     def gc_encode_blocks(self, lay, q_loc, q_scale, p_loc, p_scale, seed, kl_per_partition, n_samples, max_K, steps=None,
-                         order_by_K=True):
-        """Asynchronous.  GaussianCoder.encode over an ImportanceSampler (alpha = inf) on every block of `lay`: device tensors
+                         order_by_K=True, alpha=np.inf):
+        """Asynchronous.  GaussianCoder.encode over an ImportanceSampler on every block of `lay`: device tensors
         (K [n_blocks], indices [n_blocks, max_K] -- max(K, 1) entries of a row count --, sample [like q_loc]), rows in `lay` order.
         order_by_K: the blocks go to the kernel longest first (a workgroup codes one block at a time).  Blocks of any dim whose
-        tables fit (NormalTableTooLarge otherwise): a call with a block of more than 1024 dims runs the wide kernel over a workspace."""
+        tables fit (NormalTableTooLarge otherwise): a call with a block of more than 1024 dims runs the wide kernel over a workspace.
+        alpha: inf takes the greatest importance weight (irec_gc_importance_encode_ws); a finite alpha >= 1 the Gumbel-max over
+        alpha * w + g (irec_gc_importance_encode_gumbel over the call's Gumbel table)."""
+        if not float(alpha) >= 1.0:
+            raise _lib.IrecLibraryError(f"Alpha must be in the range [1, inf), but {alpha} was given!")
         for t in (q_loc, q_scale, p_loc, p_scale):
             assert t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device
             assert t.numel() == lay.n_tensors * lay.n
         max_K = max(1, int(max_K))
         steps = max_K if steps is None else max(int(steps), max_K)
         tables, keep = self.normal_tables(seed, n_samples, lay.distinct_dims, steps)
+        gumbel, keep_g = self.gumbel_table(seed, n_samples, steps, alpha) if np.isfinite(alpha) else (None, None)
         base, pos, dim, order = lay.block_base, lay.block_pos, lay.block_dim, None
         if order_by_K and lay.n_blocks > 1:
             _, K0 = self.block_kl(self.params(kl_per_partition, n_samples, 1), lay, q_loc, q_scale, p_loc, p_scale)
@@ -569,12 +607,15 @@ class Engine:
         # blocks of more than 1024 dims keep their state in slabs of a workspace (csrc/irec_gc.hip, the wide kernel); 0 bytes otherwise
         ws_bytes = self.lib.irec_gc_encode_workspace_bytes(self.ctx, lay.n_blocks, max(int(d) for d in lay.distinct_dims))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device) if ws_bytes else None
-        _lib.check(self.lib.irec_gc_importance_encode_ws(self.ctx, lay.n_blocks, _ptr(base), _ptr(pos), _ptr(dim), _ptr(lay.perm),
-                                                         _ptr(q_loc), _ptr(q_scale), _ptr(p_loc), _ptr(p_scale), ctypes.byref(tables),
-                                                         float(np.float32(kl_per_partition)), max_K, _ptr(out_K), _ptr(out_idx),
-                                                         _ptr(sample), _ptr(ws), ws_bytes, self._stream()),
-                   "irec_gc_importance_encode_ws")
-        del keep, ws
+        args = (self.ctx, lay.n_blocks, _ptr(base), _ptr(pos), _ptr(dim), _ptr(lay.perm), _ptr(q_loc), _ptr(q_scale), _ptr(p_loc),
+                _ptr(p_scale), ctypes.byref(tables), float(np.float32(kl_per_partition)), max_K, _ptr(out_K), _ptr(out_idx), _ptr(sample),
+                _ptr(ws), ws_bytes)
+        if gumbel is None:
+            _lib.check(self.lib.irec_gc_importance_encode_ws(*args, self._stream()), "irec_gc_importance_encode_ws")
+        else:
+            _lib.check(self.lib.irec_gc_importance_encode_gumbel(*args, ctypes.byref(gumbel), self._stream()),
+                       "irec_gc_importance_encode_gumbel")
+        del keep, keep_g, ws
         if order is not None:
             K2, idx2 = torch.empty_like(out_K), torch.empty_like(out_idx)
             K2[order] = out_K

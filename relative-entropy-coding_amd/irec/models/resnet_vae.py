@@ -434,8 +434,10 @@ class BidirectionalResNetVAE(nn.Module):
             except (MorePartitionsNeeded, SplitNotResident):
                 continue
             coder = self.residual_blocks[0].coder
+            # the header's max_index word: the samples a step chooses among (the sequential coder's are its sampler's)
+            n_samples = coder.sampler.n_samples() if coder.sampler is not None else coder.n_samples
             blob, offsets = encode_files_device(seed, (height, width, 3), coder.block_size if block_size is None else block_size, K, idx,
-                                                max_index=coder.n_samples)
+                                                max_index=n_samples)
             return ((blob, offsets, reconstruction), (K, idx)) if return_pendings else (blob, offsets, reconstruction)
         raise MorePartitionsNeeded(max(b.coder._max_K_hint for b in self.residual_blocks) + 1)
 
