@@ -538,6 +538,48 @@ irec_status irec_decode_rows_status(int64_t n_groups, int32_t blocks_per_group, 
                                     int32_t min_K, int32_t k_limit, int32_t n_samples, int32_t *status /* [n_groups] */,
                                     void *hip_stream);
 
+/* The .res container (csrc/irec_res.hip over csrc/irec_res_core.h): the pixels of an image, arithmetic-coded under the model's
+ * discretized-logistic likelihood given its reconstruction, so that .rec + .res decode to exactly the uint8 image.  .rec files are
+ * untouched by it.  pixels [n][channels][height][width] uint8, loc the same shape in float32 (the clamped reconstruction), scale the
+ * call's one likelihood scale in [2^-24, 2^24].  A pixel's model is a function of the integer rint(loc * 4096) and of scale alone
+ * (INTEGRATION.md has the counts and the file layout).  An image is channels * height * width symbols cut into streams of stream_len
+ * (1 .. 4096), n_streams = ceil(symbols / stream_len), one lane per stream.
+ * The device entry points follow irec_rec_encode_files_device: device pointers, asynchronous on hip_stream, no allocation,
+ * synchronisation or copy inside; offsets [n_images + 1] and status [n_images] are always written; nothing is written into out when
+ * offsets[n_images] > cap; a file with a nonzero status has no bytes; the reader leaves no file's [offsets[i], offsets[i + 1]) and an
+ * image with a nonzero status has its pixels zeroed.  The host forms run the same core over host memory on n_threads threads
+ * (0 = one per core, at most 32) and give the same bytes, pixels and statuses.
+ * irec_res_model_counts: the 257 cumulative counts C(0 .. 256) of one (m, scale); irec_res_symbol_counts: count[e] = C(x + 1) - C(x) of
+ * every pixel (its ideal length is -log2(count / 65536)), 0 where loc is not finite. */
+typedef enum {
+  IREC_RES_OK = 0,
+  IREC_RES_E_SCALE = 1,             /* encode: the scale is not finite, not positive or outside [2^-24, 2^24]              */
+  IREC_RES_E_LOC = 2,               /* encode: a loc that is not finite                                                   */
+  IREC_RES_E_TRUNCATED_HEADER = 3,  /* decode: fewer bytes than the header and its stream lengths                         */
+  IREC_RES_E_MAGIC = 4,             /* decode: not the magic word or not this version                                     */
+  IREC_RES_E_SHAPE = 5,             /* decode: height, width, channels or stream_len differ from the call's               */
+  IREC_RES_E_SCALE_WORD = 6,        /* decode: the file's scale word differs from the call's                              */
+  IREC_RES_E_TRUNCATED_STREAMS = 7, /* decode: the streams run past the file                                              */
+  IREC_RES_E_CORRUPT = 8,           /* decode: a stream with target < 0, width <= 0 or its shift budget spent             */
+  IREC_RES_E_CHECKSUM = 9           /* decode: the pixels do not sum to the header's checksum (another loc, damaged bits) */
+} irec_res_status;
+size_t irec_res_device_workspace_bytes(int32_t n_images, int64_t n_streams);
+irec_status irec_res_encode_files_device(const uint8_t *pixels, const float *loc, float scale, int32_t n_images, uint32_t height,
+                                         uint32_t width, uint32_t channels, uint32_t stream_len, uint8_t *out, int64_t cap,
+                                         int64_t *offsets /*[n_images + 1]*/, int32_t *status /*[n_images]*/, void *workspace,
+                                         size_t workspace_bytes, void *hip_stream);
+irec_status irec_res_decode_files_device(const uint8_t *bytes, const int64_t *offsets, const float *loc, float scale, int32_t n_images,
+                                         uint32_t height, uint32_t width, uint32_t channels, uint32_t stream_len, uint8_t *pixels_out,
+                                         int32_t *status, void *workspace, size_t workspace_bytes, void *hip_stream);
+irec_status irec_res_encode_files(const uint8_t *pixels, const float *loc, float scale, int32_t n_images, uint32_t height, uint32_t width,
+                                  uint32_t channels, uint32_t stream_len, uint8_t *out, int64_t cap, int64_t *offsets, int32_t *status,
+                                  int32_t n_threads);
+irec_status irec_res_decode_files(const uint8_t *bytes, const int64_t *offsets, const float *loc, float scale, int32_t n_images,
+                                  uint32_t height, uint32_t width, uint32_t channels, uint32_t stream_len, uint8_t *pixels_out,
+                                  int32_t *status, int32_t n_threads);
+irec_status irec_res_model_counts(int32_t m, float scale, uint32_t *cumulative /*[257]*/);
+irec_status irec_res_symbol_counts(const uint8_t *pixels, const float *loc, float scale, int64_t n, uint32_t *count /*[n]*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,15 @@ SIGNATURES = {
     "irec_rec_decode_files_device": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "irec_rec_test_core_encode_files": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "irec_rec_test_core_decode_files": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "irec_res_device_workspace_bytes": (ctypes.c_size_t, [_i32, _i64]),
+    "irec_res_encode_files_device": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _i32] + [ctypes.c_uint32] * 4 + [_vp, _i64, _vp, _vp, _vp,
+                                                    ctypes.c_size_t, _vp]),
+    "irec_res_decode_files_device": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _i32] + [ctypes.c_uint32] * 4 + [_vp, _vp, _vp,
+                                                    ctypes.c_size_t, _vp]),
+    "irec_res_encode_files": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _i32] + [ctypes.c_uint32] * 4 + [_vp, _i64, _vp, _vp, _i32]),
+    "irec_res_decode_files": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _i32] + [ctypes.c_uint32] * 4 + [_vp, _vp, _i32]),
+    "irec_res_model_counts": (ctypes.c_int, [_i32, ctypes.c_float, _vp]),
+    "irec_res_symbol_counts": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _i64, _vp]),
     "irec_decode_rows_status": (ctypes.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "irec_test_rows_status_host": (ctypes.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "irec_device_uniform_int": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),

@@ -8,9 +8,10 @@ image (:367,380-384) -- with two changes the MI355X path is built around:
   * image i belongs to rank i mod G (irec/sharding.py); the per-image bits are gathered once at the end with the path's
     only collective (RCCL over xGMI on the GPU box, gloo in the CPU tests).
 
-No dataset or checkpoint exists in the reference tree: the caller supplies images and a model; the shim
-models have no likelihood head, so "bpd" here is the CODE's share, file bits / (pixels * channels), not the reference's
-code + residual figure.
+No dataset or checkpoint exists in the reference tree: the caller supplies images and a model.  By default
+"bpd" is the CODE's share, file bits / (pixels * channels).  lossless=True adds the residual as real bytes -- NAME.res beside
+NAME.rec, the pixels arithmetic-coded under the model's discretized-logistic likelihood given the reconstruction
+(model.compress_lossless) -- and with it the reference's code + residual figures (:381-384) and the image itself, exactly.
 """
 import os
 import time
@@ -21,7 +22,7 @@ import torch
 from . import sharding
 from .coding import CodingError
 from .io import decode_files, decode_files_device, encode_files, read_compressed_code, rec_header_words, write_compressed_code
-from .models.resnet_vae import status_text
+from .models.resnet_vae import STATUS_RESIDUAL, status_text
 
 
 def _host_leg(chunk_shape, names, seed, block_size, out_dir, S, K, idx, t_compress):
@@ -84,19 +85,71 @@ def _device_leg(model, chunk, names, seed, block_size, out_dir, S):
             for i in range(n)]
 
 
-def compress_images(model, images, names, seed, block_size, out_dir, batch=None, packed=True, rec_on_device=False):
+def _lossless_leg(model, chunk, names, seed, block_size, out_dir, S, stream_len):
+    """_device_leg for uint8 images with the residual: model.compress_lossless, NAME.rec and NAME.res written, both read back and
+    decoded on the device (model.decompress_lossless, one read-back), the pixels compared there.  The rows carry _device_leg's keys
+    (the code's share) and comp_residual (the .res file's bits), comp_lossless_bpp and comp_bpd ((rec + res bits) per pixel and per
+    dimension: compression_performance.py:381-384 with bits that were written), residual_model_bits (the ideal bits of the integer
+    model), pixels_recovered."""
+    from .io.residual import residual_model_bits
+    n, _, h, w = chunk.shape
+    t0 = time.perf_counter()
+    (blob, off, res_blob, res_off, rec), (K, _) = model.compress_lossless(chunk, seed=seed, stream_len=stream_len, block_size=block_size,
+                                                                           return_pendings=True)
+    t_compress = time.perf_counter() - t0
+    t1 = time.perf_counter()
+    backs = []
+    for ext, b, o in ((".rec", blob, off), (".res", res_blob, res_off)):
+        mv, oh = memoryview(b.cpu().numpy()), o.cpu().numpy()
+        paths = [os.path.join(out_dir, f"{nm}{ext}") for nm in names]
+        for i, path in enumerate(paths):
+            with open(path, "wb") as fh:
+                fh.write(mv[oh[i]:oh[i + 1]])
+        backs.append([open(path, "rb").read() for path in paths])
+    sizes = [np.array([len(b) for b in back], dtype=np.int64) for back in backs]
+    offs = [np.concatenate([[0], np.cumsum(sz)]) for sz in sizes]
+    blobs = [torch.from_numpy(np.frombuffer(b"".join(back), dtype=np.uint8).copy()).to(chunk.device) for back in backs]
+    pixels, status = model.decompress_lossless(blobs[0], offs[0], blobs[1], offs[1], seed, tuple(chunk.shape), max_K=max(int(K.max()), 1),
+                                               strict=False, stream_len=stream_len)
+    same = ((pixels == chunk).reshape(n, -1).all(dim=1)).cpu().numpy() & (status == 0)
+    ideal = residual_model_bits(chunk, rec, model.likelihood_scale())
+    n_idx = K.sum(dim=(1, 2)).cpu().numpy()
+    t_host = (time.perf_counter() - t1) / n
+    rows = []
+    for i in range(n):
+        rec_bits, res_bits = int(sizes[0][i]) * 8, int(sizes[1][i]) * 8
+        rows.append({"name": names[i], "comp_codelength": rec_bits, "comp_lossy_bpp": rec_bits / (h * w), "comp_code_bpd": rec_bits / (h * w * 3),
+                     "code_nats": int(n_idx[i]) * float(np.log(S)), "n_indices": int(n_idx[i]), "indices_recovered": bool(status[i] == 0 or status[i] > STATUS_RESIDUAL),
+                     "comp_residual": res_bits, "comp_lossless_bpp": (rec_bits + res_bits) / (h * w), "comp_bpd": (rec_bits + res_bits) / (h * w * 3),
+                     "residual_model_bits": float(ideal[i]), "pixels_recovered": bool(same[i]), "comp_time": t_compress / n + t_host})
+    return rows
+
+
+def compress_images(model, images, names, seed, block_size, out_dir, batch=None, packed=True, rec_on_device=False, lossless=False,
+                    stream_len=None):
     """images: [n, 3, H, W] in [-0.5, 0.5] on the model's device.  Returns one dict per image (reference CSV columns where
     they apply: comp_codelength, comp_lossy_bpp, comp_time) plus `indices_recovered`, `code_nats`.
     packed (default): the indices stay packed arrays from the device to the files (model.compress_packed, irec.io.encode_files
     / decode_files), and the host leg of a batch runs on a worker thread while the device codes the next batch; packed=False is
     the per-image form with the reference's write_compressed_code / read_compressed_code on nested lists.
     rec_on_device: a batch's files are built on the device (model.compress_rec) and the read-back check runs there
-    (irec.io.decode_files_device); same rows, byte-identical files.  The default stays the host leg."""
+    (irec.io.decode_files_device); same rows, byte-identical files.  The default stays the host leg.
+    lossless: images are uint8 [n, 3, H, W] (the model sees x / 256 - 0.5); NAME.res is written beside NAME.rec, both are read back
+    and decoded to the pixels on the device, and the rows gain comp_residual, comp_lossless_bpp, comp_bpd, residual_model_bits and
+    pixels_recovered (_lossless_leg).  stream_len: symbols per .res stream (default irec.io.residual.DEFAULT_STREAM_LEN)."""
     os.makedirs(out_dir, exist_ok=True)
     n = images.shape[0]
     batch = n if not batch else int(batch)
     S = model.residual_blocks[0].coder.n_samples
     rows = []
+    if lossless:
+        for lo in range(0, n, batch):
+            chunk = images[lo:lo + batch]
+            try:
+                rows += _lossless_leg(model, chunk, names[lo:lo + chunk.shape[0]], seed, block_size, out_dir, S, stream_len)
+            except CodingError as e:                     # compression_performance.py:375-377: log and move on
+                rows += [{"name": names[lo + i], "error": str(e)} for i in range(chunk.shape[0])]
+        return rows
     if rec_on_device:
         for lo in range(0, n, batch):
             chunk = images[lo:lo + batch]
@@ -167,6 +220,17 @@ def rec_file_groups(datas):
 
 
 def decompress_images(model, paths, batch=None, strict=True):
+    """The read side of compress_images (_decompress_images has the description)."""
+    return _decompress_images(model, paths, batch, strict, False)
+
+
+def decompress_images_lossless(model, paths, batch=None, strict=True):
+    """The read side of compress_images(lossless=True): decompress_images over NAME.rec + NAME.res pairs (`paths` names the .rec
+    files), the images being the uint8 pixels.  A function of its own: decompress_images' signature is pinned."""
+    return _decompress_images(model, paths, batch, strict, True)
+
+
+def _decompress_images(model, paths, batch, strict, lossless):
     """The read side of compress_images: .rec files -> (images, rows).  The files are read and their headers parsed on the host
     (RecHeader over the 28 + 16 R header bytes), files of equal (seed, shape, R, bpt) are grouped, each group's bytes are uploaded
     once per batch and decoded by model.decompress_rec -- the arithmetic decoder, the row checks and the generative pass on the
@@ -175,8 +239,15 @@ def decompress_images(model, paths, batch=None, strict=True):
     too short for its header (its entry is None: its shape is not known); rows: one dict per file (name, status, and where the
     header could be read seed, image_shape, block_size, decomp_time; `error` with the coder's text where status != 0).
     strict: CodingError for the first file, in the order of `paths`, that cannot be decoded; strict=False reports it in its row and
-    leaves its image zero."""
+    leaves its image zero.
+    lossless: beside every NAME.rec lies NAME.res (a missing one reads as an empty file); the images are the uint8 pixels of
+    model.decompress_lossless, and status may be STATUS_RESIDUAL + irec_res_status."""
+    from .io.residual import stream_len_of
     dev = next(model.parameters()).device
+    res_datas = []
+    for path in paths if lossless else []:
+        res_path = os.path.splitext(path)[0] + ".res"
+        res_datas.append(open(res_path, "rb").read() if os.path.exists(res_path) else b"")
     datas = []
     for path in paths:
         with open(path, "rb") as fh:
@@ -199,10 +270,18 @@ def decompress_images(model, paths, batch=None, strict=True):
                 host = np.frombuffer(b"".join(datas[i] for i in part), dtype=np.uint8)
                 max_K = max([1] + [m for i in part for m in infos[i]["max_partitions"] if m <= 65536])
                 blob = torch.from_numpy(host.copy()).to(dev)
-                rec, status, K = model._decompress_rec_status(blob, off, seed, (len(part), c, h, w_), max_K)
+                if lossless:
+                    res_off = np.concatenate([[0], np.cumsum([len(res_datas[i]) for i in part])]).astype(np.int64)
+                    res_host = np.frombuffer(b"".join(res_datas[i] for i in part), dtype=np.uint8)
+                    res_blob = torch.from_numpy(res_host.copy()).to(dev)
+                    L = stream_len_of(res_datas[part[0]])
+                    rec, status, K = model._decompress_lossless_status(blob, off, res_blob, res_off, seed, (len(part), c, h, w_), max_K,
+                                                                       L if L and 1 <= L <= 4096 else None)
+                else:
+                    rec, status, K = model._decompress_rec_status(blob, off, seed, (len(part), c, h, w_), max_K)
                 texts = [model.status_text(st, K[k]) if st else "" for k, st in enumerate(status)]
             else:                                                       # IREC_REC_E_STRUCTURE: not this model's block structure
-                rec, status = torch.zeros((len(part), 3, h, w_), device=dev), [17] * len(part)
+                rec, status = torch.zeros((len(part), 3, h, w_), device=dev, dtype=torch.uint8 if lossless else None), [17] * len(part)
                 texts = [f"{status_text(17)}: {R} residual blocks of {bpt} blocks for a {h} x {w_} x {c} image do not match the model"] * len(part)
             dt = (time.perf_counter() - t0) / len(part)
             for k, i in enumerate(part):

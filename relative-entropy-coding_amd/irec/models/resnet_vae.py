@@ -28,14 +28,18 @@ class ModelError(Exception):
 # the joined per-image status of decompress_rec / decompress_packed beside irec_rec_status (1 .. 18)
 STATUS_HEADER = 19      # the file's seed, height, width, channels or R differ from the call's
 STATUS_ROWS = 32        # + irec_rows_status (1 K_RANGE, 2 INDEX_RANGE, 3 RATIO_TABLE)
+STATUS_RESIDUAL = 48    # + irec_res_status (decompress_lossless: the .res file of an image whose .rec file decoded)
 
 
 def status_text(status, table_length=None, requested=None):
     """The coder's text for a joined status.  A count beyond the fitted ratio table gets the reference's message when the table's
     length and the count that was asked for are known."""
     from ..coding.coder import RATIO_TABLE_TEXT
+    from ..io.residual import res_status_text
     from ..io.utils import _REC_STATUS_TEXT
     status = int(status)
+    if status > STATUS_RESIDUAL:
+        return res_status_text(status - STATUS_RESIDUAL)
     if status == STATUS_ROWS + _lib.IREC_ROWS_E_RATIO_TABLE:
         if table_length is not None and requested is not None:
             return RATIO_TABLE_TEXT.format(table_length, requested)
@@ -355,6 +359,10 @@ class BidirectionalResNetVAE(nn.Module):
             for res_block_idx in range(num_res_blocks)])
         self._generative_base = nn.Parameter(torch.zeros(deterministic_filters))
         self._packed_rows_cache, self._header_want_cache = {}, {}   # device constants of the packed decompress path, per batch shape
+        # resnet_vae.py:581: the log of the discretized-logistic likelihood's one scale (the .res coder's model, compress_lossless).
+        # Created after every other parameter and without a random draw: no existing initialisation moves.
+        self.likelihood_log_scale = nn.Parameter(torch.zeros(()))
+        self._likelihood_scale_cache = None
 
     def generative_base(self, batch_size, height, width):
         """resnet_vae.py:619-623."""
@@ -633,6 +641,88 @@ class BidirectionalResNetVAE(nn.Module):
             self._raise_status(host, K)
             return reconstruction
         return reconstruction, host
+
+    # ---- the lossless pair: .rec (the latents' indices) + .res (the pixels under the likelihood given the reconstruction) ----------
+    def likelihood_scale(self):
+        """exp(likelihood_log_scale) as the float32 the .res coder takes by value.  The parameter is read back when it has changed
+        since the last call (its version counter), not per call."""
+        p = self.likelihood_log_scale
+        key = (p._version, p.data_ptr())
+        if self._likelihood_scale_cache is None or self._likelihood_scale_cache[0] != key:
+            from ..io.residual import scale_from_log
+            self._likelihood_scale_cache = (key, scale_from_log(p.detach().cpu().item()))
+        return self._likelihood_scale_cache[1]
+
+    @torch.no_grad()
+    def compress_lossless(self, images_u8, seed, stream_len=None, update_sampler=False, block_size=None, return_pendings=False):
+        """images_u8 [N, 3, H, W] uint8 CUDA -> (rec_blob, rec_offsets, res_blob, res_offsets, reconstruction), CUDA tensors.  The model
+        sees x / 256 - 0.5; the .rec files are exactly compress_rec's on that input; image i's .res file is
+        res_blob[res_offsets[i]:res_offsets[i + 1]]: its pixels arithmetic-coded on the device under the discretized logistic of
+        loc = the reconstruction that decompress_rec makes of those files (returned as `reconstruction`) and
+        scale = exp(likelihood_log_scale) (irec.io.encode_residuals_device; stream_len: symbols per stream, default
+        irec.io.residual.DEFAULT_STREAM_LEN).  decompress_lossless gives the images back exactly.
+        return_pendings: also compress_rec's device K / idx views, (the five, (K, idx))."""
+        from ..io.residual import encode_residuals_device
+        if not (images_u8.is_cuda and images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[1] == 3):
+            raise ModelError("compress_lossless takes a CUDA uint8 tensor [N, 3, H, W]")
+        x = images_u8.to(torch.float32).mul_(1.0 / 256.0).sub_(0.5)                 # exact: the values are k / 256 - 1 / 2
+        (blob, offsets, _), pendings = self.compress_rec(x, seed, update_sampler=update_sampler, block_size=block_size, return_pendings=True)
+        # loc must be the DECODER's reconstruction to the bit.  compress_rec's own differs from it in the last bits (its generative
+        # pass runs beside the inference heads: other convolution shapes; tests/test_decompress_device_gpu.py bounds the gap by 1e-5),
+        # so the pass that decompress_rec will run is run here, on the rows the files were built from: same function, same rows,
+        # same batch, the same bits (DESIGN.md §8).
+        K, idx = pendings
+        reconstruction = self._decompress_device(K, idx, seed, tuple(images_u8.shape), torch.zeros(K.shape[0], dtype=torch.int32, device=K.device))
+        try:
+            res_blob, res_offsets = encode_residuals_device(images_u8, reconstruction, self.likelihood_scale(), stream_len=stream_len)
+        except ValueError as e:
+            raise CodingError(str(e))
+        out = (blob, offsets, res_blob, res_offsets, reconstruction)
+        return (out, pendings) if return_pendings else out
+
+    def _decompress_lossless_device(self, rec_blob, rec_offsets, res_blob, res_offsets, seed, image_shape, max_K, stream_len):
+        """Everything of decompress_lossless that runs on the device, on one stream: _decompress_rec_device, the three launches of the
+        .res reader on its reconstruction, the joined status, refused images zeroed.  Returns (pixels uint8, status int32 [N], K) on
+        the device.  No host synchronisation."""
+        from ..io.residual import _decode_residuals_device_launch
+        reconstruction, joined, K = self._decompress_rec_device(rec_blob, rec_offsets, seed, image_shape, max_K)
+        pixels, res_status = _decode_residuals_device_launch(res_blob, res_offsets, reconstruction, self.likelihood_scale(), stream_len,
+                                                             on_device=True)
+        joined = torch.where(joined != 0, joined, torch.where(res_status != 0, res_status + STATUS_RESIDUAL, res_status))
+        # an image that an earlier stage refused was residual-decoded on a reconstruction that means nothing: zero, not garbage
+        pixels = pixels * (joined == 0).to(torch.uint8).reshape(-1, 1, 1, 1)
+        return pixels, joined, K
+
+    @torch.no_grad()
+    def _decompress_lossless_status(self, rec_blob, rec_offsets, res_blob, res_offsets, seed, image_shape, max_K=None, stream_len=None):
+        """decompress_lossless up to its read-back: (pixels, status int32 numpy [N], K on the device)."""
+        from ..io.residual import MAX_STREAM_LEN, _stream_len_device
+        if max_K is None:
+            max_K = self.files_max_K(rec_blob, rec_offsets)
+        if stream_len is None:
+            off = res_offsets.cpu().numpy() if hasattr(res_offsets, "cpu") else np.asarray(res_offsets)
+            stream_len = _stream_len_device(res_blob, off[:2])
+            stream_len = stream_len if stream_len and 1 <= stream_len <= MAX_STREAM_LEN else None   # (a damaged word: the default, and a status)
+        pixels, joined, K = self._decompress_lossless_device(rec_blob, rec_offsets, res_blob, res_offsets, seed, image_shape, int(max_K),
+                                                             stream_len)
+        return pixels, joined.cpu().numpy(), K
+
+    @torch.no_grad()
+    def decompress_lossless(self, rec_blob, rec_offsets, res_blob, res_offsets, seed, image_shape, max_K=None, strict=True, stream_len=None):
+        """The inverse of compress_lossless: N .rec files and their N .res files (blobs uint8 CUDA; offsets [N + 1] on the device or the
+        host) to the images, uint8 [N, 3, H, W] on the device, exactly.  decompress_rec's device pass, then the .res reader on its
+        reconstruction on the same stream, and ONE read-back -- the per-image status: decompress_rec's, then
+        STATUS_RESIDUAL + irec_res_status (include/irec.h) for an image whose .rec decoded but whose .res did not; first cause in that
+        order.  An image with a nonzero status is zero.  A reconstruction that differs from the encoder's in any pixel's
+        rint(loc * 4096) is the checksum status, not wrong pixels.
+        strict: CodingError with the first such image's text, "(image i)" appended; strict=False: (images, status int32 numpy [N]).
+        max_K None costs decompress_rec's small read-back of the .rec headers, stream_len None one of 12 bytes of the first .res
+        header; a caller that knows them passes them."""
+        pixels, host, K = self._decompress_lossless_status(rec_blob, rec_offsets, res_blob, res_offsets, seed, image_shape, max_K, stream_len)
+        if strict:
+            self._raise_status(host, K)
+            return pixels
+        return pixels, host
 
 
 class GraphedDecompress:
