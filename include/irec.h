@@ -477,6 +477,18 @@ int64_t irec_rec_encode_files(uint32_t seed, uint32_t block_size, uint32_t max_i
 irec_status irec_rec_decode_files(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
                                   int32_t blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
                                   int32_t n_threads);
+/* The same two calls for files whose residual blocks differ in size ("ragged": a two-level model codes 13 blocks at one level and 302
+ * at the other).  blocks_per_res [R], every entry >= 1; first[r] = sum of the entries before r, T = first[R]; block j of residual block
+ * r of image i is row i T + first[r] + j of K [n_images][T] and idx [n_images][T][max_K].  Bytes, return values and errors as above:
+ * every file is what irec_rec_encode_file gives for that image, the reader's outputs are what irec_rec_decode_file gives, rows
+ * zero-filled past K, and a file whose R or any block count differs from the call's fails the call naming the image. */
+int64_t irec_rec_encode_files_ragged(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                     uint32_t channels, int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res,
+                                     int32_t max_K, const int32_t *K /*[n][T]*/, const int32_t *idx /*[n][T][max_K]*/, uint8_t *out,
+                                     int64_t cap, int64_t *offsets, int32_t n_threads);
+irec_status irec_rec_decode_files_ragged(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                         const int32_t *blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K /*[n][T]*/,
+                                         int32_t *idx /*[n][T][max_K]*/, int32_t n_threads);
 
 /* The same two calls on the device (csrc/irec_rec.hip over csrc/irec_rec_core.h): the files of a batch built from, and read into,
  * device memory, one lane per stream, so that no index crosses to the host between a batch and its bytes.  Every pointer but
@@ -506,7 +518,7 @@ typedef enum {
   IREC_REC_E_INDEX_CORRUPT = 14,    /* decode: an index stream with target < 0 or width <= 0                              */
   IREC_REC_E_INDEX_BUDGET = 15,     /* decode: an index stream whose renormalisation budget ran out (no terminator)       */
   IREC_REC_E_MISMATCH = 16,         /* decode: counts or indices do not match the header (also: more values than allowed) */
-  IREC_REC_E_STRUCTURE = 17,        /* decode: not n_res_blocks residual blocks of blocks_per_res blocks each             */
+  IREC_REC_E_STRUCTURE = 17,        /* decode: not n_res_blocks residual blocks of the call's blocks_per_res blocks        */
   IREC_REC_E_MAX_K = 18             /* decode: a block with more partitions than max_K                                    */
 } irec_rec_status;
 size_t irec_rec_device_workspace_bytes(int32_t n_images, int32_t n_res_blocks);
@@ -518,6 +530,25 @@ irec_status irec_rec_encode_files_device(uint32_t seed, uint32_t block_size, uin
 irec_status irec_rec_decode_files_device(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
                                          int32_t blocks_per_res, int32_t max_K, uint32_t *headers /*[n][9]*/, int32_t *K, int32_t *idx,
                                          int32_t *status, void *workspace, size_t workspace_bytes, void *hip_stream);
+/* The ragged forms of the two device calls: the layout of irec_rec_encode_files_ragged (row i T + first[r] + j) under the stride
+ * conventions, bytes, offsets, statuses and guarantees of the uniform device forms -- offsets and status always written, nothing
+ * written when the files do not fit cap, no read outside a file's own range, the outputs of an image with a nonzero status zeroed
+ * (headers [n][9], K [n][T], idx [n][T][max_K]).  A file whose R or any block count differs from the call's -- also one with the
+ * call's T split differently, written as (4, 1) and read as (1, 4) -- has IREC_REC_E_STRUCTURE.  blocks_per_res is a HOST array of
+ * n_res_blocks <= IREC_REC_RAGGED_MAX_RES entries: its prefix sums travel by value in the kernel arguments, so these entry points too
+ * allocate nothing and copy nothing.  More residual blocks than that, an entry < 1 or a T above INT32_MAX: IREC_E_INVALID with the
+ * cause in irec_last_error, nothing launched, the outputs untouched.  The workspace is irec_rec_device_workspace_bytes's. */
+#define IREC_REC_RAGGED_MAX_RES 64
+irec_status irec_rec_encode_files_device_ragged(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                                uint32_t channels, int32_t n_images, int32_t n_res_blocks,
+                                                const int32_t *blocks_per_res /*host [n_res_blocks]*/, int32_t max_K,
+                                                const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride,
+                                                uint8_t *out, int64_t cap, int64_t *offsets /*[n_images + 1]*/, int32_t *status /*[n_images]*/,
+                                                void *workspace, size_t workspace_bytes, void *hip_stream);
+irec_status irec_rec_decode_files_device_ragged(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                                const int32_t *blocks_per_res /*host [n_res_blocks]*/, int32_t max_K,
+                                                uint32_t *headers /*[n][9]*/, int32_t *K, int32_t *idx, int32_t *status, void *workspace,
+                                                size_t workspace_bytes, void *hip_stream);
 
 /* The verdict on the rows a decode call is about to read, on the device (csrc/irec_rows.hip over csrc/irec_rows_core.h).  The decode
  * entry points above answer a row they cannot decode with p_loc, silently; a caller whose rows never leave the device (the output of

@@ -338,15 +338,22 @@ void for_each_image(int32_t n_images, int32_t n_threads, F &&body) {
 } // namespace
 extern "C" {
 
-int64_t irec_rec_encode_files(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
-                              uint32_t channels, int32_t n_images, int32_t n_res_blocks, int32_t blocks_per_res, int32_t max_K,
-                              const int32_t *K, const int32_t *idx, uint8_t *out, int64_t cap, int64_t *offsets, int32_t n_threads) try {
-  if (n_images < 0 || n_res_blocks < 1 || blocks_per_res < 1 || max_K < 0 || !K || (max_K > 0 && !idx) || !offsets) {
-    io_fail("irec_rec_encode_files: bad arguments"); return -1; }
+} // extern "C"
+namespace {
+// blocks per image of a call's layout, or -1: an entry < 1 or a sum that leaves int32
+int64_t layout_blocks(const std::vector<int32_t> &bpr) {
+  int64_t t = 0;
+  for (int32_t b : bpr) { if (b < 1) return -1; t += b; }
+  return t <= 0x7fffffff ? t : -1;
+}
+
+int64_t encode_files_impl(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width, uint32_t channels,
+                          int32_t n_images, const std::vector<int32_t> &bpr, int32_t max_K, const int32_t *K, const int32_t *idx,
+                          uint8_t *out, int64_t cap, int64_t *offsets, int32_t n_threads) {
+  const int32_t n_res_blocks = (int32_t)bpr.size();
   std::vector<std::vector<uint8_t>> files((size_t)n_images);
   std::vector<std::string> errs((size_t)n_images);
-  const int64_t per_img = (int64_t)n_res_blocks * blocks_per_res;
-  const std::vector<int32_t> bpr((size_t)n_res_blocks, blocks_per_res);
+  const int64_t per_img = layout_blocks(bpr);
   for_each_image(n_images, n_threads, [&](int32_t i) { try {
     const int32_t *Ki = K + (int64_t)i * per_img;
     std::vector<int32_t> flat;
@@ -378,18 +385,41 @@ int64_t irec_rec_encode_files(uint32_t seed, uint32_t block_size, uint32_t max_i
   if (out && cap >= total)
     for (int32_t i = 0; i < n_images; ++i) std::memcpy(out + offsets[i], files[(size_t)i].data(), files[(size_t)i].size());
   return total;
+}
+} // namespace
+extern "C" {
+
+int64_t irec_rec_encode_files(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                              uint32_t channels, int32_t n_images, int32_t n_res_blocks, int32_t blocks_per_res, int32_t max_K,
+                              const int32_t *K, const int32_t *idx, uint8_t *out, int64_t cap, int64_t *offsets, int32_t n_threads) try {
+  if (n_images < 0 || n_res_blocks < 1 || blocks_per_res < 1 || max_K < 0 || !K || (max_K > 0 && !idx) || !offsets) {
+    io_fail("irec_rec_encode_files: bad arguments"); return -1; }
+  return encode_files_impl(seed, block_size, max_index, height, width, channels, n_images, std::vector<int32_t>((size_t)n_res_blocks, blocks_per_res),
+                           max_K, K, idx, out, cap, offsets, n_threads);
 } catch (const std::exception &e) { g_io_error = std::string("irec_rec_encode_files: ") + e.what(); return -1; }
+
+// The same for residual blocks of differing sizes: K [n_images][T], idx [n_images][T][max_K], T = sum of blocks_per_res [n_res_blocks].
+int64_t irec_rec_encode_files_ragged(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                     uint32_t channels, int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res,
+                                     int32_t max_K, const int32_t *K, const int32_t *idx, uint8_t *out, int64_t cap, int64_t *offsets,
+                                     int32_t n_threads) try {
+  if (n_images < 0 || n_res_blocks < 1 || !blocks_per_res || max_K < 0 || !K || (max_K > 0 && !idx) || !offsets) {
+    io_fail("irec_rec_encode_files_ragged: bad arguments"); return -1; }
+  const std::vector<int32_t> bpr(blocks_per_res, blocks_per_res + n_res_blocks);
+  if (layout_blocks(bpr) < 0) { io_fail("irec_rec_encode_files_ragged: an entry of blocks_per_res is below 1, or their sum does not fit int32"); return -1; }
+  return encode_files_impl(seed, block_size, max_index, height, width, channels, n_images, bpr, max_K, K, idx, out, cap, offsets, n_threads);
+} catch (const std::exception &e) { g_io_error = std::string("irec_rec_encode_files_ragged: ") + e.what(); return -1; }
 
 // The inverse: n_images containers (bytes at offsets[i] .. offsets[i + 1]) decoded on host threads into the packed layout
 // above (rows zero-filled past K).  headers [n_images][9] as irec_rec_decode_file's; every file must hold n_res_blocks
 // residual blocks of blocks_per_res coded blocks with at most max_K partitions, else the call fails naming the image.
-irec_status irec_rec_decode_files(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
-                                  int32_t blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
-                                  int32_t n_threads) try {
-  if (!bytes || !offsets || n_images < 0 || n_res_blocks < 1 || blocks_per_res < 1 || max_K < 0 || !headers || !K || (max_K > 0 && !idx))
-    return io_fail("irec_rec_decode_files: bad arguments");
+} // extern "C"
+namespace {
+irec_status decode_files_impl(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, const std::vector<int32_t> &want, int32_t max_K,
+                              uint32_t *headers, int32_t *K, int32_t *idx, int32_t n_threads) {
+  const int32_t n_res_blocks = (int32_t)want.size();
   std::vector<std::string> errs((size_t)n_images);
-  const int64_t per_img = (int64_t)n_res_blocks * blocks_per_res;
+  const int64_t per_img = layout_blocks(want);
   for_each_image(n_images, n_threads, [&](int32_t i) { try {
     std::vector<int32_t> bpr((size_t)n_res_blocks), flat;
     int64_t sizes[3] = {0, 0, 0};
@@ -409,7 +439,7 @@ irec_status irec_rec_decode_files(const uint8_t *bytes, const int64_t *offsets, 
       } else if (st == IREC_OK) {
         if (sizes[0] != n_res_blocks || sizes[1] != per_img) { st = IREC_E_INVALID; g_io_error = "irec_rec_decode_files: block structure differs"; break; }
         for (int32_t r = 0; r < n_res_blocks; ++r)
-          if (bpr[(size_t)r] != blocks_per_res) { st = IREC_E_INVALID; g_io_error = "irec_rec_decode_files: block structure differs"; }
+          if (bpr[(size_t)r] != want[(size_t)r]) { st = IREC_E_INVALID; g_io_error = "irec_rec_decode_files: block structure differs"; }
         if (st != IREC_OK) break;
         int64_t at = 0;
         for (int64_t b = 0; b < per_img; ++b) {
@@ -427,6 +457,27 @@ irec_status irec_rec_decode_files(const uint8_t *bytes, const int64_t *offsets, 
   for (int32_t i = 0; i < n_images; ++i)
     if (!errs[(size_t)i].empty()) { g_io_error = errs[(size_t)i] + " (image " + std::to_string(i) + ")"; return IREC_E_INVALID; }
   return IREC_OK;
+}
+} // namespace
+extern "C" {
+
+irec_status irec_rec_decode_files(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                  int32_t blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
+                                  int32_t n_threads) try {
+  if (!bytes || !offsets || n_images < 0 || n_res_blocks < 1 || blocks_per_res < 1 || max_K < 0 || !headers || !K || (max_K > 0 && !idx))
+    return io_fail("irec_rec_decode_files: bad arguments");
+  return decode_files_impl(bytes, offsets, n_images, std::vector<int32_t>((size_t)n_res_blocks, blocks_per_res), max_K, headers, K, idx, n_threads);
 } catch (const std::exception &e) { g_io_error = std::string("irec_rec_decode_files: ") + e.what(); return IREC_E_INVALID; }
+
+// The same for residual blocks of differing sizes: every file must hold blocks_per_res[r] coded blocks in residual block r.
+irec_status irec_rec_decode_files_ragged(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                         const int32_t *blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
+                                         int32_t n_threads) try {
+  if (!bytes || !offsets || n_images < 0 || n_res_blocks < 1 || !blocks_per_res || max_K < 0 || !headers || !K || (max_K > 0 && !idx))
+    return io_fail("irec_rec_decode_files_ragged: bad arguments");
+  const std::vector<int32_t> bpr(blocks_per_res, blocks_per_res + n_res_blocks);
+  if (layout_blocks(bpr) < 0) return io_fail("irec_rec_decode_files_ragged: an entry of blocks_per_res is below 1, or their sum does not fit int32");
+  return decode_files_impl(bytes, offsets, n_images, bpr, max_K, headers, K, idx, n_threads);
+} catch (const std::exception &e) { g_io_error = std::string("irec_rec_decode_files_ragged: ") + e.what(); return IREC_E_INVALID; }
 
 } // extern "C"

@@ -84,7 +84,7 @@ __global__ __launch_bounds__(REC_NT) void rec_decode_status_kernel(irec_rec::Dec
     __syncthreads();
     if (t == 0) c.status[i] = st;
     if (st) {
-      const int64_t nK = (int64_t)c.R * c.bpt, nI = nK * c.max_K;
+      const int64_t nK = irec_rec::image_blocks(c), nI = nK * c.max_K;
       if (t < 9) c.headers[9 * i + t] = 0;
       for (int64_t e = t; e < nK; e += REC_NT) c.K[i * nK + e] = 0;
       for (int64_t e = t; e < nI; e += REC_NT) c.idx[i * nI + e] = 0;
@@ -106,6 +106,14 @@ bool decode_args_ok(const uint8_t *bytes, const int64_t *offsets, int32_t N, int
   return bytes && offsets && N >= 0 && R >= 1 && R <= 65535 && bpt >= 1 && max_K >= 0 && (N == 0 || (headers && K && status)) &&
          (N == 0 || max_K == 0 || idx) && ((int64_t)N * R) / REC_NT < 0x7fffffff;
 }
+// blocks_per_res[R] of a ragged call (a host array) as the prefix sums the call carries; nullptr, or why not
+const char *ragged_layout(int32_t R, const int32_t *blocks_per_res, int32_t *first) {
+  if (R < 1 || R > IREC_REC_RAGGED_MAX_RES) return "n_res_blocks outside [1, IREC_REC_RAGGED_MAX_RES]";
+  if (!blocks_per_res) return "blocks_per_res is null";
+  for (int32_t r = 0; r < R; ++r) if (blocks_per_res[r] < 1) return "an entry of blocks_per_res is below 1";
+  if (!irec_rec::ragged_first(R, blocks_per_res, first)) return "the blocks of an image do not fit int32";
+  return nullptr;
+}
 } // namespace
 } // namespace irec
 
@@ -114,6 +122,39 @@ bool decode_args_ok(const uint8_t *bytes, const int64_t *offsets, int32_t N, int
     hipError_t e_ = (expr);                                                                             \
     if (e_ != hipSuccess) return irec::set_last_error(IREC_E_HIP, #expr, hipGetErrorString(e_));         \
   } while (0)
+
+namespace irec {
+namespace {
+// the three launches of a call whose arguments and workspace have been checked, uniform or ragged
+irec_status launch_encode(irec_rec::EncodeCall &c, void *workspace, void *hip_stream) {
+  irec_rec::encode_bind_workspace(c, workspace);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int64_t streams = 2 * (int64_t)c.N * c.R;
+  if (streams > 0) {
+    hipLaunchKernelGGL(rec_size_kernel, dim3(rec_grid(streams)), dim3(REC_NT), 0, st, c);
+    REC_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(rec_layout_kernel, dim3(1), dim3(REC_NT), 0, st, c);
+  REC_HIP(hipGetLastError());
+  if (streams > 0) {
+    hipLaunchKernelGGL(rec_write_kernel, dim3(rec_grid(streams + c.N)), dim3(REC_NT), 0, st, c);
+    REC_HIP(hipGetLastError());
+  }
+  return IREC_OK;
+}
+irec_status launch_decode(const irec_rec::DecodeCall &c, void *hip_stream) {
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int64_t lanes = (int64_t)c.N * c.R;
+  hipLaunchKernelGGL(rec_decode_counts_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c);
+  REC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(rec_decode_indices_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c);
+  REC_HIP(hipGetLastError());
+  hipLaunchKernelGGL(rec_decode_status_kernel, dim3(c.N < 65536 ? c.N : 65536), dim3(REC_NT), 0, st, c);
+  REC_HIP(hipGetLastError());
+  return IREC_OK;
+}
+} // namespace
+} // namespace irec
 
 extern "C" {
 
@@ -133,21 +174,25 @@ irec_status irec_rec_encode_files_device(uint32_t seed, uint32_t block_size, uin
   if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < irec_rec_device_workspace_bytes(n_images, n_res_blocks))
     return set_last_error(IREC_E_WORKSPACE, "irec_rec_encode_files_device", "workspace too small (irec_rec_device_workspace_bytes) or not 8-byte aligned");
   irec_rec::EncodeCall c{seed, block_size, max_index, height, width, channels, n_images, n_res_blocks, blocks_per_res, max_K,
-                         K, k_stride, idx, idx_stride, out, cap, offsets, status, nullptr, nullptr, nullptr};
-  irec_rec::encode_bind_workspace(c, workspace);
-  hipStream_t st = (hipStream_t)hip_stream;
-  const int64_t streams = 2 * (int64_t)n_images * n_res_blocks;
-  if (streams > 0) {
-    hipLaunchKernelGGL(rec_size_kernel, dim3(rec_grid(streams)), dim3(REC_NT), 0, st, c);
-    REC_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(rec_layout_kernel, dim3(1), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
-  if (streams > 0) {
-    hipLaunchKernelGGL(rec_write_kernel, dim3(rec_grid(streams + n_images)), dim3(REC_NT), 0, st, c);
-    REC_HIP(hipGetLastError());
-  }
-  return IREC_OK;
+                         K, k_stride, idx, idx_stride, out, cap, offsets, status, nullptr, nullptr, nullptr, {}};
+  return launch_encode(c, workspace, hip_stream);
+}
+
+irec_status irec_rec_encode_files_device_ragged(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                                uint32_t channels, int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res,
+                                                int32_t max_K, const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride,
+                                                uint8_t *out, int64_t cap, int64_t *offsets, int32_t *status, void *workspace,
+                                                size_t workspace_bytes, void *hip_stream) {
+  using namespace irec;
+  irec_rec::EncodeCall c{seed, block_size, max_index, height, width, channels, n_images, n_res_blocks, 0, max_K,
+                         K, k_stride, idx, idx_stride, out, cap, offsets, status, nullptr, nullptr, nullptr, {}};
+  if (const char *why = ragged_layout(n_res_blocks, blocks_per_res, c.first))
+    return set_last_error(IREC_E_INVALID, "irec_rec_encode_files_device_ragged", why);
+  if (!encode_args_ok(height, width, channels, n_images, n_res_blocks, 1, max_K, K, k_stride, idx, idx_stride, out, cap, offsets, status))
+    return set_last_error(IREC_E_INVALID, "irec_rec_encode_files_device_ragged", "bad arguments");
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < irec_rec_device_workspace_bytes(n_images, n_res_blocks))
+    return set_last_error(IREC_E_WORKSPACE, "irec_rec_encode_files_device_ragged", "workspace too small (irec_rec_device_workspace_bytes) or not 8-byte aligned");
+  return launch_encode(c, workspace, hip_stream);
 }
 
 irec_status irec_rec_decode_files_device(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
@@ -159,44 +204,91 @@ irec_status irec_rec_decode_files_device(const uint8_t *bytes, const int64_t *of
   if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < irec_rec_device_workspace_bytes(n_images, n_res_blocks))
     return set_last_error(IREC_E_WORKSPACE, "irec_rec_decode_files_device", "workspace too small (irec_rec_device_workspace_bytes) or not 8-byte aligned");
   if (n_images == 0) return IREC_OK;
-  irec_rec::DecodeCall c{bytes, offsets, n_images, n_res_blocks, blocks_per_res, max_K, headers, K, idx, status, (int32_t *)workspace};
-  hipStream_t st = (hipStream_t)hip_stream;
-  const int64_t lanes = (int64_t)n_images * n_res_blocks;
-  hipLaunchKernelGGL(rec_decode_counts_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(rec_decode_indices_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
-  hipLaunchKernelGGL(rec_decode_status_kernel, dim3(n_images < 65536 ? n_images : 65536), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
-  return IREC_OK;
+  irec_rec::DecodeCall c{bytes, offsets, n_images, n_res_blocks, blocks_per_res, max_K, headers, K, idx, status, (int32_t *)workspace, {}};
+  return launch_decode(c, hip_stream);
+}
+
+irec_status irec_rec_decode_files_device_ragged(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                                const int32_t *blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
+                                                int32_t *status, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  using namespace irec;
+  irec_rec::DecodeCall c{bytes, offsets, n_images, n_res_blocks, 0, max_K, headers, K, idx, status, (int32_t *)workspace, {}};
+  if (const char *why = ragged_layout(n_res_blocks, blocks_per_res, c.first))
+    return set_last_error(IREC_E_INVALID, "irec_rec_decode_files_device_ragged", why);
+  if (!decode_args_ok(bytes, offsets, n_images, n_res_blocks, 1, max_K, headers, K, idx, status))
+    return set_last_error(IREC_E_INVALID, "irec_rec_decode_files_device_ragged", "bad arguments");
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < irec_rec_device_workspace_bytes(n_images, n_res_blocks))
+    return set_last_error(IREC_E_WORKSPACE, "irec_rec_decode_files_device_ragged", "workspace too small (irec_rec_device_workspace_bytes) or not 8-byte aligned");
+  if (n_images == 0) return IREC_OK;
+  return launch_decode(c, hip_stream);
 }
 
 // ---- the same lane functions over host memory, in a plain loop (csrc/irec_internal.h) ------------------------------------------------
-irec_status irec_rec_test_core_encode_files(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
-                                            uint32_t channels, int32_t n_images, int32_t n_res_blocks, int32_t blocks_per_res, int32_t max_K,
-                                            const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride, uint8_t *out, int64_t cap,
-                                            int64_t *offsets, int32_t *status) try {
-  using namespace irec;
-  if (!encode_args_ok(height, width, channels, n_images, n_res_blocks, blocks_per_res, max_K, K, k_stride, idx, idx_stride, out, cap, offsets, status))
-    return set_last_error(IREC_E_INVALID, "irec_rec_test_core_encode_files", "bad arguments");
-  std::vector<int64_t> ws((size_t)(irec_rec_device_workspace_bytes(n_images, n_res_blocks) / 8 + 1));
-  irec_rec::EncodeCall c{seed, block_size, max_index, height, width, channels, n_images, n_res_blocks, blocks_per_res, max_K,
-                         K, k_stride, idx, idx_stride, out, cap, offsets, status, nullptr, nullptr, nullptr};
+} // extern "C"
+namespace irec {
+namespace {
+irec_status core_encode_host(irec_rec::EncodeCall &c, const char *who) try {
+  std::vector<int64_t> ws((size_t)(irec_rec_device_workspace_bytes(c.N, c.R) / 8 + 1));
   irec_rec::encode_bind_workspace(c, ws.data());
   irec_rec::encode_call_host(c);
   return IREC_OK;
-} catch (const std::exception &e) { return irec::set_last_error(IREC_E_INVALID, "irec_rec_test_core_encode_files", e.what()); }
+} catch (const std::exception &e) { return set_last_error(IREC_E_INVALID, who, e.what()); }
+irec_status core_decode_host(irec_rec::DecodeCall &c, const char *who) try {
+  std::vector<int32_t> ws((size_t)(2 * (int64_t)c.N * c.R + 1));
+  c.stream_status = ws.data();
+  irec_rec::decode_call_host(c);
+  return IREC_OK;
+} catch (const std::exception &e) { return set_last_error(IREC_E_INVALID, who, e.what()); }
+} // namespace
+} // namespace irec
+extern "C" {
+
+irec_status irec_rec_test_core_encode_files(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                            uint32_t channels, int32_t n_images, int32_t n_res_blocks, int32_t blocks_per_res, int32_t max_K,
+                                            const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride, uint8_t *out, int64_t cap,
+                                            int64_t *offsets, int32_t *status) {
+  using namespace irec;
+  if (!encode_args_ok(height, width, channels, n_images, n_res_blocks, blocks_per_res, max_K, K, k_stride, idx, idx_stride, out, cap, offsets, status))
+    return set_last_error(IREC_E_INVALID, "irec_rec_test_core_encode_files", "bad arguments");
+  irec_rec::EncodeCall c{seed, block_size, max_index, height, width, channels, n_images, n_res_blocks, blocks_per_res, max_K,
+                         K, k_stride, idx, idx_stride, out, cap, offsets, status, nullptr, nullptr, nullptr, {}};
+  return core_encode_host(c, "irec_rec_test_core_encode_files");
+}
+
+irec_status irec_rec_test_core_encode_files_ragged(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                                   uint32_t channels, int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res,
+                                                   int32_t max_K, const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride,
+                                                   uint8_t *out, int64_t cap, int64_t *offsets, int32_t *status) {
+  using namespace irec;
+  irec_rec::EncodeCall c{seed, block_size, max_index, height, width, channels, n_images, n_res_blocks, 0, max_K,
+                         K, k_stride, idx, idx_stride, out, cap, offsets, status, nullptr, nullptr, nullptr, {}};
+  if (const char *why = ragged_layout(n_res_blocks, blocks_per_res, c.first))
+    return set_last_error(IREC_E_INVALID, "irec_rec_test_core_encode_files_ragged", why);
+  if (!encode_args_ok(height, width, channels, n_images, n_res_blocks, 1, max_K, K, k_stride, idx, idx_stride, out, cap, offsets, status))
+    return set_last_error(IREC_E_INVALID, "irec_rec_test_core_encode_files_ragged", "bad arguments");
+  return core_encode_host(c, "irec_rec_test_core_encode_files_ragged");
+}
 
 irec_status irec_rec_test_core_decode_files(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
                                             int32_t blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
-                                            int32_t *status) try {
+                                            int32_t *status) {
   using namespace irec;
   if (!decode_args_ok(bytes, offsets, n_images, n_res_blocks, blocks_per_res, max_K, headers, K, idx, status))
     return set_last_error(IREC_E_INVALID, "irec_rec_test_core_decode_files", "bad arguments");
-  std::vector<int32_t> ws((size_t)(2 * (int64_t)n_images * n_res_blocks + 1));
-  irec_rec::DecodeCall c{bytes, offsets, n_images, n_res_blocks, blocks_per_res, max_K, headers, K, idx, status, ws.data()};
-  irec_rec::decode_call_host(c);
-  return IREC_OK;
-} catch (const std::exception &e) { return irec::set_last_error(IREC_E_INVALID, "irec_rec_test_core_decode_files", e.what()); }
+  irec_rec::DecodeCall c{bytes, offsets, n_images, n_res_blocks, blocks_per_res, max_K, headers, K, idx, status, nullptr, {}};
+  return core_decode_host(c, "irec_rec_test_core_decode_files");
+}
+
+irec_status irec_rec_test_core_decode_files_ragged(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                                   const int32_t *blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
+                                                   int32_t *status) {
+  using namespace irec;
+  irec_rec::DecodeCall c{bytes, offsets, n_images, n_res_blocks, 0, max_K, headers, K, idx, status, nullptr, {}};
+  if (const char *why = ragged_layout(n_res_blocks, blocks_per_res, c.first))
+    return set_last_error(IREC_E_INVALID, "irec_rec_test_core_decode_files_ragged", why);
+  if (!decode_args_ok(bytes, offsets, n_images, n_res_blocks, 1, max_K, headers, K, idx, status))
+    return set_last_error(IREC_E_INVALID, "irec_rec_test_core_decode_files_ragged", "bad arguments");
+  return core_decode_host(c, "irec_rec_test_core_decode_files_ragged");
+}
 
 } // extern "C"

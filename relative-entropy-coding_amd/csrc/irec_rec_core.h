@@ -11,6 +11,10 @@
 //
 // One call is 2 N R streams, one lane each: lanes [0, N R) the index streams, [N R, 2 N R) the count streams (a wave holds streams
 // of one kind), stream (i, r) of a kind at i R + r.  Every lane function below touches only memory that its lane owns.
+//
+// Blocks per residual block: one count for the whole call (bpt >= 1, any R), or one per residual block (bpt = 0: "ragged", R <=
+// IREC_REC_RAGGED_MAX_RES) as the prefix sums first[r] = sum_{q < r} blocks[q], which travel by value inside the call so that a kernel
+// argument carries them.  Either way an image is T = first[R] rows, block j of residual block r of image i is row i T + first[r] + j.
 #ifndef IREC_REC_CORE_H_
 #define IREC_REC_CORE_H_
 
@@ -150,11 +154,29 @@ IREC_REC_HD inline uint32_t get_u16(const uint8_t *p) { return (uint32_t)p[0] | 
 struct EncodeCall {
   uint32_t seed, block_size, max_index, height, width, channels;
   int32_t N, R, bpt, max_K;
-  const int32_t *K; int64_t k_stride; const int32_t *idx; int64_t idx_stride;   // block b = (i R + r) bpt + j: K[b k_stride], idx[b idx_stride + t]
+  const int32_t *K; int64_t k_stride; const int32_t *idx; int64_t idx_stride;   // block b = i T + first[r] + j: K[b k_stride], idx[b idx_stride + t]
   uint8_t *out; int64_t cap; int64_t *offsets; int32_t *status;
   // workspace: bits of every stream, its status, the largest K of every residual block
   int64_t *n_bits; int32_t *stream_status; int32_t *max_part;
+  int32_t first[IREC_REC_RAGGED_MAX_RES + 1];   // bpt = 0 only
 };
+// the layout of a call (EncodeCall or DecodeCall): blocks of residual block r, its first row within an image, rows per image
+template <class Call> IREC_REC_HD inline int32_t res_blocks(const Call &c, int32_t r) { return c.bpt ? c.bpt : c.first[r + 1] - c.first[r]; }
+template <class Call> IREC_REC_HD inline int64_t res_first(const Call &c, int32_t r) { return c.bpt ? (int64_t)r * c.bpt : (int64_t)c.first[r]; }
+template <class Call> IREC_REC_HD inline int64_t image_blocks(const Call &c) { return c.bpt ? (int64_t)c.R * c.bpt : (int64_t)c.first[c.R]; }
+// first[0 .. R] from blocks_per_res[R]; false for R outside [1, IREC_REC_RAGGED_MAX_RES], an entry < 1 or a sum that leaves int32
+inline bool ragged_first(int32_t R, const int32_t *blocks_per_res, int32_t *first) {
+  if (R < 1 || R > IREC_REC_RAGGED_MAX_RES || !blocks_per_res) return false;
+  int64_t at = 0;
+  for (int32_t r = 0; r < R; ++r) {
+    first[r] = (int32_t)at;
+    if (blocks_per_res[r] < 1) return false;
+    at += blocks_per_res[r];
+    if (at > 0x7fffffff) return false;
+  }
+  for (int32_t r = R; r <= IREC_REC_RAGGED_MAX_RES; ++r) first[r] = (int32_t)at;
+  return true;
+}
 IREC_REC_HD inline int64_t encode_workspace_bytes(int64_t N, int64_t R) { return 2 * N * R * 8 + 2 * N * R * 4 + N * R * 4; }
 IREC_REC_HD inline void encode_bind_workspace(EncodeCall &c, void *ws) {
   const int64_t NR = (int64_t)c.N * c.R;
@@ -180,9 +202,11 @@ template <class Sink>
 IREC_REC_HD inline int32_t encode_lane_stream(const EncodeCall &c, int64_t lane, Sink &sink, int32_t *max_part_out) {
   const int64_t NR = (int64_t)c.N * c.R;
   const bool counts = lane >= NR;
-  const int64_t b0 = (counts ? lane - NR : lane) * c.bpt;
+  const int64_t s = counts ? lane - NR : lane;
+  const int32_t r = (int32_t)(s % c.R), nb = res_blocks(c, r);
+  const int64_t b0 = (s / c.R) * image_blocks(c) + res_first(c, r);
   int32_t mx = 0; int64_t tot = 0;
-  for (int32_t j = 0; j < c.bpt; ++j) {
+  for (int32_t j = 0; j < nb; ++j) {
     const int32_t k = c.K[(b0 + j) * c.k_stride];
     if (k < 0 || k > c.max_K) return IREC_REC_E_K_RANGE;
     mx = k > mx ? k : mx; tot += k;
@@ -192,7 +216,7 @@ IREC_REC_HD inline int32_t encode_lane_stream(const EncodeCall &c, int64_t lane,
     const Model m = make_model((uint64_t)mx + 1, COUNT_WEIGHT);
     if (!model_fits(m)) return IREC_REC_E_MODEL_RANGE;
     CountFetch f{c.K, c.k_stride, b0};
-    return encode_stream(m, c.bpt, f, sink) ? IREC_REC_E_K_RANGE : IREC_REC_OK;
+    return encode_stream(m, nb, f, sink) ? IREC_REC_E_K_RANGE : IREC_REC_OK;
   }
   const Model m = make_model(c.max_index, INDEX_WEIGHT);
   if (!model_fits(m)) return IREC_REC_E_MODEL_RANGE;
@@ -239,7 +263,7 @@ IREC_REC_HD inline void encode_write_lane(const EncodeCall &c, int64_t lane) {
     put_u16(f + 20, c.channels); put_u16(f + 22, 0); put_u16(f + 24, 0); put_u16(f + 26, (uint32_t)c.R);
     for (int32_t r = 0; r < c.R; ++r) {
       uint8_t *d = f + 28 + 4 * r;
-      put_u32(d, (uint32_t)c.bpt);
+      put_u32(d, (uint32_t)res_blocks(c, r));
       put_u32(d + 4 * c.R, (uint32_t)stream_bytes(c.n_bits[NR + i * c.R + r]));
       put_u32(d + 8 * c.R, (uint32_t)stream_bytes(c.n_bits[i * c.R + r]));
       put_u32(d + 12 * c.R, (uint32_t)c.max_part[i * c.R + r]);
@@ -263,15 +287,16 @@ IREC_REC_HD inline void encode_write_lane(const EncodeCall &c, int64_t lane) {
 // ================================================================================================================================
 struct DecodeCall {
   const uint8_t *bytes; const int64_t *offsets; int32_t N, R, bpt, max_K;
-  uint32_t *headers; int32_t *K; int32_t *idx; int32_t *status;
+  uint32_t *headers; int32_t *K; int32_t *idx; int32_t *status;   // K [N][T], idx [N][T][max_K]: residual block r of image i from row i T + first[r]
   int32_t *stream_status;   // workspace [2 N R], laid out like the encoder's lanes
+  int32_t first[IREC_REC_RAGGED_MAX_RES + 1];   // bpt = 0 only
 };
 IREC_REC_HD inline int64_t decode_workspace_bytes(int64_t N, int64_t R) { return 2 * N * R * 4; }
 
 struct StreamLoc { int64_t c_pos, c_len, x_pos, x_len; uint32_t max_part, max_index; };
 
 // Every check of irec_rec_decode_file that does not need a stream decoded, for residual block r of a file, plus the batched reader's
-// (R and blocks per residual block as the caller says).  The file is only read inside [file, file + n_bytes).
+// (R and the blocks of residual block r as the caller says).  The file is only read inside [file, file + n_bytes).
 IREC_REC_HD inline int32_t decode_locate(const uint8_t *file, int64_t n_bytes, int32_t R, int32_t bpt, int32_t r, StreamLoc *loc, uint32_t *hdr9) {
   if (n_bytes < 28) return IREC_REC_E_TRUNCATED_HEADER;
   uint32_t h[9];
@@ -310,22 +335,22 @@ struct IndexEmit {   // value after value into row j up to its K, the rest of ev
 // launch 1, lane < N R: the checks of residual block r of image i, its K row; lane r = 0 also leaves the image's header
 IREC_REC_HD inline void decode_counts_lane(const DecodeCall &c, int64_t s) {
   const int64_t NR = (int64_t)c.N * c.R, i = s / c.R;
-  const int32_t r = (int32_t)(s % c.R);
-  int32_t *row = c.K + s * c.bpt;
+  const int32_t r = (int32_t)(s % c.R), nb = res_blocks(c, r);
+  int32_t *row = c.K + i * image_blocks(c) + res_first(c, r);
   c.stream_status[s] = IREC_REC_OK;
   const int64_t lo = c.offsets[i], n_bytes = c.offsets[i + 1] - lo;
   StreamLoc loc;
-  int32_t st = lo < 0 || n_bytes < 0 ? IREC_REC_E_TRUNCATED_HEADER : decode_locate(c.bytes + lo, n_bytes, c.R, c.bpt, r, &loc, r == 0 ? c.headers + 9 * i : nullptr);
+  int32_t st = lo < 0 || n_bytes < 0 ? IREC_REC_E_TRUNCATED_HEADER : decode_locate(c.bytes + lo, n_bytes, c.R, nb, r, &loc, r == 0 ? c.headers + 9 * i : nullptr);
   if (st == IREC_REC_OK) {
     BitReader in;
-    CountEmit emit{row, c.bpt, c.max_K};
+    CountEmit emit{row, nb, c.max_K};
     int64_t n = 0;
     if (!in.open(c.bytes + lo + loc.c_pos, loc.c_len)) st = IREC_REC_E_COUNT_MARKER;
     else {
-      const int d = decode_stream(make_model((uint64_t)loc.max_part + 1, COUNT_WEIGHT), in, c.bpt, emit, &n);
+      const int d = decode_stream(make_model((uint64_t)loc.max_part + 1, COUNT_WEIGHT), in, nb, emit, &n);
       if (d == DEC_CORRUPT) st = IREC_REC_E_COUNT_CORRUPT;
       else if (d == DEC_BUDGET) st = IREC_REC_E_COUNT_BUDGET;
-      else if (d == DEC_TOO_MANY || n != c.bpt) st = IREC_REC_E_MISMATCH;
+      else if (d == DEC_TOO_MANY || n != nb) st = IREC_REC_E_MISMATCH;
       else if (emit.over) st = IREC_REC_E_MAX_K;
     }
   }
@@ -335,18 +360,19 @@ IREC_REC_HD inline void decode_counts_lane(const DecodeCall &c, int64_t s) {
 // launch 2, lane < N R: the index stream of (i, r) into its rows, by the K of launch 1
 IREC_REC_HD inline void decode_indices_lane(const DecodeCall &c, int64_t s) {
   const int64_t NR = (int64_t)c.N * c.R, i = s / c.R;
-  const int32_t r = (int32_t)(s % c.R);
+  const int32_t r = (int32_t)(s % c.R), nb = res_blocks(c, r);
+  const int64_t row0 = i * image_blocks(c) + res_first(c, r);
   if (c.stream_status[NR + s]) return;            // no K to go by (the image's outputs are zeroed by the last launch)
   const int64_t lo = c.offsets[i], n_bytes = c.offsets[i + 1] - lo;
   StreamLoc loc;
-  int32_t st = decode_locate(c.bytes + lo, n_bytes, c.R, c.bpt, r, &loc, nullptr);
+  int32_t st = decode_locate(c.bytes + lo, n_bytes, c.R, nb, r, &loc, nullptr);
   if (st == IREC_REC_OK) {
-    const int32_t *Krow = c.K + s * c.bpt;
+    const int32_t *Krow = c.K + row0;
     int64_t tot = 0, n = 0;
-    for (int32_t j = 0; j < c.bpt; ++j) tot += Krow[j];
+    for (int32_t j = 0; j < nb; ++j) tot += Krow[j];
     const Model m = make_model(loc.max_index, INDEX_WEIGHT);
     BitReader in;
-    IndexEmit emit{Krow, c.idx + s * c.bpt * (int64_t)c.max_K, c.bpt, c.max_K};
+    IndexEmit emit{Krow, c.idx + row0 * (int64_t)c.max_K, nb, c.max_K};
     if (!model_fits(m)) st = IREC_REC_E_INDEX_MODEL;
     else if (!in.open(c.bytes + lo + loc.x_pos, loc.x_len)) st = IREC_REC_E_INDEX_MARKER;
     else {
@@ -377,7 +403,7 @@ inline void encode_call_host(const EncodeCall &c) {
   for (int64_t lane = 0; lane < streams + c.N; ++lane) encode_write_lane(c, lane);
 }
 inline void decode_call_host(const DecodeCall &c) {
-  const int64_t lanes = (int64_t)c.N * c.R, nK = (int64_t)c.R * c.bpt, nI = nK * c.max_K;
+  const int64_t lanes = (int64_t)c.N * c.R, nK = image_blocks(c), nI = nK * c.max_K;
   for (int64_t s = 0; s < lanes; ++s) decode_counts_lane(c, s);
   for (int64_t s = 0; s < lanes; ++s) decode_indices_lane(c, s);
   for (int64_t i = 0; i < c.N; ++i) {

@@ -33,6 +33,8 @@ MAX_BEAMS = 256
 MAX_PARTITIONS = 65536
 IREC_ROWS_OK, IREC_ROWS_E_K_RANGE, IREC_ROWS_E_INDEX_RANGE, IREC_ROWS_E_RATIO_TABLE = 0, 1, 2, 3   # irec_rows_status
 IREC_REC_E_MAX_K = 18            # irec_rec_status: a block with more partitions than max_K
+IREC_REC_E_STRUCTURE = 17        # irec_rec_status: a file whose R or block counts differ from the call's
+REC_RAGGED_MAX_RES = 64          # IREC_REC_RAGGED_MAX_RES
 INT32_MAX = 2 ** 31 - 1
 
 
@@ -160,10 +162,18 @@ SIGNATURES = {
     "irec_rec_decode_file": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64]),
     "irec_rec_encode_files": (_i64, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i32]),
     "irec_rec_decode_files": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32]),
+    "irec_rec_encode_files_ragged": (_i64, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32]),
+    "irec_rec_decode_files_ragged": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32]),
     "irec_rec_device_workspace_bytes": (ctypes.c_size_t, [_i32, _i32]),
     "irec_rec_encode_files_device": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
                                                     _vp, ctypes.c_size_t, _vp]),
     "irec_rec_decode_files_device": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_rec_encode_files_device_ragged": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                                           _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_rec_decode_files_device_ragged": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_rec_test_core_encode_files_ragged": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                              _vp, _vp]),
+    "irec_rec_test_core_decode_files_ragged": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "irec_rec_test_core_encode_files": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "irec_rec_test_core_decode_files": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "irec_res_device_workspace_bytes": (ctypes.c_size_t, [_i32, _i64]),

@@ -31,6 +31,17 @@ class SplitNotResident(CodingError):
     codes these blocks again -- goes out without sharing; see there for when sharing comes back."""
 
 
+class _RaggedShares:
+    """K [N, T] seen as _check_packed indexes it, K[:, r, :]: the columns [first[r], first[r + 1]) of call r."""
+
+    def __init__(self, K, first):
+        self.K, self.first = K, first
+
+    def __getitem__(self, key):
+        r = key[1]
+        return self.K[:, self.first[r]:self.first[r + 1]]
+
+
 class PendingCode:
     """Result of one asynchronous encode call: everything stays on the device until the host asks.
     K [n_blocks] int32, idx [n_blocks, max_K] int32 (rows in layout order), sample (input shape)."""
@@ -151,6 +162,59 @@ class PendingCode:
         if pendings[0].min_indices:
             both[..., 0].clamp_(min=pendings[0].min_indices)
         return both[..., 0], both[..., 1:]
+
+    @staticmethod
+    def _joined_ragged(pendings):
+        """The rows of R calls that share a tensor count and seed but NOT a layout (the two levels of the lossy model: 13 and 302 blocks
+        per image) as ONE device tensor [N, T, 1 + width], image-major, K in column 0: call r's blocks of image i in natural block order
+        from row i T + first[r].  Returns (tensor, blocks_per_res)."""
+        lay = pendings[0].lay
+        if any(p.lay.natural is None or p.lay.n_tensors != lay.n_tensors or p.lay.seed != lay.seed for p in pendings):
+            raise CodingError("gather_packed_ragged needs whole calls on one tensor count and seed")
+        width = max(p.idx.shape[1] for p in pendings)
+        rows = []
+        for p in pendings:
+            r = torch.cat([p.K[:, None], p.idx], dim=1)
+            if r.shape[1] < width + 1:
+                r = torch.nn.functional.pad(r, (0, width + 1 - r.shape[1]))
+            rows.append(r)
+        n, bpr = lay.n_tensors, [p.lay.blocks_per_tensor for p in pendings]
+        cache = lay.__dict__.setdefault("_ragged_index", {})
+        key = tuple((p.lay.n, p.lay.block_size) for p in pendings)       # (`natural` is a function of these and the tensor count)
+        if key not in cache:
+            base = np.concatenate([[0], np.cumsum([p.lay.n_blocks for p in pendings])])
+            sel = np.concatenate([base[r] + np.asarray(p.lay.natural, dtype=np.int64).reshape(n, bpr[r]) for r, p in enumerate(pendings)], axis=1)
+            cache[key] = torch.from_numpy(np.ascontiguousarray(sel.reshape(-1))).to(pendings[0].K.device)
+        return torch.cat(rows, dim=0).index_select(0, cache[key]).reshape(n, sum(bpr), width + 1), bpr
+
+    @staticmethod
+    def _check_packed_ragged(pendings, K, bpr):
+        """_check_packed on K [N, T] (numpy): every call's checks on its own share of the partition counts read back."""
+        first = np.concatenate([[0], np.cumsum(bpr)])
+        PendingCode._check_packed(pendings, _RaggedShares(K, first))
+
+    @staticmethod
+    def gather_packed_ragged(pendings):
+        """gather_packed for calls on DIFFERENT layouts: (K [N, T] int32, idx [N, T, max_K] int32, blocks_per_res), numpy, max_K the widest
+        call's, T = sum(blocks_per_res) -- ONE gather on the device and ONE device-to-host copy.  irec.io.encode_files_ragged takes them
+        as they are.  The checks of gather_packed run on each call's own share of K."""
+        both, bpr = PendingCode._joined_ragged(pendings)
+        both = both.cpu().numpy()
+        K, idx = both[..., 0], both[..., 1:]
+        PendingCode._check_packed_ragged(pendings, K, bpr)
+        if pendings[0].min_indices:
+            K = np.maximum(K, pendings[0].min_indices)
+        return np.ascontiguousarray(K), np.ascontiguousarray(idx), bpr
+
+    @staticmethod
+    def gather_packed_ragged_device(pendings):
+        """gather_packed_ragged with the indices left on the device: the K [N, T] and idx [N, T, max_K] VIEWS of the one joined tensor, which
+        irec.io.encode_files_device_ragged takes as they are (strided).  Only K is read back, for the same checks."""
+        both, bpr = PendingCode._joined_ragged(pendings)
+        PendingCode._check_packed_ragged(pendings, both[..., 0].cpu().numpy(), bpr)
+        if pendings[0].min_indices:
+            both[..., 0].clamp_(min=pendings[0].min_indices)
+        return both[..., 0], both[..., 1:], bpr
 
     @staticmethod
     def _all_gave_up(pendings):

@@ -300,6 +300,110 @@ def _decompress_images(model, paths, batch, strict, lossless):
     return images, rows
 
 
+# ---- the two-level lossy model (irec.models.lossy.Large2LevelVAE): the same two drivers over ragged files -------------------------
+def compress_images_lossy(model, sampler, images, names, seed, block_size, out_dir, batch=None, rec_on_device=False):
+    """compress_images for Large2LevelVAE and its coder `sampler`: images [n, 3, H, W] on the model's device, in batches through
+    model.compress_rec (two coder launches per batch, one read-back), one NAME.rec per image -- byte for byte the file
+    model.compress(file_path, ...) writes for it -- read back and compared with the rows the files were built from.
+    rec_on_device: the files are built and checked on the device (irec.io.encode_files_device_ragged / decode_files_device_ragged)
+    instead of on host threads, the default.  Returns one dict per image with compress_images' keys."""
+    from .io import decode_files_device_ragged, decode_files_ragged
+    os.makedirs(out_dir, exist_ok=True)
+    n = images.shape[0]
+    batch = n if not batch else int(batch)
+    S = model._max_index(sampler)
+    rows = []
+    for lo in range(0, n, batch):
+        chunk = images[lo:lo + batch]
+        m, _, h, w = chunk.shape
+        t0 = time.perf_counter()
+        try:
+            (blob, off, _), (K, idx, bpr) = model.compress_rec(chunk, seed, sampler, block_size=block_size, rec_on_device=rec_on_device,
+                                                               return_pendings=True)
+        except CodingError as e:                         # compression_performance.py:375-377: log and move on
+            rows += [{"name": names[lo + i], "error": str(e)} for i in range(m)]
+            continue
+        t_compress = time.perf_counter() - t0
+        t1 = time.perf_counter()
+        host, off_host = (blob.cpu().numpy(), off.cpu().numpy()) if rec_on_device else (blob, off)
+        paths = [os.path.join(out_dir, f"{nm}.rec") for nm in names[lo:lo + m]]
+        mv = memoryview(host)
+        for i, path in enumerate(paths):
+            with open(path, "wb") as fh:
+                fh.write(mv[off_host[i]:off_host[i + 1]])
+        back = [open(path, "rb").read() for path in paths]
+        sizes = np.array([len(b) for b in back], dtype=np.int64)
+        off2 = np.concatenate([[0], np.cumsum(sizes)])
+        blob2 = np.frombuffer(b"".join(back), dtype=np.uint8)
+        want = np.array([seed, block_size, h, w, 3], dtype=np.int64)
+        if rec_on_device:
+            hdr, K2, idx2 = decode_files_device_ragged(torch.from_numpy(blob2.copy()).to(blob.device), off2, bpr, idx.shape[2])
+            live = torch.arange(idx.shape[2], device=idx.device)[None, None, :] < K[..., None]
+            same = ((K2 == K).all(dim=1) & ((idx2 == idx) | ~live).all(dim=2).all(dim=1) &
+                    (hdr[:, [0, 1, 3, 4, 5]] == torch.from_numpy(want).to(hdr.device)).all(dim=1)).cpu().numpy()
+            n_idx = K.sum(dim=1).cpu().numpy()
+        else:
+            hdr, K2, idx2 = decode_files_ragged(blob2, off2, bpr, idx.shape[2])
+            live = np.arange(idx.shape[2])[None, None, :] < K[..., None]
+            same = (K2 == K).all(axis=1) & ((idx2 == idx) | ~live).all(axis=(1, 2)) & (hdr[:, [0, 1, 3, 4, 5]].astype(np.int64) == want).all(axis=1)
+            n_idx = K.sum(axis=1)
+        t_host = (time.perf_counter() - t1) / m
+        rows += [{"name": names[lo + i], "comp_codelength": int(sizes[i]) * 8, "comp_lossy_bpp": int(sizes[i]) * 8 / (h * w),
+                  "comp_code_bpd": int(sizes[i]) * 8 / (h * w * 3), "code_nats": int(n_idx[i]) * float(np.log(S)),
+                  "n_indices": int(n_idx[i]), "indices_recovered": bool(same[i]), "comp_time": t_compress / m + t_host} for i in range(m)]
+    return rows
+
+
+def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_on_device=False):
+    """decompress_images for Large2LevelVAE and its coder `sampler`: .rec files -> (images, rows), the files grouped by header (seed,
+    shape, block structure) and each group decoded in batches by model.decompress_rec -- on host threads, or with rec_on_device on
+    the device -- with one read-back per batch, the per-image status.  images, rows and strict as decompress_images has them."""
+    dev = next(model.parameters()).device
+    datas = []
+    for path in paths:
+        with open(path, "rb") as fh:
+            datas.append(fh.read())
+    infos, groups = rec_file_groups(datas)
+    images, rows = [None] * len(paths), [None] * len(paths)
+    for i, w in enumerate(infos):
+        if w is None:
+            rows[i] = {"name": os.path.basename(paths[i]), "status": 4, "error": status_text(4)}     # IREC_REC_E_TRUNCATED_HEADER
+    for (seed, (h, w_, c), R, bpt), members in groups.items():
+        fits = R == 2 and c == 3 and h % 64 == 0 and w_ % 64 == 0 and h > 0 and w_ > 0 and \
+            list(infos[members[0]]["bpt"]) == model.blocks_per_res((1, c, h, w_), sampler.block_size)
+        step = len(members) if not batch else int(batch)
+        for lo in range(0, len(members), step):
+            part = members[lo:lo + step]
+            t0 = time.perf_counter()
+            if fits:
+                sizes = np.array([len(datas[i]) for i in part], dtype=np.int64)
+                off = np.concatenate([[0], np.cumsum(sizes)])
+                host = np.frombuffer(b"".join(datas[i] for i in part), dtype=np.uint8)
+                max_K = max([1] + [m for i in part for m in infos[i]["max_partitions"] if m <= 65536])
+                blob = torch.from_numpy(host.copy()).to(dev) if rec_on_device else host
+                rec, status = model.decompress_rec(blob, off, seed, (len(part), c, h, w_), sampler, max_K=max_K, strict=False,
+                                                   rec_on_device=rec_on_device)
+                texts = [status_text(int(st)) if st else "" for st in status]
+            else:                                                       # IREC_REC_E_STRUCTURE: not this model's block structure
+                rec, status = torch.zeros((len(part), 3, h, w_), device=dev), [17] * len(part)
+                texts = [f"{status_text(17)}: {R} residual blocks of {bpt} blocks for a {h} x {w_} x {c} image do not match the model"] * len(part)
+            dt = (time.perf_counter() - t0) / len(part)
+            for k, i in enumerate(part):
+                images[i] = rec[k] if status[k] == 0 else torch.zeros_like(rec[k])
+                rows[i] = {"name": os.path.basename(paths[i]), "seed": seed, "image_shape": (h, w_, c), "block_size": infos[i]["block_size"],
+                           "status": int(status[k]), "decomp_time": dt}
+                if status[k]:
+                    rows[i]["error"] = texts[k]
+    if strict:
+        for i, row in enumerate(rows):
+            if row["status"]:
+                raise CodingError(f"{row['error']} (image {i})")
+    shapes = {tuple(im.shape) for im in images if im is not None}
+    if len(shapes) == 1 and all(im is not None for im in images):
+        return torch.stack(images, dim=0), rows
+    return images, rows
+
+
 def compress_sharded(model, all_images, seed, block_size, out_dir, rank=0, world=1, dist=None, batch=None):
     """Config 3 (300 images over G GPUs): this rank compresses images rank, rank + G, ...; every rank gets the [n_images]
     vectors of file bits and code nats back (one all_gather each, <= 38 floats per rank: latency only)."""

@@ -331,6 +331,177 @@ def decode_files_device(blob, offsets, n_res_blocks, blocks_per_res, max_K):
     return hdr.to(torch.int64) & 0xFFFFFFFF, K, idx
 
 
+# ---- residual blocks of differing sizes ("ragged": the two-level lossy model codes 13 blocks at level 2 and 302 at level 1) ---------------
+# K [N, T], idx [N, T, max_K], T = sum(blocks_per_res); block j of residual block r of image i is row i T + first[r] + j.
+def _ragged_layout(blocks_per_res, what):
+    bpr = np.ascontiguousarray(np.asarray(blocks_per_res, dtype=np.int64).reshape(-1))
+    if bpr.size < 1 or (bpr < 1).any() or int(bpr.sum()) > _lib.INT32_MAX:
+        raise ValueError(f"{what}: blocks_per_res must hold at least one entry, every entry >= 1, their sum an int32 (got {list(bpr)})")
+    return bpr.astype(np.int32), int(bpr.sum())
+
+
+def encode_files_ragged(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, n_threads=0):
+    """encode_files for residual blocks of differing sizes (irec_rec_encode_files_ragged): K [N, T] int32, idx [N, T, max_K] int32,
+    T = sum(blocks_per_res).  Returns (blob uint8, offsets int64 [N + 1]); file i is byte for byte what write_compressed_code writes for
+    image i's lists."""
+    lib = _lib.load()
+    bpr, T = _ragged_layout(blocks_per_res, "encode_files_ragged")
+    K = np.ascontiguousarray(K, dtype=np.int32)
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    if K.ndim != 2 or K.shape[1] != T or idx.ndim != 3 or idx.shape[:2] != K.shape:
+        raise ValueError(f"encode_files_ragged: K {K.shape} and idx {idx.shape} are not [N, {T}] and [N, {T}, max_K]")
+    n, max_K = K.shape[0], idx.shape[2]
+    h, w, c = (int(v) for v in image_shape)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    cap = n * (64 + 16 * bpr.size) + 2 * int(K.sum()) + 16 * K.size + 1024
+    while True:
+        out = np.empty(cap, dtype=np.uint8)
+        total = lib.irec_rec_encode_files_ragged(int(seed), int(block_size), int(max_index), h, w, c, n, bpr.size, bpr.ctypes.data, max_K,
+                                                 K.ctypes.data, idx.ctypes.data if idx.size else None, out.ctypes.data, cap,
+                                                 offsets.ctypes.data, int(n_threads))
+        if total < 0:
+            raise ValueError(lib.irec_io_last_error().decode())
+        if total <= cap:
+            return out[:total], offsets
+        cap = int(total)
+
+
+def decode_files_ragged(blob, offsets, blocks_per_res, max_K, n_threads=0):
+    """The inverse of encode_files_ragged (irec_rec_decode_files_ragged): (headers [N, 9] uint32, K [N, T], idx [N, T, max_K] with rows
+    zero-filled past K); ValueError naming the first file that is damaged or of another structure."""
+    lib = _lib.load()
+    bpr, T = _ragged_layout(blocks_per_res, "decode_files_ragged")
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = offsets.size - 1
+    hdr = np.zeros((n, 9), dtype=np.uint32)
+    K = np.zeros((n, T), dtype=np.int32)
+    idx = np.zeros((n, T, max(max_K, 1)), dtype=np.int32)
+    st = lib.irec_rec_decode_files_ragged(blob.ctypes.data, offsets.ctypes.data, n, bpr.size, bpr.ctypes.data, int(max_K), hdr.ctypes.data,
+                                          K.ctypes.data, idx.ctypes.data, int(n_threads))
+    if st != 0:
+        raise ValueError(lib.irec_io_last_error().decode())
+    return hdr, K, idx[..., :max_K]
+
+
+def _row_strides(K, idx):
+    """_block_strides for [N, T] and [N, T, max_K]: row b = i T + t at K[b k_stride], idx[b idx_stride + .]."""
+    n, T = K.shape
+    max_K = idx.shape[2]
+    ks = K.stride(1) if K.numel() else 1
+    if K.numel() and (ks < 1 or K.stride() != (T * ks, ks)):
+        K, ks = K.contiguous(), 1
+    ist = idx.stride(1) if idx.numel() else max(max_K, 1)
+    if idx.numel() and (ist < max_K or idx.stride(2) != 1 or idx.stride(0) != T * ist):
+        idx, ist = idx.contiguous(), max_K
+    return K, int(ks), idx, int(ist)
+
+
+def _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, out):
+    """One irec_rec_encode_files_device_ragged call on the current stream, nothing read back: (offsets int64 [N + 1], status int32 [N], both
+    views of `both`, which one copy fetches).  The bytes are in `out` only if offsets[N] <= out.numel()."""
+    import torch
+    lib = _lib.load()
+    bpr, T = _ragged_layout(blocks_per_res, "encode_files_device_ragged")
+    if not (K.is_cuda and idx.is_cuda and K.dtype == torch.int32 and idx.dtype == torch.int32):
+        raise ValueError("encode_files_device_ragged takes CUDA int32 tensors")
+    if K.dim() != 2 or K.shape[1] != T or idx.dim() != 3 or tuple(idx.shape[:2]) != tuple(K.shape):
+        raise ValueError(f"encode_files_device_ragged: K {tuple(K.shape)} and idx {tuple(idx.shape)} are not [N, {T}] and [N, {T}, max_K]")
+    n, max_K = K.shape[0], idx.shape[2]
+    h, w, c = (int(v) for v in image_shape)
+    K, ks, idx, ist = _row_strides(K, idx)
+    dev = K.device
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(lib.irec_rec_device_workspace_bytes(n, bpr.size), 8), dtype=torch.uint8, device=dev)
+        both = torch.empty(n + 1 + (n + 1) // 2, dtype=torch.int64, device=dev)          # offsets, then status: one read-back
+        offsets, status = both[:n + 1], both[n + 1:].view(torch.int32)[:n]
+        st = lib.irec_rec_encode_files_device_ragged(int(seed), int(block_size), int(max_index), h, w, c, n, bpr.size, bpr.ctypes.data, max_K,
+                                                     K.data_ptr(), ks, idx.data_ptr() if idx.numel() else None, ist,
+                                                     out.data_ptr() if out.numel() else None, out.numel(), offsets.data_ptr(),
+                                                     status.data_ptr() if n else None, ws.data_ptr(), ws.numel(),
+                                                     torch.cuda.current_stream().cuda_stream)
+    if st == _lib.IREC_E_INVALID:
+        raise ValueError(lib.irec_last_error().decode())
+    _lib.check(st, "irec_rec_encode_files_device_ragged")
+    return offsets, status, both
+
+
+def encode_files_device_ragged(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, out=None):
+    """encode_files_ragged on the device (irec_rec_encode_files_device_ragged): K [N, T], idx [N, T, max_K] int32 CUDA tensors, contiguous
+    or views of one joined [rows][1 + width] tensor (PendingCode.gather_packed_ragged_device).  Returns (blob uint8, offsets int64
+    [N + 1]) as CUDA tensors, byte for byte what encode_files_ragged gives; the only host synchronisation is ONE read-back of offsets
+    and status.  out: a CUDA uint8 buffer to write into (a short one costs a second run at the size the first one reports)."""
+    import torch
+    bpr, T = _ragged_layout(blocks_per_res, "encode_files_device_ragged")
+    if out is None:
+        n, max_K = (K.shape[0], idx.shape[2]) if K.dim() == 2 and idx.dim() == 3 else (0, 0)
+        # irec_io.cpp's own first allowance: 64 + 40 bits per symbol and terminator, per stream
+        cap = n * (28 + 16 * bpr.size + sum((64 + 40 * (int(b) + 1)) // 8 + 1 + (64 + 40 * (int(b) * max_K + 1)) // 8 + 1 for b in bpr))
+        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=K.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == K.device):
+        raise ValueError("encode_files_device_ragged: out must be a contiguous CUDA uint8 tensor on the indices' device")
+    n = K.shape[0]
+    for _attempt in range(2):
+        offsets, _, both = _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, bpr, out)
+        host = both.cpu().numpy()
+        _raise_first_status(host[n + 1:].view(np.int32)[:n])
+        total = int(host[n])
+        if total <= out.numel():
+            return out[:total], offsets
+        out = torch.empty(total, dtype=torch.uint8, device=K.device)                       # exactly what the first run asked for
+    raise ValueError("irec_rec_encode_files_device_ragged: the files did not fit the size the call itself reported")
+
+
+def _decode_files_device_ragged_launch(blob, offsets, blocks_per_res, max_K, on_device=False):
+    """One irec_rec_decode_files_device_ragged call on the current stream: (headers int32 [N, 9] holding the uint32 words, K [N, T],
+    idx [N, T, max_K], status int32 [N]) on the device; `offsets` and `on_device` as _decode_files_device_launch takes them."""
+    import torch
+    lib = _lib.load()
+    bpr, T = _ragged_layout(blocks_per_res, "decode_files_device_ragged")
+    if not (blob.is_cuda and blob.dtype == torch.uint8):
+        raise ValueError("decode_files_device_ragged takes a CUDA uint8 tensor")
+    blob = blob.contiguous()
+    dev = blob.device
+    max_K = int(max_K)
+    off_dev = None
+    if on_device and hasattr(offsets, "is_cuda") and offsets.is_cuda:
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError("decode_files_device_ragged: device offsets must be int64 [N + 1]")
+        n = offsets.numel() - 1
+        off_dev = torch.cummax(offsets.to(dev).clamp(0, blob.numel()), dim=0).values.contiguous()
+    else:
+        off_host = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
+        n = off_host.size - 1
+        # the kernels read no byte outside [offsets[i], offsets[i + 1]): those ranges must lie inside the blob
+        if n < 0 or off_host[0] < 0 or (np.diff(off_host) < 0).any() or off_host[-1] > blob.numel():
+            raise ValueError("decode_files_device_ragged: offsets must be non-decreasing and end inside the blob")
+    with torch.cuda.device(dev):
+        offsets = off_dev if off_dev is not None else torch.from_numpy(off_host.copy()).to(dev)   # (a copy: the caller's array may be read-only)
+        ws = torch.empty(max(lib.irec_rec_device_workspace_bytes(n, bpr.size), 8), dtype=torch.uint8, device=dev)
+        hdr = torch.zeros((n, 9), dtype=torch.int32, device=dev)
+        K = torch.empty((n, T), dtype=torch.int32, device=dev)
+        idx = torch.empty((n, T, max_K), dtype=torch.int32, device=dev)
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        st = lib.irec_rec_decode_files_device_ragged(blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, bpr.size,
+                                                     bpr.ctypes.data, max_K, hdr.data_ptr(), K.data_ptr(),
+                                                     idx.data_ptr() if idx.numel() else None, status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     torch.cuda.current_stream().cuda_stream)
+    if st == _lib.IREC_E_INVALID:
+        raise ValueError(lib.irec_last_error().decode())
+    _lib.check(st, "irec_rec_decode_files_device_ragged")
+    return hdr, K, idx, status[:n]
+
+
+def decode_files_device_ragged(blob, offsets, blocks_per_res, max_K):
+    """decode_files_ragged on the device (irec_rec_decode_files_device_ragged): blob uint8 CUDA tensor, offsets [N + 1] (CUDA, CPU or
+    numpy).  Returns CUDA tensors (headers [N, 9] int64, K [N, T] int32, idx [N, T, max_K] int32 with rows zero-filled past K);
+    ValueError naming the first damaged file."""
+    import torch
+    hdr, K, idx, status = _decode_files_device_ragged_launch(blob, offsets, blocks_per_res, max_K)
+    _raise_first_status(status.cpu().numpy())
+    return hdr.to(torch.int64) & 0xFFFFFFFF, K, idx
+
+
 def rec_header_words(data):
     """The header of one .rec file from its bytes (a pure function: RecHeader over the 28 + 16 R header bytes): a dict of seed,
     image_shape (h, w, c), block_size, max_index, R, bpt (blocks per residual block, a list), max_partitions (a list), or None for

@@ -8,12 +8,16 @@ As with the RVAE shim, only the hand-off is modelled: the Balle-style analysis /
 SURVEY.md §2 rows 12-14).  Latent shapes follow the reference: level 1 = [1, H/16, W/16, 196], level 2 = [1, H/64, W/64, 128]
 (large_2_level_vae.py:313, compress_with_lossy_model.py:36-37), handed to the coder in NHWC order.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import _lib
+from ..coding.beam_search_coder import MorePartitionsNeeded, PendingCode, SplitNotResident
+from ..coding.utils import CodingError
 from ..io import read_compressed_code, write_compressed_code
-from .resnet_vae import _Normal, _nchw, _nhwc, deterministic_transforms
+from .resnet_vae import STATUS_HEADER, STATUS_ROWS, ModelError, _Normal, _nchw, _nhwc, deterministic_transforms, status_text
 
 
 def _down(cin, cout, n):
@@ -49,6 +53,7 @@ class Large2LevelVAE(nn.Module):
         self._prior_log_scale_head = nn.Conv2d(f2, f2, 3, padding=1)
         self._level_1_posterior_loc_combiner = nn.Conv2d(2 * f1, f1, 1)
         self._level_1_posterior_log_scale_combiner = nn.Conv2d(2 * f1, f1, 1)
+        self._rows_cache = {}
 
     def prior_base(self, batch_size, height, width):
         """large_2_level_vae.py:312-313."""
@@ -64,9 +69,15 @@ class Large2LevelVAE(nn.Module):
 
     @torch.no_grad()
     def forward(self, tensor, sampling_fn=None):
-        """large_2_level_vae.py:320-404.  tensor: [1, 3, H, W]; returns ([level_2_indices, level_1_indices], reconstruction)."""
+        """large_2_level_vae.py:320-404.  tensor: [N, 3, H, W] (the reference's N = 1, or a batch that `sampling_fn` codes with
+        batched=True); returns ([level_2_indices, level_1_indices], reconstruction)."""
         if sampling_fn is None:
             raise NotImplementedError("training / sampling passes are outside the compression shim")
+        block_indices, y = self._code_levels(tensor, sampling_fn)
+        return block_indices, self.synthesis_transform(_nchw(y))
+
+    def _code_levels(self, tensor, sampling_fn):
+        """`forward` up to the coded level-1 sample: ([level_2_indices, level_1_indices], y NHWC)."""
         batch_size, _, height, width = tensor.shape
         l1_post_loc, l1_post_log_scale = torch.chunk(self.analysis_transform(tensor), 2, dim=1)
         l2_post_loc, l2_post_log_scale = torch.chunk(self.hyper_analysis_transform(l1_post_loc), 2, dim=1)
@@ -80,7 +91,7 @@ class Large2LevelVAE(nn.Module):
         self.level_1_prior = _Normal(_nhwc(l1_prior_loc), _nhwc(l1_prior_scale))
         self.level_1_posterior = _Normal(_nhwc(loc), _nhwc(F.softplus(log_scale) + 1e-7))
         level_1_indices, y = sampling_fn(target=self.level_1_posterior, coder=self.level_1_prior)            # :394-395
-        return [level_2_indices, level_1_indices], self.synthesis_transform(_nchw(y))
+        return [level_2_indices, level_1_indices], y
 
     def compress(self, file_path, image, seed, sampler, block_size, max_index):
         """large_2_level_vae.py:406-419.  image: [H, W, 3] tensor (the reference's layout)."""
@@ -105,3 +116,209 @@ class Large2LevelVAE(nn.Module):
             self.level_1_prior = _Normal(_nhwc(l1_prior_loc), _nhwc(l1_prior_scale))
             y = sampler.decode(self.level_1_prior, seed=seed, indices=block_indices[1])                       # :451
             return self.synthesis_transform(_nchw(y))
+
+    # ---- the packed path: a batch per call, indices as rows (K [N, T], idx [N, T, max_K]), ragged .rec files ----------------------
+    # The two levels differ in size (a Kodak image: 13 coder blocks at level 2, 302 at level 1), so an image is T = sum(blocks_per_res)
+    # rows, level 2's first -- file order, block_indices = [level_2, level_1].
+    def blocks_per_res(self, image_shape, block_size):
+        """[level-2 blocks, level-1 blocks] of an image (Coder.split, coder.py:69-83).  image_shape: [N, 3, H, W]."""
+        _, _, h, w = image_shape
+        dims = [(h // 64) * (w // 64) * self.level_2_filters, (h // 16) * (w // 16) * self.level_1_filters]
+        return [1 if block_size is None else -(-n // int(block_size)) for n in dims]
+
+    @staticmethod
+    def _max_index(sampler):
+        """The header's max_index word: the samples a step chooses among (the sequential coder's are its sampler's)."""
+        return sampler.sampler.n_samples() if getattr(sampler, "sampler", None) is not None else sampler.n_samples
+
+    def _compress_device(self, images, seed, sampler):
+        """The coding half of a batched compress, on the device with no host synchronisation: ([level-2, level-1] PendingCode, y).  The
+        two calls are sequential (level 1's prior comes from the coded level-2 sample) and deferred."""
+        sampling_fn = lambda target, coder: sampler.encode(target, coder, seed=seed, batched=True, defer=True)  # noqa: E731
+        with deterministic_transforms():
+            return self._code_levels(images, sampling_fn)
+
+    def _compress_gather(self, images, seed, sampler, gather):
+        """(gather(pendings), reconstruction).  The rows are read back BEFORE the synthesis transform is launched, so that what the caller
+        does with them on the host (the files' arithmetic coder) runs while the device computes the reconstruction, as the list path's
+        write_compressed_code does; a pass that has to be coded again has not paid for a reconstruction either."""
+        for _attempt in range(6):
+            pendings, y = self._compress_device(images, seed, sampler)
+            try:
+                gathered = gather(pendings)
+            except (MorePartitionsNeeded, SplitNotResident):
+                continue
+            with deterministic_transforms():
+                return gathered, self.synthesis_transform(_nchw(y))   # a block needs more index slots than the coder's hint (now raised), or a shared block's partners were not
+                           # resident (the coder's next call goes out unshared): code again
+        raise MorePartitionsNeeded(sampler._max_K_hint + 1)
+
+    @torch.no_grad()
+    def compress_packed(self, images, seed, sampler):
+        """`compress` for a batch [N, 3, H, W], the indices left packed: (K [N, T], idx [N, T, max_K], blocks_per_res, reconstruction),
+        K / idx int32 numpy -- ONE device-to-host copy, no Python object per index.  irec.io.encode_files_ragged takes them."""
+        (K, idx, bpr), reconstruction = self._compress_gather(images, seed, sampler, PendingCode.gather_packed_ragged)
+        return K, idx, bpr, reconstruction
+
+    @torch.no_grad()
+    def compress_rec(self, images, seed, sampler, block_size=None, rec_on_device=False, return_pendings=False):
+        """A batch to its .rec files: (blob uint8, offsets int64 [N + 1], reconstruction), image i's file blob[offsets[i]:offsets[i + 1]]
+        byte for byte what `compress(file_path, ...)` writes for it.  rec_on_device=False (the default: an arithmetic coder's stream is
+        serial, and Kodak-size streams are long): one packed read-back, then irec.io.encode_files_ragged on host threads; blob and
+        offsets are numpy.  rec_on_device=True: the rows stay on the device (PendingCode.gather_packed_ragged_device,
+        irec.io.encode_files_device_ragged), only K, the offsets and the statuses are read back; blob and offsets are CUDA tensors.
+        block_size: the header's block-size word (default: the coder's own; 0 for a coder without one).
+        return_pendings: also the rows the files were built from, ((blob, offsets, reconstruction), (K, idx, blocks_per_res))."""
+        from ..io import encode_files_device_ragged, encode_files_ragged
+        _, _, height, width = images.shape
+        gather = PendingCode.gather_packed_ragged_device if rec_on_device else PendingCode.gather_packed_ragged
+        (K, idx, bpr), reconstruction = self._compress_gather(images, seed, sampler, gather)
+        if block_size is None:
+            block_size = sampler.block_size if sampler.block_size is not None else 0
+        encode = encode_files_device_ragged if rec_on_device else encode_files_ragged
+        blob, offsets = encode(seed, (height, width, 3), block_size, K, idx, self._max_index(sampler), bpr)
+        return ((blob, offsets, reconstruction), (K, idx, bpr)) if return_pendings else (blob, offsets, reconstruction)
+
+    def _packed_rows(self, n, bpr, device):
+        """Per level r the int32 device map (image i, block j) -> row i T + first[r] + j of packed K [N, T] arrays."""
+        key = (n, tuple(bpr), str(device))
+        if key not in self._rows_cache:
+            if len(self._rows_cache) > 16:
+                self._rows_cache.clear()
+            T, first = sum(bpr), np.concatenate([[0], np.cumsum(bpr)])
+            i = torch.arange(n, dtype=torch.int32).reshape(n, 1)
+            self._rows_cache[key] = [(i * T + int(first[r]) + torch.arange(b, dtype=torch.int32).reshape(1, b)).reshape(-1).contiguous().to(device)
+                                     for r, b in enumerate(bpr)]
+        return self._rows_cache[key]
+
+    def _decompress_device(self, K, idx, seed, image_shape, sampler, status):
+        """The generative pass driven by rows on the device: K [N, T], idx [N, T, max_K] int32 (contiguous, or the views of one joined
+        tensor), each level's coder reading its rows in place and accumulating its verdict on them into `status` (int32 [N], device).
+        No host synchronisation."""
+        n, _, height, width = image_shape
+        bpr = self.blocks_per_res(image_shape, sampler.block_size)
+        if K.dim() != 2 or tuple(K.shape) != (n, sum(bpr)) or idx.dim() != 3 or tuple(idx.shape[:2]) != tuple(K.shape):
+            raise ModelError(f"K {tuple(K.shape)} / idx {tuple(idx.shape)} are not [N = {n}, T = {sum(bpr)}] and [N, T, max_K]: images of shape "
+                             f"{tuple(image_shape)} are coded in {bpr} blocks")
+        rows = self._packed_rows(n, bpr, K.device)
+        with deterministic_transforms():
+            l2_prior_loc, l2_prior_scale = self._level_2_prior(n, height, width)
+            self.level_2_prior = _Normal(_nhwc(l2_prior_loc), _nhwc(l2_prior_scale))
+            z = sampler.decode(self.level_2_prior, None, seed=seed, batched=True, packed=(K, idx, rows[0]), status=status)
+            l1_prior_loc, l1_prior_scale, _ = self._level_1_prior(_nchw(z))
+            self.level_1_prior = _Normal(_nhwc(l1_prior_loc), _nhwc(l1_prior_scale))
+            y = sampler.decode(self.level_1_prior, None, seed=seed, batched=True, packed=(K, idx, rows[1]), status=status)
+            return self.synthesis_transform(_nchw(y))
+
+    @staticmethod
+    def _raise_status(status):
+        """CodingError for the first image with a nonzero joined status (BidirectionalResNetVAE.decompress_rec has the encoding)."""
+        bad = np.flatnonzero(status)
+        if bad.size:
+            raise CodingError(f"{status_text(int(status[bad[0]]))} (image {int(bad[0])})")
+
+    @staticmethod
+    def _to_device(a, device):
+        return a.to(device) if hasattr(a, "is_cuda") else torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+    @torch.no_grad()
+    def decompress_packed(self, K, idx, seed, image_shape, sampler, strict=True):
+        """`decompress` for packed rows (K [N, T], idx [N, T, max_K] int32: CUDA tensors read where they lie, or numpy arrays uploaded
+        once): ONE read-back, the per-image status.  strict: CodingError naming the first image whose rows cannot be decoded;
+        strict=False: (reconstruction, status int32 numpy [N]) -- 0, or STATUS_ROWS + irec_rows_status; the images with status 0 are
+        what they would be without the others."""
+        device = self._prior_base.device
+        K, idx = self._to_device(K, device), self._to_device(idx, device)
+        status = torch.zeros(int(image_shape[0]), dtype=torch.int32, device=device)
+        reconstruction = self._decompress_device(K, idx, seed, image_shape, sampler, status)
+        host = status.cpu().numpy()
+        host = np.where(host != 0, host + STATUS_ROWS, 0).astype(np.int32)
+        if strict:
+            self._raise_status(host)
+            return reconstruction
+        return reconstruction, host
+
+    @staticmethod
+    def _decode_files_host(blob, offsets, bpr, max_K):
+        """irec.io.decode_files_ragged with a verdict per file: (headers, K, idx, status int32 [N]).  The host reader stops at the first
+        file it refuses; only then is every file read alone, a refused one leaving zero rows and the irec_rec_status of the reader's
+        words for it (the first of a class that shares its text)."""
+        from ..io.utils import _REC_STATUS_TEXT, decode_files_ragged
+        n = len(offsets) - 1
+        try:
+            hdr, K, idx = decode_files_ragged(blob, offsets, bpr, max_K)
+            return hdr, K, idx, np.zeros(n, dtype=np.int32)
+        except ValueError:
+            pass
+        hdr, K, idx = np.zeros((n, 9), np.uint32), np.zeros((n, sum(bpr)), np.int32), np.zeros((n, sum(bpr), max_K), np.int32)
+        status = np.zeros(n, dtype=np.int32)
+        for i in range(n):
+            one = blob[int(offsets[i]):int(offsets[i + 1])]
+            try:
+                hdr[i], K[i], idx[i] = (a[0] for a in decode_files_ragged(one if one.size else np.zeros(1, np.uint8), np.array([0, one.size]), bpr,
+                                                                         max_K, n_threads=1))
+            except ValueError as e:
+                text = str(e).rsplit(" (image", 1)[0]
+                status[i] = next((code for code, t in sorted(_REC_STATUS_TEXT.items()) if t == text and code >= 4), 16)
+        return hdr, K, idx, status
+
+    @staticmethod
+    def _files_max_K_device(blob, offsets, R=2):
+        """Index slots per block that decode the files of a blob on the device (irec.io.rec_files_max_K): only the 28 + 16 R header bytes
+        of every file are gathered and copied to the host."""
+        from ..io.utils import rec_files_max_K
+        dev, hb = blob.device, 28 + 16 * R
+        off = offsets.to(dev) if hasattr(offsets, "is_cuda") else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev)
+        n = off.numel() - 1
+        if n < 1 or blob.numel() < 1:
+            return 1
+        at = (off[:-1, None] + torch.arange(hb, device=dev)).clamp_(0, blob.numel() - 1)
+        whole = (off[1:] - off[:-1] >= hb) & (off[:-1] >= 0) & (off[1:] <= blob.numel())          # a shorter file: a zero header, no words
+        head = blob.reshape(-1)[at] * whole[:, None].to(torch.uint8)
+        return rec_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb)
+
+    @torch.no_grad()
+    def decompress_rec(self, blob, offsets, seed, image_shape, sampler, max_K=None, strict=True, rec_on_device=False):
+        """The inverse of compress_rec: N .rec files (file i = blob[offsets[i]:offsets[i + 1]]) to reconstructions [N, 3, H, W].
+        rec_on_device=False: the files are read on host threads (irec.io.decode_files_ragged; blob / offsets numpy or tensors) and the
+        rows uploaded once; rec_on_device=True: blob is a CUDA tensor and the rows never leave the device
+        (irec.io.decode_files_device_ragged's launch form).  Either way the headers are checked against seed, image_shape and R = 2,
+        each level's coder reads its rows in place and checks them on the device, and there is ONE read-back, the per-image status, in
+        the encoding of BidirectionalResNetVAE.decompress_rec: 0 ok; 1 .. 18 irec_rec_status; STATUS_HEADER; STATUS_ROWS +
+        irec_rows_status; first cause in that order.  strict: CodingError with the cause, "(image i)" appended; strict=False:
+        (reconstruction, status int32 numpy [N]), the images with status 0 being what they would be without the others.
+        max_K: index slots per block (None: the largest max_partitions word of the files' headers)."""
+        from ..io.utils import _decode_files_device_ragged_launch, rec_files_max_K
+        n, _, height, width = image_shape
+        bpr = self.blocks_per_res(image_shape, sampler.block_size)
+        device = self._prior_base.device
+        if rec_on_device:
+            if max_K is None:
+                max_K = self._files_max_K_device(blob, offsets)
+            hdr, K, idx, rec_status = _decode_files_device_ragged_launch(blob, offsets, bpr, int(max_K), on_device=True)
+            words = hdr.to(torch.int64).bitwise_and_(0xFFFFFFFF)
+        else:
+            blob_h = np.ascontiguousarray(blob.cpu().numpy() if hasattr(blob, "cpu") else blob, dtype=np.uint8)
+            off_h = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
+            if max_K is None:
+                max_K = rec_files_max_K(blob_h, off_h)
+            hdr, K, idx, rec_status = self._decode_files_host(blob_h, off_h, bpr, int(max_K))
+            both = np.concatenate([K[..., None], idx], axis=2)                                    # one upload for the rows
+            both = torch.from_numpy(both).to(device)
+            K, idx = both[..., 0], both[..., 1:]
+            words = torch.from_numpy(hdr.astype(np.int64)).to(device)
+            rec_status = torch.from_numpy(rec_status).to(device)
+        if len(rec_status) != n:
+            raise ModelError(f"{len(rec_status)} files for images of shape {tuple(image_shape)}")
+        want = torch.tensor([int(seed) & 0xFFFFFFFF, int(height), int(width), 3, 2], dtype=torch.int64).to(device)
+        differs = (torch.cat([words[:, 0:1], words[:, 3:6], words[:, 8:9]], dim=1) != want).any(dim=1)   # seed, height, width, channels, R
+        rows_status = torch.zeros(n, dtype=torch.int32, device=device)
+        reconstruction = self._decompress_device(K, idx, seed, image_shape, sampler, rows_status)
+        joined = torch.where(rec_status != 0, rec_status,
+                             torch.where(differs, torch.full_like(rec_status, STATUS_HEADER),
+                                         torch.where(rows_status != 0, rows_status + STATUS_ROWS, rows_status)))
+        host = joined.cpu().numpy()
+        if strict:
+            self._raise_status(host)
+            return reconstruction
+        return reconstruction, host
