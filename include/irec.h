@@ -519,7 +519,8 @@ typedef enum {
   IREC_REC_E_INDEX_BUDGET = 15,     /* decode: an index stream whose renormalisation budget ran out (no terminator)       */
   IREC_REC_E_MISMATCH = 16,         /* decode: counts or indices do not match the header (also: more values than allowed) */
   IREC_REC_E_STRUCTURE = 17,        /* decode: not n_res_blocks residual blocks of the call's blocks_per_res blocks        */
-  IREC_REC_E_MAX_K = 18             /* decode: a block with more partitions than max_K                                    */
+  IREC_REC_E_MAX_K = 18,            /* decode: a block with more partitions than max_K                                    */
+  IREC_REC_E_TABLE = 19             /* a symbol table whose entries cannot be coded under (the *_tables entry points only) */
 } irec_rec_status;
 size_t irec_rec_device_workspace_bytes(int32_t n_images, int32_t n_res_blocks);
 irec_status irec_rec_encode_files_device(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
@@ -549,6 +550,74 @@ irec_status irec_rec_decode_files_device_ragged(const uint8_t *bytes, const int6
                                                 const int32_t *blocks_per_res /*host [n_res_blocks]*/, int32_t max_K,
                                                 uint32_t *headers /*[n][9]*/, int32_t *K, int32_t *idx, int32_t *status, void *workspace,
                                                 size_t workspace_bytes, void *hip_stream);
+
+/* Empirical symbol tables (the reference's index_counts_file / num_aux_var_counts_file, rec/io/utils.py:31-56, 173-190) on the batched
+ * and the device paths.  A table of n symbols is its cumulative counts cum [n + 1]: cum[0] = 0, cum[n] <= 2^30, symbol m over
+ * [cum[m], cum[m + 1]); symbol 0 is the terminator and symbol m >= 1 the value m - 1, so a table codes the values [0, n - 2].
+ * irec_rec_tables_build: cum from counts [n_symbols]; n_symbols >= 2, every count >= 1 and their sum <= 2^30, else IREC_E_INVALID
+ *   with the cause in irec_last_error and cum untouched.
+ * index_cum [n_index_symbols + 1]: the one table of every index stream.  count_cum [n_count_cum] with count_first [n_res_blocks + 1]:
+ *   one table per residual block, back to back, that of residual block r at count_cum[count_first[r] .. count_first[r + 1]).
+ *   Either of index_cum and count_cum may be NULL: the default model for that kind of stream.
+ * Writing: a kind coded under a table sets its header word (6: counts, 7: indices); with count tables the largest-K words are
+ *   0xFFFFFFFF.  A value without a symbol in its table is IREC_REC_E_INDEX_RANGE / IREC_REC_E_K_RANGE; the header keeps max_index.
+ *   Without tables the bytes are those of the entry points above.
+ * Reading: the FILE's two header words decide, per kind -- set and the call has that table: the table; set and no table:
+ *   IREC_REC_E_COUNT_FILES; clear: the default model, whatever the call brought.  One call reads files of both sorts.  With the count
+ *   word set the bound on K is the table's (n_r - 2) and the call's max_K.
+ * A table is caller data: an entry under which the coder could not terminate (cum[0] != 0, cum[n] > 2^30, cum[m] >= cum[m + 1]) or a
+ *   count_first that leaves count_cum gives that image IREC_REC_E_TABLE; no loop runs on and no read leaves the arrays as described.
+ * The host forms take the ragged layout (blocks_per_res [R]; a uniform one is R equal entries), run on n_threads threads and report
+ *   per image: offsets [n_images + 1] and status [n_images] always written, a file with a nonzero status has no bytes; the writer
+ *   returns the total (also when > cap: nothing written, call again), -1 for bad arguments; the reader zeroes the outputs of an image
+ *   with a nonzero status.  The device forms keep the stride conventions, guarantees and workspace of
+ *   irec_rec_encode_files_device_ragged / irec_rec_decode_files_device_ragged; the tables are DEVICE pointers, blocks_per_res a host
+ *   array: no allocation, no synchronisation, no copy to the host.  An index table of at most IREC_REC_TABLE_LDS_SYMBOLS symbols is
+ *   staged in LDS by every workgroup that codes index streams (16 KB + 4 B at the limit: a 256-lane workgroup of these latency-bound
+ *   lanes then still shares a CU's 160 KB with eight others, and the limit covers every sample count the coders here draw, S <= 4096
+ *   being rows of at most 4095 values plus the terminator); a larger one is read from global memory. */
+#define IREC_REC_TABLE_LDS_SYMBOLS 4096
+irec_status irec_rec_tables_build(const int64_t *counts, int32_t n_symbols, uint32_t *cum /*[n_symbols + 1]*/);
+int64_t irec_rec_encode_files_tables(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                     uint32_t channels, int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res,
+                                     int32_t max_K, const int32_t *K /*[n][T]*/, const int32_t *idx /*[n][T][max_K]*/,
+                                     const uint32_t *index_cum, int32_t n_index_symbols, const uint32_t *count_cum,
+                                     const int32_t *count_first /*[R + 1]*/, int64_t n_count_cum, uint8_t *out, int64_t cap,
+                                     int64_t *offsets /*[n_images + 1]*/, int32_t *status /*[n_images]*/, int32_t n_threads);
+irec_status irec_rec_decode_files_tables(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                         const int32_t *blocks_per_res, int32_t max_K, const uint32_t *index_cum, int32_t n_index_symbols,
+                                         const uint32_t *count_cum, const int32_t *count_first, int64_t n_count_cum,
+                                         uint32_t *headers /*[n][9]*/, int32_t *K /*[n][T]*/, int32_t *idx /*[n][T][max_K]*/,
+                                         int32_t *status /*[n]*/, int32_t n_threads);
+irec_status irec_rec_encode_files_device_tables(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                                uint32_t channels, int32_t n_images, int32_t n_res_blocks,
+                                                const int32_t *blocks_per_res /*host [n_res_blocks]*/, int32_t max_K,
+                                                const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride,
+                                                const uint32_t *index_cum, int32_t n_index_symbols, const uint32_t *count_cum,
+                                                const int32_t *count_first, int64_t n_count_cum, uint8_t *out, int64_t cap,
+                                                int64_t *offsets /*[n_images + 1]*/, int32_t *status /*[n_images]*/, void *workspace,
+                                                size_t workspace_bytes, void *hip_stream);
+irec_status irec_rec_decode_files_device_tables(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                                const int32_t *blocks_per_res /*host [n_res_blocks]*/, int32_t max_K,
+                                                const uint32_t *index_cum, int32_t n_index_symbols, const uint32_t *count_cum,
+                                                const int32_t *count_first, int64_t n_count_cum, uint32_t *headers /*[n][9]*/, int32_t *K,
+                                                int32_t *idx, int32_t *status, void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Histograms of packed rows, to fit tables from: K [n_images][T] and idx [n_images][T][max_K] under the stride conventions above, added
+ * INTO uint64 arrays (a corpus is fed batch by batch; zero them first):
+ *   index_hist [n_index_values]                  the first K indices of every row whose K lies in [0, min(max_K, n_count_values - 1)];
+ *   count_hist [n_res_blocks][n_count_values]    the K of every row, by its residual block;
+ *   streams [1 + n_res_blocks]                   streams seen: [0] index streams (n_images R), [1 + r] count streams of block r (n_images);
+ *   rejected [1]                                 values outside their range (a K outside [0, n_count_values) or above max_K -- its row's
+ *                                                indices are then not looked at --, an index outside [0, n_index_values)): not counted.
+ * Integer adds only: the result does not depend on the order of the adds.  The device form (csrc/irec_rec_tables.hip) keeps the bins
+ * of a workgroup in LDS and adds every non-empty one to global memory once; asynchronous on hip_stream, nothing allocated or copied. */
+irec_status irec_rec_hist_rows(int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res, int32_t max_K, const int32_t *K,
+                               int64_t k_stride, const int32_t *idx, int64_t idx_stride, int32_t n_index_values, int32_t n_count_values,
+                               uint64_t *index_hist, uint64_t *count_hist, uint64_t *streams, uint64_t *rejected);
+irec_status irec_rec_hist_rows_device(int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res /*host*/, int32_t max_K,
+                                      const int32_t *K, int64_t k_stride, const int32_t *idx, int64_t idx_stride, int32_t n_index_values,
+                                      int32_t n_count_values, uint64_t *index_hist, uint64_t *count_hist, uint64_t *streams,
+                                      uint64_t *rejected, void *hip_stream);
 
 /* The verdict on the rows a decode call is about to read, on the device (csrc/irec_rows.hip over csrc/irec_rows_core.h).  The decode
  * entry points above answer a row they cannot decode with p_loc, silently; a caller whose rows never leave the device (the output of

@@ -35,6 +35,9 @@ IREC_ROWS_OK, IREC_ROWS_E_K_RANGE, IREC_ROWS_E_INDEX_RANGE, IREC_ROWS_E_RATIO_TA
 IREC_REC_E_MAX_K = 18            # irec_rec_status: a block with more partitions than max_K
 IREC_REC_E_STRUCTURE = 17        # irec_rec_status: a file whose R or block counts differ from the call's
 REC_RAGGED_MAX_RES = 64          # IREC_REC_RAGGED_MAX_RES
+IREC_REC_E_COUNT_FILES = 5       # irec_rec_status: a file that uses count tables the call did not bring
+IREC_REC_E_TABLE = 19            # irec_rec_status: a symbol table whose entries cannot be coded under
+REC_TABLE_LDS_SYMBOLS = 4096     # IREC_REC_TABLE_LDS_SYMBOLS
 INT32_MAX = 2 ** 31 - 1
 
 
@@ -176,6 +179,21 @@ SIGNATURES = {
     "irec_rec_test_core_decode_files_ragged": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "irec_rec_test_core_encode_files": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "irec_rec_test_core_decode_files": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "irec_rec_tables_build": (ctypes.c_int, [_vp, _i32, _vp]),
+    # (index_cum, n_index_symbols, count_cum, count_first, n_count_cum) = [_vp, _i32, _vp, _vp, _i64] in every *_tables entry
+    "irec_rec_encode_files_tables": (_i64, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _vp] + [_vp, _i32, _vp, _vp, _i64] +
+                                     [_vp, _i64, _vp, _vp, _i32]),
+    "irec_rec_decode_files_tables": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32] + [_vp, _i32, _vp, _vp, _i64] + [_vp, _vp, _vp, _vp, _i32]),
+    "irec_rec_encode_files_device_tables": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64] +
+                                            [_vp, _i32, _vp, _vp, _i64] + [_vp, _i64, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_rec_decode_files_device_tables": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32] + [_vp, _i32, _vp, _vp, _i64] +
+                                            [_vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_rec_test_core_encode_files_tables": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64] +
+                                               [_vp, _i32, _vp, _vp, _i64] + [_vp, _i64, _vp, _vp]),
+    "irec_rec_test_core_decode_files_tables": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32] + [_vp, _i32, _vp, _vp, _i64] +
+                                               [_vp, _vp, _vp, _vp]),
+    "irec_rec_hist_rows": (ctypes.c_int, [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "irec_rec_hist_rows_device": (ctypes.c_int, [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "irec_res_device_workspace_bytes": (ctypes.c_size_t, [_i32, _i64]),
     "irec_res_encode_files_device": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _i32] + [ctypes.c_uint32] * 4 + [_vp, _i64, _vp, _vp, _vp,
                                                     ctypes.c_size_t, _vp]),

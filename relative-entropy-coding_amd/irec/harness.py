@@ -25,13 +25,13 @@ from .io import decode_files, decode_files_device, encode_files, read_compressed
 from .models.resnet_vae import STATUS_RESIDUAL, status_text
 
 
-def _host_leg(chunk_shape, names, seed, block_size, out_dir, S, K, idx, t_compress):
+def _host_leg(chunk_shape, names, seed, block_size, out_dir, S, K, idx, t_compress, tables=None):
     """Write / read back / compare the .rec files of one batch from its packed read-back (compression_performance.py:350-375
     per image): the containers are built natively for all images at once (irec_rec_encode_files, host threads), written, read
     back, decoded together (irec_rec_decode_files) and compared as arrays."""
     n, _, h, w = chunk_shape
     t1 = time.perf_counter()
-    blob, off = encode_files(seed, (h, w, 3), block_size, K, idx, max_index=S)      # the reference passes 20 < S = 36 (SURVEY §7 quirks)
+    blob, off = encode_files(seed, (h, w, 3), block_size, K, idx, max_index=S, tables=tables)   # the reference passes 20 < S = 36 (SURVEY §7 quirks)
     paths = [os.path.join(out_dir, f"{nm}.rec") for nm in names]
     mv = memoryview(blob)
     for i, path in enumerate(paths):
@@ -40,7 +40,7 @@ def _host_leg(chunk_shape, names, seed, block_size, out_dir, S, K, idx, t_compre
     back = [open(path, "rb").read() for path in paths]
     sizes = np.array([len(b) for b in back], dtype=np.int64)
     off2 = np.concatenate([[0], np.cumsum(sizes)])
-    hdr, K2, idx2 = decode_files(np.frombuffer(b"".join(back), dtype=np.uint8), off2, K.shape[1], K.shape[2], idx.shape[3])
+    hdr, K2, idx2 = decode_files(np.frombuffer(b"".join(back), dtype=np.uint8), off2, K.shape[1], K.shape[2], idx.shape[3], tables=tables)
     live = np.arange(idx.shape[3])[None, None, None, :] < K[..., None]
     same = (K2 == K).all(axis=(1, 2)) & ((idx2 == idx) | ~live).all(axis=(1, 2, 3)) & \
         (hdr[:, [0, 1, 3, 4, 5]] == np.array([seed, block_size, h, w, 3], dtype=np.uint32)).all(axis=1)
@@ -52,13 +52,14 @@ def _host_leg(chunk_shape, names, seed, block_size, out_dir, S, K, idx, t_compre
             for i in range(n)]
 
 
-def _device_leg(model, chunk, names, seed, block_size, out_dir, S):
+def _device_leg(model, chunk, names, seed, block_size, out_dir, S, tables=None):
     """_host_leg with the files built and checked on the device: the batch's files come from model.compress_rec (the arithmetic coder
     runs on the device), are written, read back, decoded on the device (irec_rec_decode_files_device) and compared there with the
     indices that compress_rec's coders left.  The rows carry the same keys."""
     n, _, h, w = chunk.shape
     t0 = time.perf_counter()
-    (blob, off, _), pendings = model.compress_rec(chunk, seed=seed, update_sampler=False, block_size=block_size, return_pendings=True)
+    (blob, off, _), pendings = model.compress_rec(chunk, seed=seed, update_sampler=False, block_size=block_size, return_pendings=True,
+                                                  tables=tables)
     t_compress = time.perf_counter() - t0
     t1 = time.perf_counter()
     K, idx = pendings                                             # views of the joined device tensor the files were built from
@@ -72,7 +73,7 @@ def _device_leg(model, chunk, names, seed, block_size, out_dir, S):
     sizes = np.array([len(b) for b in back], dtype=np.int64)
     off2 = np.concatenate([[0], np.cumsum(sizes)])
     blob2 = torch.from_numpy(np.frombuffer(b"".join(back), dtype=np.uint8).copy()).to(blob.device)
-    hdr, K2, idx2 = decode_files_device(blob2, off2, K.shape[1], K.shape[2], idx.shape[3])
+    hdr, K2, idx2 = decode_files_device(blob2, off2, K.shape[1], K.shape[2], idx.shape[3], tables=tables)
     live = torch.arange(idx.shape[3], device=idx.device)[None, None, None, :] < K[..., None]
     want = torch.tensor([seed, block_size, h, w, 3], dtype=torch.int64, device=hdr.device)
     same = ((K2 == K).all(dim=2).all(dim=1) & ((idx2 == idx) | ~live).all(dim=3).all(dim=2).all(dim=1) &
@@ -126,7 +127,7 @@ def _lossless_leg(model, chunk, names, seed, block_size, out_dir, S, stream_len)
 
 
 def compress_images(model, images, names, seed, block_size, out_dir, batch=None, packed=True, rec_on_device=False, lossless=False,
-                    stream_len=None):
+                    stream_len=None, tables=None):
     """images: [n, 3, H, W] in [-0.5, 0.5] on the model's device.  Returns one dict per image (reference CSV columns where
     they apply: comp_codelength, comp_lossy_bpp, comp_time) plus `indices_recovered`, `code_nats`.
     packed (default): the indices stay packed arrays from the device to the files (model.compress_packed, irec.io.encode_files
@@ -136,7 +137,11 @@ def compress_images(model, images, names, seed, block_size, out_dir, batch=None,
     (irec.io.decode_files_device); same rows, byte-identical files.  The default stays the host leg.
     lossless: images are uint8 [n, 3, H, W] (the model sees x / 256 - 0.5); NAME.res is written beside NAME.rec, both are read back
     and decoded to the pixels on the device, and the rows gain comp_residual, comp_lossless_bpp, comp_bpd, residual_model_bits and
-    pixels_recovered (_lossless_leg).  stream_len: symbols per .res stream (default irec.io.residual.DEFAULT_STREAM_LEN)."""
+    pixels_recovered (_lossless_leg).  stream_len: symbols per .res stream (default irec.io.residual.DEFAULT_STREAM_LEN).
+    tables: an irec.io.SymbolTables (fit_symbol_tables) the files are coded under, on the packed host leg or the device leg;
+    decompress_images_tables reads them.  The per-image form and the lossless pair keep the default models (ValueError)."""
+    if tables is not None and (lossless or not (rec_on_device or (packed and hasattr(model, "compress_packed")))):
+        raise ValueError("compress_images: tables go with the packed host leg or rec_on_device, not with lossless or packed=False")
     os.makedirs(out_dir, exist_ok=True)
     n = images.shape[0]
     batch = n if not batch else int(batch)
@@ -154,7 +159,7 @@ def compress_images(model, images, names, seed, block_size, out_dir, batch=None,
         for lo in range(0, n, batch):
             chunk = images[lo:lo + batch]
             try:
-                rows += _device_leg(model, chunk, names[lo:lo + chunk.shape[0]], seed, block_size, out_dir, S)
+                rows += _device_leg(model, chunk, names[lo:lo + chunk.shape[0]], seed, block_size, out_dir, S, tables)
             except CodingError as e:                     # compression_performance.py:375-377: log and move on
                 rows += [{"name": names[lo + i], "error": str(e)} for i in range(chunk.shape[0])]
         return rows
@@ -171,7 +176,7 @@ def compress_images(model, images, names, seed, block_size, out_dir, batch=None,
                     jobs.append([{"name": names[lo + i], "error": str(e)} for i in range(chunk.shape[0])])
                     continue
                 jobs.append(pool.submit(_host_leg, tuple(chunk.shape), names[lo:lo + chunk.shape[0]], seed, block_size, out_dir,
-                                        S, K, idx, time.perf_counter() - t0))
+                                        S, K, idx, time.perf_counter() - t0, tables))
             for j in jobs:
                 rows += j if isinstance(j, list) else j.result()
         return rows
@@ -224,13 +229,19 @@ def decompress_images(model, paths, batch=None, strict=True):
     return _decompress_images(model, paths, batch, strict, False)
 
 
+def decompress_images_tables(model, paths, tables, batch=None, strict=True):
+    """decompress_images for files written under an irec.io.SymbolTables (compress_images(tables=)); files without header flags decode
+    in the same call.  A function of its own: decompress_images' signature is pinned."""
+    return _decompress_images(model, paths, batch, strict, False, tables)
+
+
 def decompress_images_lossless(model, paths, batch=None, strict=True):
     """The read side of compress_images(lossless=True): decompress_images over NAME.rec + NAME.res pairs (`paths` names the .rec
     files), the images being the uint8 pixels.  A function of its own: decompress_images' signature is pinned."""
     return _decompress_images(model, paths, batch, strict, True)
 
 
-def _decompress_images(model, paths, batch, strict, lossless):
+def _decompress_images(model, paths, batch, strict, lossless, tables=None):
     """The read side of compress_images: .rec files -> (images, rows).  The files are read and their headers parsed on the host
     (RecHeader over the 28 + 16 R header bytes), files of equal (seed, shape, R, bpt) are grouped, each group's bytes are uploaded
     once per batch and decoded by model.decompress_rec -- the arithmetic decoder, the row checks and the generative pass on the
@@ -269,6 +280,8 @@ def _decompress_images(model, paths, batch, strict, lossless):
                 off = np.concatenate([[0], np.cumsum(sizes)])
                 host = np.frombuffer(b"".join(datas[i] for i in part), dtype=np.uint8)
                 max_K = max([1] + [m for i in part for m in infos[i]["max_partitions"] if m <= 65536])
+                if tables is not None and tables.max_K is not None:
+                    max_K = max(max_K, tables.max_K)          # (a file under count tables says 0xFFFFFFFF: the bound is the tables')
                 blob = torch.from_numpy(host.copy()).to(dev)
                 if lossless:
                     res_off = np.concatenate([[0], np.cumsum([len(res_datas[i]) for i in part])]).astype(np.int64)
@@ -278,7 +291,7 @@ def _decompress_images(model, paths, batch, strict, lossless):
                     rec, status, K = model._decompress_lossless_status(blob, off, res_blob, res_off, seed, (len(part), c, h, w_), max_K,
                                                                        L if L and 1 <= L <= 4096 else None)
                 else:
-                    rec, status, K = model._decompress_rec_status(blob, off, seed, (len(part), c, h, w_), max_K)
+                    rec, status, K = model._decompress_rec_status(blob, off, seed, (len(part), c, h, w_), max_K, tables)
                 texts = [model.status_text(st, K[k]) if st else "" for k, st in enumerate(status)]
             else:                                                       # IREC_REC_E_STRUCTURE: not this model's block structure
                 rec, status = torch.zeros((len(part), 3, h, w_), device=dev, dtype=torch.uint8 if lossless else None), [17] * len(part)
@@ -301,12 +314,13 @@ def _decompress_images(model, paths, batch, strict, lossless):
 
 
 # ---- the two-level lossy model (irec.models.lossy.Large2LevelVAE): the same two drivers over ragged files -------------------------
-def compress_images_lossy(model, sampler, images, names, seed, block_size, out_dir, batch=None, rec_on_device=False):
+def compress_images_lossy(model, sampler, images, names, seed, block_size, out_dir, batch=None, rec_on_device=False, tables=None):
     """compress_images for Large2LevelVAE and its coder `sampler`: images [n, 3, H, W] on the model's device, in batches through
     model.compress_rec (two coder launches per batch, one read-back), one NAME.rec per image -- byte for byte the file
     model.compress(file_path, ...) writes for it -- read back and compared with the rows the files were built from.
     rec_on_device: the files are built and checked on the device (irec.io.encode_files_device_ragged / decode_files_device_ragged)
-    instead of on host threads, the default.  Returns one dict per image with compress_images' keys."""
+    instead of on host threads, the default.  tables: an irec.io.SymbolTables (fit_symbol_tables_lossy) the files are coded under.
+    Returns one dict per image with compress_images' keys."""
     from .io import decode_files_device_ragged, decode_files_ragged
     os.makedirs(out_dir, exist_ok=True)
     n = images.shape[0]
@@ -319,7 +333,7 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
         t0 = time.perf_counter()
         try:
             (blob, off, _), (K, idx, bpr) = model.compress_rec(chunk, seed, sampler, block_size=block_size, rec_on_device=rec_on_device,
-                                                               return_pendings=True)
+                                                               return_pendings=True, tables=tables)
         except CodingError as e:                         # compression_performance.py:375-377: log and move on
             rows += [{"name": names[lo + i], "error": str(e)} for i in range(m)]
             continue
@@ -337,13 +351,13 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
         blob2 = np.frombuffer(b"".join(back), dtype=np.uint8)
         want = np.array([seed, block_size, h, w, 3], dtype=np.int64)
         if rec_on_device:
-            hdr, K2, idx2 = decode_files_device_ragged(torch.from_numpy(blob2.copy()).to(blob.device), off2, bpr, idx.shape[2])
+            hdr, K2, idx2 = decode_files_device_ragged(torch.from_numpy(blob2.copy()).to(blob.device), off2, bpr, idx.shape[2], tables=tables)
             live = torch.arange(idx.shape[2], device=idx.device)[None, None, :] < K[..., None]
             same = ((K2 == K).all(dim=1) & ((idx2 == idx) | ~live).all(dim=2).all(dim=1) &
                     (hdr[:, [0, 1, 3, 4, 5]] == torch.from_numpy(want).to(hdr.device)).all(dim=1)).cpu().numpy()
             n_idx = K.sum(dim=1).cpu().numpy()
         else:
-            hdr, K2, idx2 = decode_files_ragged(blob2, off2, bpr, idx.shape[2])
+            hdr, K2, idx2 = decode_files_ragged(blob2, off2, bpr, idx.shape[2], tables=tables)
             live = np.arange(idx.shape[2])[None, None, :] < K[..., None]
             same = (K2 == K).all(axis=1) & ((idx2 == idx) | ~live).all(axis=(1, 2)) & (hdr[:, [0, 1, 3, 4, 5]].astype(np.int64) == want).all(axis=1)
             n_idx = K.sum(axis=1)
@@ -354,10 +368,11 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
     return rows
 
 
-def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_on_device=False):
+def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_on_device=False, tables=None):
     """decompress_images for Large2LevelVAE and its coder `sampler`: .rec files -> (images, rows), the files grouped by header (seed,
     shape, block structure) and each group decoded in batches by model.decompress_rec -- on host threads, or with rec_on_device on
-    the device -- with one read-back per batch, the per-image status.  images, rows and strict as decompress_images has them."""
+    the device -- with one read-back per batch, the per-image status.  images, rows and strict as decompress_images has them.
+    tables: the irec.io.SymbolTables the files were written under (files without header flags decode in the same call)."""
     dev = next(model.parameters()).device
     datas = []
     for path in paths:
@@ -380,9 +395,11 @@ def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_
                 off = np.concatenate([[0], np.cumsum(sizes)])
                 host = np.frombuffer(b"".join(datas[i] for i in part), dtype=np.uint8)
                 max_K = max([1] + [m for i in part for m in infos[i]["max_partitions"] if m <= 65536])
+                if tables is not None and tables.max_K is not None:
+                    max_K = max(max_K, tables.max_K)
                 blob = torch.from_numpy(host.copy()).to(dev) if rec_on_device else host
                 rec, status = model.decompress_rec(blob, off, seed, (len(part), c, h, w_), sampler, max_K=max_K, strict=False,
-                                                   rec_on_device=rec_on_device)
+                                                   rec_on_device=rec_on_device, tables=tables)
                 texts = [status_text(int(st)) if st else "" for st in status]
             else:                                                       # IREC_REC_E_STRUCTURE: not this model's block structure
                 rec, status = torch.zeros((len(part), 3, h, w_), device=dev), [17] * len(part)
@@ -402,6 +419,66 @@ def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_
     if len(shapes) == 1 and all(im is not None for im in images):
         return torch.stack(images, dim=0), rows
     return images, rows
+
+
+# ---- fitting symbol tables (irec.io.SymbolTables) to a model's own rows -----------------------------------------------------------------
+def _fit_batches(batches, n_index_values, n_count_values):
+    """hist_rows over (K [N, T], idx [N, T, max_K], blocks_per_res) device batches, accumulated on the device, finalised once."""
+    from .io import hist_rows, tables_from_histograms
+    hist = None
+    for K, idx, bpr in batches:
+        hist = hist_rows(K, idx, bpr, n_index_values, n_count_values, into=hist)
+    if hist is None:
+        raise ValueError("fit_symbol_tables: no images")
+    host = hist.numpy()
+    if int(host.rejected[0]):
+        raise CodingError(f"fit_symbol_tables: {int(host.rejected[0])} values outside the tables' ranges")
+    return tables_from_histograms(host)
+
+
+def fit_symbol_tables(model, images, seed, batch=None, max_K=None):
+    """An irec.io.SymbolTables fitted to what BidirectionalResNetVAE `model` codes for `images` [n, 3, H, W] (on its device): the
+    batches go through the model's packed device pass, their rows are histogrammed where they lie (irec.io.hist_rows) and the counts
+    are read back once.  One index table over the coder's samples, one count table per residual block over K in [0, max_K]
+    (default: the largest index-slot count a batch came with, doubled: a K the fit never saw still has a symbol)."""
+    from .coding.beam_search_coder import PendingCode, MorePartitionsNeeded, SplitNotResident
+    n = images.shape[0]
+    step = n if not batch else int(batch)
+    coder = model.residual_blocks[0].coder
+    S = coder.sampler.n_samples() if coder.sampler is not None else coder.n_samples
+    rows = []
+    with torch.no_grad():
+        for lo in range(0, n, step):
+            for _attempt in range(6):
+                pendings, _ = model._compress_device(images[lo:lo + step], seed, False)
+                try:
+                    K, idx = PendingCode.gather_packed_device(pendings)
+                    break
+                except (MorePartitionsNeeded, SplitNotResident):
+                    continue
+            else:
+                raise MorePartitionsNeeded(max(b.coder._max_K_hint for b in model.residual_blocks) + 1)
+            m, R, bpt = K.shape
+            rows.append((K.reshape(m, R * bpt), idx.reshape(m, R * bpt, idx.shape[3]), [bpt] * R))
+    if max_K is None:
+        max_K = 2 * max(idx.shape[2] for _, idx, _ in rows)
+    return _fit_batches(rows, S, int(max_K) + 1)
+
+
+def fit_symbol_tables_lossy(model, sampler, images, seed, block_size, batch=None, max_K=None):
+    """fit_symbol_tables for Large2LevelVAE and its coder `sampler`: one index table, one count table for each of the two levels.
+    block_size: the coder's, as compress_images_lossy takes it (the layout is the sampler's own)."""
+    from .coding.beam_search_coder import PendingCode
+    n = images.shape[0]
+    step = n if not batch else int(batch)
+    rows = []
+    with torch.no_grad():
+        for lo in range(0, n, step):
+            (K, idx, bpr), _ = model._compress_gather(images[lo:lo + step], seed, sampler, PendingCode.gather_packed_ragged_device)
+            rows.append((K, idx, bpr))
+    if max_K is None:
+        max_K = 2 * max(idx.shape[2] for _, idx, _ in rows)
+    return _fit_batches(rows, model._max_index(sampler), int(max_K) + 1)
 
 
 def compress_sharded(model, all_images, seed, block_size, out_dir, rank=0, world=1, dist=None, batch=None):

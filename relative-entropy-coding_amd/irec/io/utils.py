@@ -142,16 +142,20 @@ def _native_decode(data):
     return int(hdr[0]), (int(hdr[3]), int(hdr[4]), int(hdr[5])), int(hdr[1]), blocks
 
 
-def encode_files(seed, image_shape, block_size, K, idx, max_index, n_threads=0):
+def encode_files(seed, image_shape, block_size, K, idx, max_index, n_threads=0, tables=None):
     """N containers at once from a packed read-back (irec_rec_encode_files): K [N, R, bpt] int32, idx [N, R, bpt, max_K] int32.
     Returns (blob uint8, offsets int64 [N + 1]): file i = blob[offsets[i]:offsets[i + 1]], byte for byte what
-    write_compressed_code writes for image i (rec/io/utils.py:7-106, default symbol models)."""
+    write_compressed_code writes for image i (rec/io/utils.py:7-106, default symbol models).
+    tables: a SymbolTables -- the files as write_compressed_code writes them with those count files (irec_rec_encode_files_tables)."""
     lib = _lib.load()
     K = np.ascontiguousarray(K, dtype=np.int32)
     idx = np.ascontiguousarray(idx, dtype=np.int32)
     n, r, bpt = K.shape
     max_K = idx.shape[3] if idx.ndim == 4 else 0
     assert idx.shape[:3] == K.shape
+    if tables is not None:
+        return encode_files_ragged(seed, image_shape, block_size, K.reshape(n, r * bpt), idx.reshape(n, r * bpt, max_K), max_index,
+                                   [bpt] * r, n_threads, tables=tables)
     h, w, c = (int(v) for v in image_shape)
     offsets = np.zeros(n + 1, dtype=np.int64)
     cap = n * (64 + 16 * r) + 2 * int(K.sum()) + 16 * K.size + 1024
@@ -167,9 +171,15 @@ def encode_files(seed, image_shape, block_size, K, idx, max_index, n_threads=0):
         cap = int(total)
 
 
-def decode_files(blob, offsets, n_res_blocks, blocks_per_res, max_K, n_threads=0):
+def decode_files(blob, offsets, n_res_blocks, blocks_per_res, max_K, n_threads=0, tables=None):
     """The inverse of encode_files (irec_rec_decode_files): (headers [N, 9] uint32 -- seed, block_size, max_index, height,
-    width, channels, two flags, R --, K [N, R, bpt], idx [N, R, bpt, max_K] with rows zero-filled past K)."""
+    width, channels, two flags, R --, K [N, R, bpt], idx [N, R, bpt, max_K] with rows zero-filled past K).
+    tables: a SymbolTables for the files whose header flags ask for one (irec_rec_decode_files_tables); files without flags decode
+    under the default models in the same call."""
+    if tables is not None:
+        r, bpt = int(n_res_blocks), int(blocks_per_res)
+        hdr, K, idx = decode_files_ragged(blob, offsets, [bpt] * r, max_K, n_threads, tables=tables)
+        return hdr, K.reshape(-1, r, bpt), idx.reshape(-1, r, bpt, idx.shape[-1])
     lib = _lib.load()
     blob = np.ascontiguousarray(blob, dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
@@ -202,6 +212,7 @@ _REC_STATUS_TEXT = {
     16: "irec_rec_decode_file: streams do not match the header",
     17: "irec_rec_decode_files: block structure differs",
     18: "irec_rec_decode_files: more partitions than max_K",
+    19: "irec_rec: a symbol table whose entries cannot be coded under (cum[0] != 0, a total above 2^30, or an empty interval)",
 }
 
 
@@ -251,7 +262,7 @@ def _encode_files_device_launch(seed, image_shape, block_size, K, idx, max_index
     return offsets, status, both
 
 
-def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=None):
+def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=None, tables=None):
     """encode_files on the device (irec_rec_encode_files_device): K [N, R, bpt], idx [N, R, bpt, max_K] int32 CUDA tensors, contiguous
     or views of one joined [rows][1 + width] tensor (PendingCode.gather_packed_device).  Returns (blob uint8, offsets int64 [N + 1]) as
     CUDA tensors, byte for byte what encode_files gives; the only host synchronisation is ONE read-back of offsets and status.
@@ -263,6 +274,10 @@ def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=No
         raise ValueError(f"encode_files_device: K {tuple(K.shape)} and idx {tuple(idx.shape)} are not [N, R, bpt] and [N, R, bpt, max_K]")
     n, r, bpt = K.shape
     max_K = idx.shape[3]
+    if tables is not None:                             # (R <= IREC_REC_RAGGED_MAX_RES: the entry point with tables takes the ragged layout)
+        K, ks, idx, ist = _block_strides(K, idx)
+        return encode_files_device_ragged(seed, image_shape, block_size, K.as_strided((n, r * bpt), (r * bpt * ks, ks)),
+                                          idx.as_strided((n, r * bpt, max_K), (r * bpt * ist, ist, 1)), max_index, [bpt] * r, out, tables=tables)
     if out is None:
         # irec_io.cpp's own first allowance: 64 + 40 bits per symbol and terminator, per stream
         cap = n * (28 + 16 * r + r * ((64 + 40 * (bpt + 1)) // 8 + 1 + (64 + 40 * (bpt * max_K + 1)) // 8 + 1))
@@ -280,7 +295,7 @@ def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=No
     raise ValueError("irec_rec_encode_files_device: the files did not fit the size the call itself reported")
 
 
-def _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K, on_device=False):
+def _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K, on_device=False, tables=None):
     """One irec_rec_decode_files_device call on the current stream: (headers int32 [N, 9] holding the uint32 words, K, idx, status int32 [N])
     on the device, nothing read back but `offsets` (checked against the blob before any kernel sees them).
     on_device: offsets that ARE on the device stay there -- instead of the check on the host they are clamped into the blob and made
@@ -288,6 +303,10 @@ def _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max
     wrong reads as a damaged file); nothing is read back and the call can be captured in a HIP graph."""
     import torch
     lib = _lib.load()
+    if tables is not None:                             # (the entry point with tables takes the ragged layout: R equal entries)
+        r, bpt = int(n_res_blocks), int(blocks_per_res)
+        hdr, K, idx, status = _decode_files_device_ragged_launch(blob, offsets, [bpt] * r, max_K, on_device=on_device, tables=tables)
+        return hdr, K.view(-1, r, bpt), idx.view(-1, r, bpt, int(max_K)), status
     if not (blob.is_cuda and blob.dtype == torch.uint8):
         raise ValueError("decode_files_device takes a CUDA uint8 tensor")
     blob = blob.contiguous()
@@ -321,11 +340,15 @@ def _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max
     return hdr, K, idx, status[:n]
 
 
-def decode_files_device(blob, offsets, n_res_blocks, blocks_per_res, max_K):
+def decode_files_device(blob, offsets, n_res_blocks, blocks_per_res, max_K, tables=None):
     """decode_files on the device (irec_rec_decode_files_device): blob uint8 CUDA tensor, offsets [N + 1] (CUDA, CPU or numpy).
     Returns CUDA tensors (headers [N, 9] int64 -- seed, block_size, max_index, height, width, channels, two flags, R --,
     K [N, R, bpt] int32, idx [N, R, bpt, max_K] int32 with rows zero-filled past K); ValueError naming the first damaged file."""
     import torch
+    if tables is not None:
+        r, bpt = int(n_res_blocks), int(blocks_per_res)
+        hdr, K, idx = decode_files_device_ragged(blob, offsets, [bpt] * r, max_K, tables=tables)
+        return hdr, K.view(-1, r, bpt), idx.view(-1, r, bpt, int(max_K))
     hdr, K, idx, status = _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K)
     _raise_first_status(status.cpu().numpy())
     return hdr.to(torch.int64) & 0xFFFFFFFF, K, idx
@@ -340,7 +363,7 @@ def _ragged_layout(blocks_per_res, what):
     return bpr.astype(np.int32), int(bpr.sum())
 
 
-def encode_files_ragged(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, n_threads=0):
+def encode_files_ragged(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, n_threads=0, tables=None):
     """encode_files for residual blocks of differing sizes (irec_rec_encode_files_ragged): K [N, T] int32, idx [N, T, max_K] int32,
     T = sum(blocks_per_res).  Returns (blob uint8, offsets int64 [N + 1]); file i is byte for byte what write_compressed_code writes for
     image i's lists."""
@@ -354,6 +377,19 @@ def encode_files_ragged(seed, image_shape, block_size, K, idx, max_index, blocks
     h, w, c = (int(v) for v in image_shape)
     offsets = np.zeros(n + 1, dtype=np.int64)
     cap = n * (64 + 16 * bpr.size) + 2 * int(K.sum()) + 16 * K.size + 1024
+    while tables is not None:                          # (per-image statuses; the size a short buffer needs comes back with them)
+        out = np.empty(cap, dtype=np.uint8)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        total = lib.irec_rec_encode_files_tables(int(seed), int(block_size), int(max_index), h, w, c, n, bpr.size, bpr.ctypes.data, max_K,
+                                                 K.ctypes.data, idx.ctypes.data if idx.size else None,
+                                                 *tables.host_args(bpr.size, "encode_files_ragged"), out.ctypes.data, cap,
+                                                 offsets.ctypes.data, status.ctypes.data, int(n_threads))
+        if total < 0:
+            raise ValueError(lib.irec_last_error().decode())
+        _raise_first_status(status[:n])
+        if total <= cap:
+            return out[:total], offsets
+        cap = int(total)
     while True:
         out = np.empty(cap, dtype=np.uint8)
         total = lib.irec_rec_encode_files_ragged(int(seed), int(block_size), int(max_index), h, w, c, n, bpr.size, bpr.ctypes.data, max_K,
@@ -366,7 +402,7 @@ def encode_files_ragged(seed, image_shape, block_size, K, idx, max_index, blocks
         cap = int(total)
 
 
-def decode_files_ragged(blob, offsets, blocks_per_res, max_K, n_threads=0):
+def decode_files_ragged(blob, offsets, blocks_per_res, max_K, n_threads=0, tables=None):
     """The inverse of encode_files_ragged (irec_rec_decode_files_ragged): (headers [N, 9] uint32, K [N, T], idx [N, T, max_K] with rows
     zero-filled past K); ValueError naming the first file that is damaged or of another structure."""
     lib = _lib.load()
@@ -377,11 +413,39 @@ def decode_files_ragged(blob, offsets, blocks_per_res, max_K, n_threads=0):
     hdr = np.zeros((n, 9), dtype=np.uint32)
     K = np.zeros((n, T), dtype=np.int32)
     idx = np.zeros((n, T, max(max_K, 1)), dtype=np.int32)
+    if tables is not None:
+        hdr, K, idx, status = _decode_files_tables_status(blob, offsets, bpr, max_K, tables, n_threads)
+        _raise_first_status(status)
+        return hdr, K, idx
     st = lib.irec_rec_decode_files_ragged(blob.ctypes.data, offsets.ctypes.data, n, bpr.size, bpr.ctypes.data, int(max_K), hdr.ctypes.data,
                                           K.ctypes.data, idx.ctypes.data, int(n_threads))
     if st != 0:
         raise ValueError(lib.irec_io_last_error().decode())
     return hdr, K, idx[..., :max_K]
+
+
+def _decode_files_tables_status(blob, offsets, blocks_per_res, max_K, tables, n_threads=0):
+    """irec_rec_decode_files_tables: (headers [N, 9] uint32, K [N, T], idx [N, T, max_K], status int32 [N]) -- a verdict per file, the
+    outputs of a refused one zero."""
+    lib = _lib.load()
+    bpr, T = _ragged_layout(blocks_per_res, "decode_files_ragged")
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = offsets.size - 1
+    if n < 0 or offsets[0] < 0 or (np.diff(offsets) < 0).any() or offsets[-1] > blob.size:
+        raise ValueError("decode_files_ragged: offsets must be non-decreasing and end inside the blob")
+    hdr = np.zeros((n, 9), dtype=np.uint32)
+    K = np.zeros((n, T), dtype=np.int32)
+    idx = np.zeros((n, T, int(max_K)), dtype=np.int32)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    pad = np.zeros(1, dtype=np.uint8)
+    st = lib.irec_rec_decode_files_tables(blob.ctypes.data if blob.size else pad.ctypes.data, offsets.ctypes.data, n, bpr.size,
+                                          bpr.ctypes.data, int(max_K), *tables.host_args(bpr.size, "decode_files_ragged"),
+                                          hdr.ctypes.data, K.ctypes.data, idx.ctypes.data if idx.size else None, status.ctypes.data,
+                                          int(n_threads))
+    if st != 0:
+        raise ValueError(lib.irec_last_error().decode())
+    return hdr, K, idx, status[:n]
 
 
 def _row_strides(K, idx):
@@ -397,7 +461,7 @@ def _row_strides(K, idx):
     return K, int(ks), idx, int(ist)
 
 
-def _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, out):
+def _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, out, tables=None):
     """One irec_rec_encode_files_device_ragged call on the current stream, nothing read back: (offsets int64 [N + 1], status int32 [N], both
     views of `both`, which one copy fetches).  The bytes are in `out` only if offsets[N] <= out.numel()."""
     import torch
@@ -415,6 +479,17 @@ def _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, ma
         ws = torch.empty(max(lib.irec_rec_device_workspace_bytes(n, bpr.size), 8), dtype=torch.uint8, device=dev)
         both = torch.empty(n + 1 + (n + 1) // 2, dtype=torch.int64, device=dev)          # offsets, then status: one read-back
         offsets, status = both[:n + 1], both[n + 1:].view(torch.int32)[:n]
+        if tables is not None:
+            st = lib.irec_rec_encode_files_device_tables(int(seed), int(block_size), int(max_index), h, w, c, n, bpr.size, bpr.ctypes.data, max_K,
+                                                         K.data_ptr(), ks, idx.data_ptr() if idx.numel() else None, ist,
+                                                         *tables.to(dev).device_args(bpr.size, "encode_files_device_ragged"),
+                                                         out.data_ptr() if out.numel() else None, out.numel(), offsets.data_ptr(),
+                                                         status.data_ptr() if n else None, ws.data_ptr(), ws.numel(),
+                                                         torch.cuda.current_stream().cuda_stream)
+            if st == _lib.IREC_E_INVALID:
+                raise ValueError(lib.irec_last_error().decode())
+            _lib.check(st, "irec_rec_encode_files_device_tables")
+            return offsets, status, both
         st = lib.irec_rec_encode_files_device_ragged(int(seed), int(block_size), int(max_index), h, w, c, n, bpr.size, bpr.ctypes.data, max_K,
                                                      K.data_ptr(), ks, idx.data_ptr() if idx.numel() else None, ist,
                                                      out.data_ptr() if out.numel() else None, out.numel(), offsets.data_ptr(),
@@ -426,7 +501,7 @@ def _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, ma
     return offsets, status, both
 
 
-def encode_files_device_ragged(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, out=None):
+def encode_files_device_ragged(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, out=None, tables=None):
     """encode_files_ragged on the device (irec_rec_encode_files_device_ragged): K [N, T], idx [N, T, max_K] int32 CUDA tensors, contiguous
     or views of one joined [rows][1 + width] tensor (PendingCode.gather_packed_ragged_device).  Returns (blob uint8, offsets int64
     [N + 1]) as CUDA tensors, byte for byte what encode_files_ragged gives; the only host synchronisation is ONE read-back of offsets
@@ -442,7 +517,7 @@ def encode_files_device_ragged(seed, image_shape, block_size, K, idx, max_index,
         raise ValueError("encode_files_device_ragged: out must be a contiguous CUDA uint8 tensor on the indices' device")
     n = K.shape[0]
     for _attempt in range(2):
-        offsets, _, both = _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, bpr, out)
+        offsets, _, both = _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, bpr, out, tables)
         host = both.cpu().numpy()
         _raise_first_status(host[n + 1:].view(np.int32)[:n])
         total = int(host[n])
@@ -452,7 +527,7 @@ def encode_files_device_ragged(seed, image_shape, block_size, K, idx, max_index,
     raise ValueError("irec_rec_encode_files_device_ragged: the files did not fit the size the call itself reported")
 
 
-def _decode_files_device_ragged_launch(blob, offsets, blocks_per_res, max_K, on_device=False):
+def _decode_files_device_ragged_launch(blob, offsets, blocks_per_res, max_K, on_device=False, tables=None):
     """One irec_rec_decode_files_device_ragged call on the current stream: (headers int32 [N, 9] holding the uint32 words, K [N, T],
     idx [N, T, max_K], status int32 [N]) on the device; `offsets` and `on_device` as _decode_files_device_launch takes them."""
     import torch
@@ -482,6 +557,16 @@ def _decode_files_device_ragged_launch(blob, offsets, blocks_per_res, max_K, on_
         K = torch.empty((n, T), dtype=torch.int32, device=dev)
         idx = torch.empty((n, T, max_K), dtype=torch.int32, device=dev)
         status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        if tables is not None:
+            st = lib.irec_rec_decode_files_device_tables(blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, bpr.size,
+                                                         bpr.ctypes.data, max_K,
+                                                         *tables.to(dev).device_args(bpr.size, "decode_files_device_ragged"),
+                                                         hdr.data_ptr(), K.data_ptr(), idx.data_ptr() if idx.numel() else None,
+                                                         status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+            if st == _lib.IREC_E_INVALID:
+                raise ValueError(lib.irec_last_error().decode())
+            _lib.check(st, "irec_rec_decode_files_device_tables")
+            return hdr, K, idx, status[:n]
         st = lib.irec_rec_decode_files_device_ragged(blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, bpr.size,
                                                      bpr.ctypes.data, max_K, hdr.data_ptr(), K.data_ptr(),
                                                      idx.data_ptr() if idx.numel() else None, status.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -492,12 +577,12 @@ def _decode_files_device_ragged_launch(blob, offsets, blocks_per_res, max_K, on_
     return hdr, K, idx, status[:n]
 
 
-def decode_files_device_ragged(blob, offsets, blocks_per_res, max_K):
+def decode_files_device_ragged(blob, offsets, blocks_per_res, max_K, tables=None):
     """decode_files_ragged on the device (irec_rec_decode_files_device_ragged): blob uint8 CUDA tensor, offsets [N + 1] (CUDA, CPU or
     numpy).  Returns CUDA tensors (headers [N, 9] int64, K [N, T] int32, idx [N, T, max_K] int32 with rows zero-filled past K);
     ValueError naming the first damaged file."""
     import torch
-    hdr, K, idx, status = _decode_files_device_ragged_launch(blob, offsets, blocks_per_res, max_K)
+    hdr, K, idx, status = _decode_files_device_ragged_launch(blob, offsets, blocks_per_res, max_K, tables=tables)
     _raise_first_status(status.cpu().numpy())
     return hdr.to(torch.int64) & 0xFFFFFFFF, K, idx
 
@@ -521,16 +606,19 @@ def rec_header_words(data):
             "bpt": list(h.blocks_per_res_block), "max_partitions": list(h.max_partitions)}
 
 
-def rec_files_max_K(blob, offsets):
+def rec_files_max_K(blob, offsets, tables=None):
     """Index slots per block that decode the files blob[offsets[i]:offsets[i + 1]] (host bytes): the largest max_partitions word of their
     headers, at least 1.  A word above IREC_MAX_PARTITIONS does not count: the reader refuses that file whatever max_K is
-    (IREC_REC_E_BLOCK_COUNTS), and a damaged word must not size a buffer."""
+    (IREC_REC_E_BLOCK_COUNTS), and a damaged word must not size a buffer.  tables: with count tables the header word is useless
+    (0xFFFFFFFF), so the bound is the tables' largest K."""
     blob = np.ascontiguousarray(blob, dtype=np.uint8)
     need = 1
     for i in range(len(offsets) - 1):
         words = rec_header_words(blob[int(offsets[i]):int(offsets[i + 1])])
         if words is not None:
             need = max([need] + [m for m in words["max_partitions"] if m <= _lib.MAX_PARTITIONS])
+    if tables is not None and tables.max_K is not None:
+        need = max(need, tables.max_K)                 # (a file coded under count tables says 0xFFFFFFFF: the bound is the tables')
     return need
 
 

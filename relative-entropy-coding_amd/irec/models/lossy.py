@@ -17,7 +17,7 @@ from .. import _lib
 from ..coding.beam_search_coder import MorePartitionsNeeded, PendingCode, SplitNotResident
 from ..coding.utils import CodingError
 from ..io import read_compressed_code, write_compressed_code
-from .resnet_vae import STATUS_HEADER, STATUS_ROWS, ModelError, _Normal, _nchw, _nhwc, deterministic_transforms, status_text
+from .resnet_vae import STATUS_HEADER, STATUS_ROWS, STATUS_TABLE, ModelError, _Normal, _nchw, _nhwc, deterministic_transforms, status_text
 
 
 def _down(cin, cout, n):
@@ -161,14 +161,16 @@ class Large2LevelVAE(nn.Module):
         return K, idx, bpr, reconstruction
 
     @torch.no_grad()
-    def compress_rec(self, images, seed, sampler, block_size=None, rec_on_device=False, return_pendings=False):
+    def compress_rec(self, images, seed, sampler, block_size=None, rec_on_device=False, return_pendings=False, tables=None):
         """A batch to its .rec files: (blob uint8, offsets int64 [N + 1], reconstruction), image i's file blob[offsets[i]:offsets[i + 1]]
         byte for byte what `compress(file_path, ...)` writes for it.  rec_on_device=False (the default: an arithmetic coder's stream is
         serial, and Kodak-size streams are long): one packed read-back, then irec.io.encode_files_ragged on host threads; blob and
         offsets are numpy.  rec_on_device=True: the rows stay on the device (PendingCode.gather_packed_ragged_device,
         irec.io.encode_files_device_ragged), only K, the offsets and the statuses are read back; blob and offsets are CUDA tensors.
         block_size: the header's block-size word (default: the coder's own; 0 for a coder without one).
-        return_pendings: also the rows the files were built from, ((blob, offsets, reconstruction), (K, idx, blocks_per_res))."""
+        return_pendings: also the rows the files were built from, ((blob, offsets, reconstruction), (K, idx, blocks_per_res)).
+        tables: an irec.io.SymbolTables (harness.fit_symbol_tables_lossy) -- the streams coded under its count tables on either leg, the
+        files flagged as the reference's writer flags them; decompress_rec needs the same tables."""
         from ..io import encode_files_device_ragged, encode_files_ragged
         _, _, height, width = images.shape
         gather = PendingCode.gather_packed_ragged_device if rec_on_device else PendingCode.gather_packed_ragged
@@ -176,7 +178,7 @@ class Large2LevelVAE(nn.Module):
         if block_size is None:
             block_size = sampler.block_size if sampler.block_size is not None else 0
         encode = encode_files_device_ragged if rec_on_device else encode_files_ragged
-        blob, offsets = encode(seed, (height, width, 3), block_size, K, idx, self._max_index(sampler), bpr)
+        blob, offsets = encode(seed, (height, width, 3), block_size, K, idx, self._max_index(sampler), bpr, tables=tables)
         return ((blob, offsets, reconstruction), (K, idx, bpr)) if return_pendings else (blob, offsets, reconstruction)
 
     def _packed_rows(self, n, bpr, device):
@@ -239,12 +241,14 @@ class Large2LevelVAE(nn.Module):
         return reconstruction, host
 
     @staticmethod
-    def _decode_files_host(blob, offsets, bpr, max_K):
+    def _decode_files_host(blob, offsets, bpr, max_K, tables=None):
         """irec.io.decode_files_ragged with a verdict per file: (headers, K, idx, status int32 [N]).  The host reader stops at the first
         file it refuses; only then is every file read alone, a refused one leaving zero rows and the irec_rec_status of the reader's
         words for it (the first of a class that shares its text)."""
-        from ..io.utils import _REC_STATUS_TEXT, decode_files_ragged
+        from ..io.utils import _REC_STATUS_TEXT, _decode_files_tables_status, decode_files_ragged
         n = len(offsets) - 1
+        if tables is not None:                          # (the reader with tables gives a verdict per file itself)
+            return _decode_files_tables_status(blob, offsets, bpr, max_K, tables)
         try:
             hdr, K, idx = decode_files_ragged(blob, offsets, bpr, max_K)
             return hdr, K, idx, np.zeros(n, dtype=np.int32)
@@ -263,7 +267,7 @@ class Large2LevelVAE(nn.Module):
         return hdr, K, idx, status
 
     @staticmethod
-    def _files_max_K_device(blob, offsets, R=2):
+    def _files_max_K_device(blob, offsets, R=2, tables=None):
         """Index slots per block that decode the files of a blob on the device (irec.io.rec_files_max_K): only the 28 + 16 R header bytes
         of every file are gathered and copied to the host."""
         from ..io.utils import rec_files_max_K
@@ -271,14 +275,14 @@ class Large2LevelVAE(nn.Module):
         off = offsets.to(dev) if hasattr(offsets, "is_cuda") else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev)
         n = off.numel() - 1
         if n < 1 or blob.numel() < 1:
-            return 1
+            return rec_files_max_K(np.zeros(0, np.uint8), np.zeros(1, np.int64), tables)
         at = (off[:-1, None] + torch.arange(hb, device=dev)).clamp_(0, blob.numel() - 1)
         whole = (off[1:] - off[:-1] >= hb) & (off[:-1] >= 0) & (off[1:] <= blob.numel())          # a shorter file: a zero header, no words
         head = blob.reshape(-1)[at] * whole[:, None].to(torch.uint8)
-        return rec_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb)
+        return rec_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb, tables)
 
     @torch.no_grad()
-    def decompress_rec(self, blob, offsets, seed, image_shape, sampler, max_K=None, strict=True, rec_on_device=False):
+    def decompress_rec(self, blob, offsets, seed, image_shape, sampler, max_K=None, strict=True, rec_on_device=False, tables=None):
         """The inverse of compress_rec: N .rec files (file i = blob[offsets[i]:offsets[i + 1]]) to reconstructions [N, 3, H, W].
         rec_on_device=False: the files are read on host threads (irec.io.decode_files_ragged; blob / offsets numpy or tensors) and the
         rows uploaded once; rec_on_device=True: blob is a CUDA tensor and the rows never leave the device
@@ -287,27 +291,31 @@ class Large2LevelVAE(nn.Module):
         the encoding of BidirectionalResNetVAE.decompress_rec: 0 ok; 1 .. 18 irec_rec_status; STATUS_HEADER; STATUS_ROWS +
         irec_rows_status; first cause in that order.  strict: CodingError with the cause, "(image i)" appended; strict=False:
         (reconstruction, status int32 numpy [N]), the images with status 0 being what they would be without the others.
-        max_K: index slots per block (None: the largest max_partitions word of the files' headers)."""
+        max_K: index slots per block (None: the largest max_partitions word of the files' headers; with count tables, their largest K).
+        tables: the irec.io.SymbolTables the files were written under; a file whose header asks for tables the call did not bring has
+        status 5 (IREC_REC_E_COUNT_FILES), one without flags decodes under the default models."""
         from ..io.utils import _decode_files_device_ragged_launch, rec_files_max_K
         n, _, height, width = image_shape
         bpr = self.blocks_per_res(image_shape, sampler.block_size)
         device = self._prior_base.device
         if rec_on_device:
             if max_K is None:
-                max_K = self._files_max_K_device(blob, offsets)
-            hdr, K, idx, rec_status = _decode_files_device_ragged_launch(blob, offsets, bpr, int(max_K), on_device=True)
+                max_K = self._files_max_K_device(blob, offsets, tables=tables)
+            hdr, K, idx, rec_status = _decode_files_device_ragged_launch(blob, offsets, bpr, int(max_K), on_device=True, tables=tables)
             words = hdr.to(torch.int64).bitwise_and_(0xFFFFFFFF)
         else:
             blob_h = np.ascontiguousarray(blob.cpu().numpy() if hasattr(blob, "cpu") else blob, dtype=np.uint8)
             off_h = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
             if max_K is None:
-                max_K = rec_files_max_K(blob_h, off_h)
-            hdr, K, idx, rec_status = self._decode_files_host(blob_h, off_h, bpr, int(max_K))
+                max_K = rec_files_max_K(blob_h, off_h, tables)
+            hdr, K, idx, rec_status = self._decode_files_host(blob_h, off_h, bpr, int(max_K), tables)
             both = np.concatenate([K[..., None], idx], axis=2)                                    # one upload for the rows
             both = torch.from_numpy(both).to(device)
             K, idx = both[..., 0], both[..., 1:]
             words = torch.from_numpy(hdr.astype(np.int64)).to(device)
             rec_status = torch.from_numpy(rec_status).to(device)
+        if tables is not None:
+            rec_status = torch.where(rec_status == _lib.IREC_REC_E_TABLE, torch.full_like(rec_status, STATUS_TABLE), rec_status)
         if len(rec_status) != n:
             raise ModelError(f"{len(rec_status)} files for images of shape {tuple(image_shape)}")
         want = torch.tensor([int(seed) & 0xFFFFFFFF, int(height), int(width), 3, 2], dtype=torch.int64).to(device)

@@ -27,6 +27,7 @@ class ModelError(Exception):
 
 # the joined per-image status of decompress_rec / decompress_packed beside irec_rec_status (1 .. 18)
 STATUS_HEADER = 19      # the file's seed, height, width, channels or R differ from the call's
+STATUS_TABLE = 20       # IREC_REC_E_TABLE (19 on the wire, which STATUS_HEADER has here): a symbol table that cannot be coded under
 STATUS_ROWS = 32        # + irec_rows_status (1 K_RANGE, 2 INDEX_RANGE, 3 RATIO_TABLE)
 STATUS_RESIDUAL = 48    # + irec_res_status (decompress_lossless: the .res file of an image whose .rec file decoded)
 
@@ -45,6 +46,7 @@ def status_text(status, table_length=None, requested=None):
             return RATIO_TABLE_TEXT.format(table_length, requested)
         return RATIO_TABLE_TEXT.split(".")[0] + "."
     own = {STATUS_HEADER: "decompress_rec: the file's header (seed, image shape, residual blocks) differs from the arguments",
+           STATUS_TABLE: _REC_STATUS_TEXT[_lib.IREC_REC_E_TABLE],
            STATUS_ROWS + _lib.IREC_ROWS_E_K_RANGE: "partition count out of range [min_K, max_K]",
            STATUS_ROWS + _lib.IREC_ROWS_E_INDEX_RANGE: "index out of range [0, n_samples)"}
     return own.get(status) or _REC_STATUS_TEXT.get(status, f"irec_rec: status {status}")
@@ -427,12 +429,14 @@ class BidirectionalResNetVAE(nn.Module):
         raise MorePartitionsNeeded(max(b.coder._max_K_hint for b in self.residual_blocks) + 1)
 
     @torch.no_grad()
-    def compress_rec(self, image, seed, update_sampler=False, block_size=None, return_pendings=False):
+    def compress_rec(self, image, seed, update_sampler=False, block_size=None, return_pendings=False, tables=None):
         """`compress_packed` with the indices never leaving the device: (blob uint8, offsets int64 [N + 1], reconstruction), CUDA tensors
         -- image i's .rec file is blob[offsets[i]:offsets[i + 1]], byte for byte what irec.io.encode_files makes of compress_packed's
         arrays (irec.io.encode_files_device: the arithmetic coder runs on the device, one lane per stream).  Only the partition counts
         and the files' offsets are read back.  block_size: the header's block-size word (default: the coders' own).
-        return_pendings: also the device K / idx views the files were built from, ((blob, offsets, reconstruction), (K, idx))."""
+        return_pendings: also the device K / idx views the files were built from, ((blob, offsets, reconstruction), (K, idx)).
+        tables: an irec.io.SymbolTables (harness.fit_symbol_tables) -- the streams coded under its count tables, the files flagged as
+        the reference's writer flags them; decompress_rec needs the same tables."""
         from ..io import encode_files_device
         _, _, height, width = image.shape
         for _attempt in range(6):
@@ -445,7 +449,7 @@ class BidirectionalResNetVAE(nn.Module):
             # the header's max_index word: the samples a step chooses among (the sequential coder's are its sampler's)
             n_samples = coder.sampler.n_samples() if coder.sampler is not None else coder.n_samples
             blob, offsets = encode_files_device(seed, (height, width, 3), coder.block_size if block_size is None else block_size, K, idx,
-                                                max_index=n_samples)
+                                                max_index=n_samples, tables=tables)
             return ((blob, offsets, reconstruction), (K, idx)) if return_pendings else (blob, offsets, reconstruction)
         raise MorePartitionsNeeded(max(b.coder._max_K_hint for b in self.residual_blocks) + 1)
 
@@ -585,12 +589,14 @@ class BidirectionalResNetVAE(nn.Module):
             return reconstruction
         return reconstruction, host
 
-    def _decompress_rec_device(self, blob, offsets, seed, image_shape, max_K):
+    def _decompress_rec_device(self, blob, offsets, seed, image_shape, max_K, tables=None):
         """Everything of decompress_rec that runs on the device: the three launches of the .rec reader, the header check, the pass,
         the joined status.  Returns (reconstruction, status int32 [N] on the device, K).  No host synchronisation."""
         from ..io.utils import _decode_files_device_launch
         n, R, bpt = int(image_shape[0]), self.num_res_blocks, self.blocks_per_tensor(image_shape)
-        hdr, K, idx, rec_status = _decode_files_device_launch(blob, offsets, R, bpt, max_K, on_device=True)
+        hdr, K, idx, rec_status = _decode_files_device_launch(blob, offsets, R, bpt, max_K, on_device=True, tables=tables)
+        if tables is not None:
+            rec_status = torch.where(rec_status == _lib.IREC_REC_E_TABLE, torch.full_like(rec_status, STATUS_TABLE), rec_status)
         words = hdr.to(torch.int64).bitwise_and_(0xFFFFFFFF)
         words = torch.cat([words[:, 0:1], words[:, 3:6], words[:, 8:9]], dim=1)      # seed, height, width, channels, R
         differs = (words != self._header_want(seed, image_shape, K.device)).any(dim=1)
@@ -601,26 +607,27 @@ class BidirectionalResNetVAE(nn.Module):
                                          torch.where(rows_status != 0, rows_status + STATUS_ROWS, rows_status)))
         return reconstruction, joined, K
 
-    def files_max_K(self, blob, offsets):
+    def files_max_K(self, blob, offsets, tables=None):
         """Index slots per block that decode the files of a blob on the device: the largest max_partitions word of their headers
-        (irec.io.rec_files_max_K).  Only the 28 + 16 R header bytes of every file are gathered and copied to the host."""
+        (irec.io.rec_files_max_K; with count tables, those tables' largest K).  Only the 28 + 16 R header bytes of every file are
+        gathered and copied to the host."""
         from ..io.utils import rec_files_max_K
         dev, hb = blob.device, 28 + 16 * self.num_res_blocks
         off = offsets.to(dev) if hasattr(offsets, "is_cuda") else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev)
         n = off.numel() - 1
         if n < 1 or blob.numel() < 1:
-            return 1
+            return rec_files_max_K(np.zeros(0, np.uint8), np.zeros(1, np.int64), tables)
         at = (off[:-1, None] + torch.arange(hb, device=dev)).clamp_(0, blob.numel() - 1)
         whole = (off[1:] - off[:-1] >= hb) & (off[:-1] >= 0) & (off[1:] <= blob.numel())          # a shorter file: a zero header, no words
         head = blob.reshape(-1)[at] * whole[:, None].to(torch.uint8)
-        return rec_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb)
+        return rec_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb, tables)
 
     @torch.no_grad()
-    def _decompress_rec_status(self, blob, offsets, seed, image_shape, max_K=None):
+    def _decompress_rec_status(self, blob, offsets, seed, image_shape, max_K=None, tables=None):
         """decompress_rec up to its read-back: (reconstruction, status int32 numpy [N], K on the device)."""
         if max_K is None:
-            max_K = self.files_max_K(blob, offsets)
-        reconstruction, joined, K = self._decompress_rec_device(blob, offsets, seed, image_shape, int(max_K))
+            max_K = self.files_max_K(blob, offsets, tables)
+        reconstruction, joined, K = self._decompress_rec_device(blob, offsets, seed, image_shape, int(max_K), tables)
         return reconstruction, joined.cpu().numpy(), K
 
     @torch.no_grad()
@@ -629,14 +636,27 @@ class BidirectionalResNetVAE(nn.Module):
         device or the host) to reconstructions [N, 3, H, W], with the indices never on the host: one launch of the device reader
         (irec.io.decode_files_device's launch form), the headers checked on the device against seed / image_shape / R, the pass
         (every coder checks its rows on the device), and ONE read-back -- the per-image status:
-          0 ok;  1 .. 18 irec_rec_status (include/irec.h);  STATUS_HEADER: seed, height, width, channels or R differ from the
+          0 ok;  1 .. 19 irec_rec_status (include/irec.h);  STATUS_HEADER: seed, height, width, channels or R differ from the
           arguments;  STATUS_ROWS + irec_rows_status: a count or an index the coder cannot decode.  First cause in that order.
         strict: CodingError with the coder's text for the first such image, "(image i)" appended; strict=False: (reconstruction,
         status int32 numpy [N]), the images with status 0 being what they would be without the others (a refused image's rows read as
         zero partitions).  max_K: index slots per block (a file with a longer row: IREC_REC_E_MAX_K); None: the largest
         max_partitions word of the files' headers (files_max_K) -- a second, small read-back of the header bytes, which a driver that
-        has the bytes on the host already (harness.decompress_images) spares by passing max_K."""
+        has the bytes on the host already (harness.decompress_images) spares by passing max_K.
+        A file written under count tables (compress_rec(tables=)) has status 5 here: decompress_rec_tables reads it."""
         reconstruction, host, K = self._decompress_rec_status(blob, offsets, seed, image_shape, max_K)
+        if strict:
+            self._raise_status(host, K)
+            return reconstruction
+        return reconstruction, host
+
+    @torch.no_grad()
+    def decompress_rec_tables(self, blob, offsets, seed, image_shape, tables, max_K=None, strict=True):
+        """decompress_rec for files written under an irec.io.SymbolTables (compress_rec(tables=)); a method of its own because
+        decompress_rec's signature is pinned.  The file's header flags decide per kind of stream: a flagged kind is read under the
+        call's table, or has status 5 (IREC_REC_E_COUNT_FILES) if the call brought none; a file without flags decodes under the
+        default models, so one call reads both sorts.  max_K None: the largest of the headers' words and the count tables' K."""
+        reconstruction, host, K = self._decompress_rec_status(blob, offsets, seed, image_shape, max_K, tables)
         if strict:
             self._raise_status(host, K)
             return reconstruction
