@@ -98,7 +98,7 @@ irec_status irec_rec_test_core_encode_files_ragged(uint32_t seed, uint32_t block
 irec_status irec_rec_test_core_decode_files_ragged(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
                                                    const int32_t *blocks_per_res, int32_t max_K, uint32_t *headers, int32_t *K, int32_t *idx,
                                                    int32_t *status);
-/* The same of irec_rec_encode_files_device_tables / irec_rec_decode_files_device_tables (csrc/irec_rec_tables.hip): the core over
+/* The same of irec_rec_encode_files_device_tables / irec_rec_decode_files_device_tables (csrc/irec_rec.hip): the core over
  * irec_rec::Tables, every pointer a host pointer, one thread. */
 irec_status irec_rec_test_core_encode_files_tables(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
                                                    uint32_t channels, int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res,

@@ -507,8 +507,9 @@ IREC_REC_HD inline int32_t decode_block_status(const DecodeCall &c, int64_t s) {
   return c.stream_status[NR + s] ? c.stream_status[NR + s] : c.stream_status[s];
 }
 
-// ---- a whole call over host memory, lane after lane in a plain loop: what the kernels of irec_rec.hip do, for the test hooks and for
-//      scripts/rec_core_check.cpp (the workspace bound by the caller) -----------------------------------------------------------------
+// ---- a whole call over host memory, lane after lane in a plain loop: what the kernels of irec_rec.hip do, for the stand-alone check
+//      programs (scripts/rec_*_check.cpp; the workspace bound by the caller).  The library's own host forms deal the same lanes to
+//      threads: irec_rec_call.h -------------------------------------------------------------------------------------------------------
 template <class T>
 inline void encode_call_host(const EncodeCall &c, const T &tb) {
   const int64_t streams = 2 * (int64_t)c.N * c.R;

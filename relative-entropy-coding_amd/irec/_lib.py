@@ -95,6 +95,32 @@ _i64 = ctypes.c_int64
 _i32 = ctypes.c_int32
 _PP = ctypes.POINTER(IrecParams)
 
+# The argument runs that the batched .rec entries of include/irec.h (and their irec_rec_test_core_* hooks) are put together from
+_REC_HEADER = [ctypes.c_uint32] * 6         # seed, block_size, max_index, height, width, channels
+_REC_ROWS = [_vp, _i64, _vp, _i64]          # K, k_stride, idx, idx_stride
+_REC_TABLES = [_vp, _i32, _vp, _vp, _i64]   # index_cum, n_index_symbols, count_cum, count_first, n_count_cum
+_REC_WORKSPACE = [_vp, ctypes.c_size_t, _vp]   # workspace, workspace_bytes, hip_stream
+
+
+def _rec_batched():
+    """irec_rec_{encode,decode}_files[_device | (hook) test_core][ | _ragged | _tables]: eighteen entries, one set of fragments."""
+    rows = {}
+    for suffix, blocks_per_res, tables in (("", _i32, False), ("_ragged", _vp, False), ("_tables", _vp, True)):
+        tb = _REC_TABLES if tables else []
+        enc = _REC_HEADER + [_i32, _i32, blocks_per_res, _i32]       # ..., n_images, n_res_blocks, blocks_per_res, max_K
+        dec = [_vp, _vp, _i32, _i32, blocks_per_res, _i32] + tb       # bytes, offsets, n_images, n_res_blocks, blocks_per_res, max_K
+        files = [_vp, _i64, _vp, _vp]                                 # out, cap, offsets, status
+        outputs = [_vp, _vp, _vp, _vp]                                # headers, K, idx, status
+        rows[f"irec_rec_encode_files_device{suffix}"] = (ctypes.c_int, enc + _REC_ROWS + tb + files + _REC_WORKSPACE)
+        rows[f"irec_rec_decode_files_device{suffix}"] = (ctypes.c_int, dec + outputs + _REC_WORKSPACE)
+        rows[f"irec_rec_test_core_encode_files{suffix}"] = (ctypes.c_int, enc + _REC_ROWS + tb + files)
+        rows[f"irec_rec_test_core_decode_files{suffix}"] = (ctypes.c_int, dec + outputs)
+        # the host forms: packed rows, a thread count; a status per image only under tables (the others name the file in their error)
+        rows[f"irec_rec_encode_files{suffix}"] = (_i64, enc + [_vp, _vp] + tb + files[:3 + tables] + [_i32])
+        rows[f"irec_rec_decode_files{suffix}"] = (ctypes.c_int, dec + outputs[:3 + tables] + [_i32])
+    return rows
+
+
 # name -> (restype, argtypes); every symbol declared in include/irec.h
 SIGNATURES = {
     "irec_last_error": (ctypes.c_char_p, []),
@@ -163,35 +189,9 @@ SIGNATURES = {
     "irec_rec_unpack_bits": (_i64, [_vp, _i64, _vp, _i64]),
     "irec_rec_encode_file": (_i64, [ctypes.c_uint32] * 6 + [_i32, _vp, _vp, _vp, _vp, _i64]),
     "irec_rec_decode_file": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64]),
-    "irec_rec_encode_files": (_i64, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i32]),
-    "irec_rec_decode_files": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32]),
-    "irec_rec_encode_files_ragged": (_i64, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32]),
-    "irec_rec_decode_files_ragged": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i32]),
     "irec_rec_device_workspace_bytes": (ctypes.c_size_t, [_i32, _i32]),
-    "irec_rec_encode_files_device": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp,
-                                                    _vp, ctypes.c_size_t, _vp]),
-    "irec_rec_decode_files_device": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    "irec_rec_encode_files_device_ragged": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
-                                                           _vp, _vp, ctypes.c_size_t, _vp]),
-    "irec_rec_decode_files_device_ragged": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    "irec_rec_test_core_encode_files_ragged": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64,
-                                                              _vp, _vp]),
-    "irec_rec_test_core_decode_files_ragged": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp]),
-    "irec_rec_test_core_encode_files": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
-    "irec_rec_test_core_decode_files": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    **_rec_batched(),
     "irec_rec_tables_build": (ctypes.c_int, [_vp, _i32, _vp]),
-    # (index_cum, n_index_symbols, count_cum, count_first, n_count_cum) = [_vp, _i32, _vp, _vp, _i64] in every *_tables entry
-    "irec_rec_encode_files_tables": (_i64, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _vp] + [_vp, _i32, _vp, _vp, _i64] +
-                                     [_vp, _i64, _vp, _vp, _i32]),
-    "irec_rec_decode_files_tables": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32] + [_vp, _i32, _vp, _vp, _i64] + [_vp, _vp, _vp, _vp, _i32]),
-    "irec_rec_encode_files_device_tables": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64] +
-                                            [_vp, _i32, _vp, _vp, _i64] + [_vp, _i64, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    "irec_rec_decode_files_device_tables": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32] + [_vp, _i32, _vp, _vp, _i64] +
-                                            [_vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    "irec_rec_test_core_encode_files_tables": (ctypes.c_int, [ctypes.c_uint32] * 6 + [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64] +
-                                               [_vp, _i32, _vp, _vp, _i64] + [_vp, _i64, _vp, _vp]),
-    "irec_rec_test_core_decode_files_tables": (ctypes.c_int, [_vp, _vp, _i32, _i32, _vp, _i32] + [_vp, _i32, _vp, _vp, _i64] +
-                                               [_vp, _vp, _vp, _vp]),
     "irec_rec_hist_rows": (ctypes.c_int, [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "irec_rec_hist_rows_device": (ctypes.c_int, [_i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "irec_res_device_workspace_bytes": (ctypes.c_size_t, [_i32, _i64]),

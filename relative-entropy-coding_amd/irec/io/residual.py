@@ -9,6 +9,7 @@ import math
 import numpy as np
 
 from .. import _lib
+from . import _files
 
 # Symbols per stream where a call does not say.  A device call's time is its longest lane's, about 0.26 ms + 4.7 us per symbol of a
 # stream up to hundreds of images, and a stream costs its 16-bit length word plus about 9 bits of coder end and padding
@@ -37,10 +38,7 @@ def res_status_text(status):
 
 
 def _raise_first_status(status):
-    bad = np.flatnonzero(status)
-    if bad.size:
-        i = int(bad[0])
-        raise ValueError(f"{res_status_text(status[i])} (image {i})")
+    _files.raise_first_status(status, res_status_text)
 
 
 def _scale32(scale):
@@ -107,8 +105,7 @@ def decode_residuals(blob, offsets, loc, scale, stream_len=None, strict=True, n_
         stream_len = stream_len_of(blob[int(offsets[0]):int(offsets[1])])
         stream_len = stream_len if stream_len and 1 <= stream_len <= MAX_STREAM_LEN else None
     n, c, h, w, stream_len, _ = _shape(loc.shape, loc.shape, stream_len, "decode_residuals")
-    if offsets.size != n + 1 or offsets[0] < 0 or (np.diff(offsets) < 0).any() or offsets[-1] > blob.size:
-        raise ValueError("decode_residuals: offsets must be [N + 1], non-decreasing and end inside the blob")
+    offsets = _files.host_offsets(offsets, blob.size, "decode_residuals", n)
     pixels = np.zeros(loc.shape, dtype=np.uint8)
     status = np.zeros(max(n, 1), dtype=np.int32)
     keep = blob if blob.size else np.zeros(1, np.uint8)
@@ -167,15 +164,12 @@ def _encode_residuals_device_launch(pixels, loc, scale, stream_len, out):
     dev = loc.device
     with torch.cuda.device(dev):
         ws = torch.empty(lib.irec_res_device_workspace_bytes(n, ns), dtype=torch.uint8, device=dev)
-        both = torch.empty(n + 1 + (n + 1) // 2, dtype=torch.int64, device=dev)          # offsets, then status: one read-back
-        offsets, status = both[:n + 1], both[n + 1:].view(torch.int32)[:n]
+        offsets, status, both = _files.offsets_and_status(n, dev)
         st = lib.irec_res_encode_files_device(pixels.data_ptr() if n else None, loc.data_ptr() if n else None, _scale32(scale), n, h, w, c,
                                               stream_len, out.data_ptr() if out.numel() else None, out.numel(), offsets.data_ptr(),
                                               status.data_ptr() if n else None, ws.data_ptr(), ws.numel(),
                                               torch.cuda.current_stream().cuda_stream)
-    if st == _lib.IREC_E_INVALID:
-        raise ValueError(lib.irec_last_error().decode())
-    _lib.check(st, "irec_res_encode_files_device")
+    _files.check_status(st, "irec_res_encode_files_device")
     return offsets, status, both
 
 
@@ -190,21 +184,14 @@ def encode_residuals_device(pixels, loc, scale, stream_len=None, out=None):
         out = torch.empty(max(n * (HEADER_BYTES + 2 * ns + c * h * w) + 64, 1), dtype=torch.uint8, device=loc.device)
     elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == loc.device):
         raise ValueError("encode_residuals_device: out must be a contiguous CUDA uint8 tensor on loc's device")
-    for _attempt in range(2):
-        offsets, _, both = _encode_residuals_device_launch(pixels, loc, scale, stream_len, out)
-        host = both.cpu().numpy()
-        _raise_first_status(host[n + 1:].view(np.int32)[:n])
-        total = int(host[n])
-        if total <= out.numel():
-            return out[:total], offsets
-        out = torch.empty(total, dtype=torch.uint8, device=loc.device)                     # exactly what the first run asked for
-    raise ValueError("irec_res_encode_files_device: the files did not fit the size the call itself reported")
+    return _files.encode_device(lambda o: _encode_residuals_device_launch(pixels, loc, scale, stream_len, o), n, out, res_status_text,
+                                "irec_res_encode_files_device")
 
 
 def _decode_residuals_device_launch(blob, offsets, loc, scale, stream_len, on_device=False):
     """One irec_res_decode_files_device call on the current stream: (pixels uint8 of loc's shape, status int32 [N]) on the device,
     nothing read back.  Host offsets are checked against the blob; on_device: offsets that are on the device stay there, clamped into
-    the blob and made non-decreasing by two small device operations (the rule of irec.io.utils._decode_files_device_launch)."""
+    the blob and made non-decreasing by two small device operations (_files.device_offsets)."""
     import torch
     lib = _lib.load()
     _check_device(None, loc, "decode_residuals_device")
@@ -213,15 +200,7 @@ def _decode_residuals_device_launch(blob, offsets, loc, scale, stream_len, on_de
     n, c, h, w, stream_len, ns = _shape(loc.shape, loc.shape, stream_len, "decode_residuals_device")
     blob, loc = blob.contiguous(), loc.contiguous()
     dev = loc.device
-    if on_device and hasattr(offsets, "is_cuda") and offsets.is_cuda:
-        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() != n + 1:
-            raise ValueError("decode_residuals_device: device offsets must be int64 [N + 1]")
-        off_dev = torch.cummax(offsets.to(dev).clamp(0, blob.numel()), dim=0).values.contiguous()
-    else:
-        off_host = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
-        if off_host.size != n + 1 or off_host[0] < 0 or (np.diff(off_host) < 0).any() or off_host[-1] > blob.numel():
-            raise ValueError("decode_residuals_device: offsets must be [N + 1], non-decreasing and end inside the blob")
-        off_dev = torch.from_numpy(off_host.copy()).to(dev)
+    off_dev = _files.device_offsets(offsets, blob, dev, on_device, "decode_residuals_device", n)
     with torch.cuda.device(dev):
         ws = torch.empty(lib.irec_res_device_workspace_bytes(n, ns), dtype=torch.uint8, device=dev)
         pixels = torch.empty(loc.shape, dtype=torch.uint8, device=dev)
@@ -229,9 +208,7 @@ def _decode_residuals_device_launch(blob, offsets, loc, scale, stream_len, on_de
         st = lib.irec_res_decode_files_device(blob.data_ptr() if blob.numel() else ws.data_ptr(), off_dev.data_ptr(), loc.data_ptr() if n else None,
                                               _scale32(scale), n, h, w, c, stream_len, pixels.data_ptr() if n else None, status.data_ptr(),
                                               ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
-    if st == _lib.IREC_E_INVALID:
-        raise ValueError(lib.irec_last_error().decode())
-    _lib.check(st, "irec_res_decode_files_device")
+    _files.check_status(st, "irec_res_decode_files_device")
     return pixels, status[:n]
 
 

@@ -21,6 +21,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 
 from .. import _lib
+from . import _files
 from .entropy_coding import ArithmeticCoder
 
 _STATIC = struct.Struct("IIIIIHHHH")
@@ -99,16 +100,14 @@ def _native_encode(seed, image_shape, block_size, block_indices, max_index):
     flat = np.fromiter(itertools.chain.from_iterable(itertools.chain.from_iterable(block_indices)), dtype=np.int32,
                        count=int(K.sum()))
     h, w, c = (int(v) for v in image_shape)
-    cap = 64 + 16 * len(bpr) + 4 * (K.size + flat.size) + 64
-    while True:
-        out = np.empty(cap, dtype=np.uint8)
+
+    def call(out):
         n = lib.irec_rec_encode_file(int(seed), int(block_size), int(max_index), h, w, c, len(bpr), bpr.ctypes.data,
-                                     K.ctypes.data, flat.ctypes.data if flat.size else None, out.ctypes.data, cap)
+                                     K.ctypes.data, flat.ctypes.data if flat.size else None, out.ctypes.data, out.size)
         if n < 0:
             raise ValueError(lib.irec_io_last_error().decode())
-        if n <= cap:
-            return out[:n].tobytes()
-        cap = int(n)
+        return n
+    return _files.encode_host(call, 64 + 16 * len(bpr) + 4 * (K.size + flat.size) + 64).tobytes()
 
 
 def _native_decode(data):
@@ -142,59 +141,10 @@ def _native_decode(data):
     return int(hdr[0]), (int(hdr[3]), int(hdr[4]), int(hdr[5])), int(hdr[1]), blocks
 
 
-def encode_files(seed, image_shape, block_size, K, idx, max_index, n_threads=0, tables=None):
-    """N containers at once from a packed read-back (irec_rec_encode_files): K [N, R, bpt] int32, idx [N, R, bpt, max_K] int32.
-    Returns (blob uint8, offsets int64 [N + 1]): file i = blob[offsets[i]:offsets[i + 1]], byte for byte what
-    write_compressed_code writes for image i (rec/io/utils.py:7-106, default symbol models).
-    tables: a SymbolTables -- the files as write_compressed_code writes them with those count files (irec_rec_encode_files_tables)."""
-    lib = _lib.load()
-    K = np.ascontiguousarray(K, dtype=np.int32)
-    idx = np.ascontiguousarray(idx, dtype=np.int32)
-    n, r, bpt = K.shape
-    max_K = idx.shape[3] if idx.ndim == 4 else 0
-    assert idx.shape[:3] == K.shape
-    if tables is not None:
-        return encode_files_ragged(seed, image_shape, block_size, K.reshape(n, r * bpt), idx.reshape(n, r * bpt, max_K), max_index,
-                                   [bpt] * r, n_threads, tables=tables)
-    h, w, c = (int(v) for v in image_shape)
-    offsets = np.zeros(n + 1, dtype=np.int64)
-    cap = n * (64 + 16 * r) + 2 * int(K.sum()) + 16 * K.size + 1024
-    while True:
-        out = np.empty(cap, dtype=np.uint8)
-        total = lib.irec_rec_encode_files(int(seed), int(block_size), int(max_index), h, w, c, n, r, bpt, max_K, K.ctypes.data,
-                                          idx.ctypes.data if idx.size else None, out.ctypes.data, cap, offsets.ctypes.data,
-                                          int(n_threads))
-        if total < 0:
-            raise ValueError(lib.irec_io_last_error().decode())
-        if total <= cap:
-            return out[:total], offsets
-        cap = int(total)
-
-
-def decode_files(blob, offsets, n_res_blocks, blocks_per_res, max_K, n_threads=0, tables=None):
-    """The inverse of encode_files (irec_rec_decode_files): (headers [N, 9] uint32 -- seed, block_size, max_index, height,
-    width, channels, two flags, R --, K [N, R, bpt], idx [N, R, bpt, max_K] with rows zero-filled past K).
-    tables: a SymbolTables for the files whose header flags ask for one (irec_rec_decode_files_tables); files without flags decode
-    under the default models in the same call."""
-    if tables is not None:
-        r, bpt = int(n_res_blocks), int(blocks_per_res)
-        hdr, K, idx = decode_files_ragged(blob, offsets, [bpt] * r, max_K, n_threads, tables=tables)
-        return hdr, K.reshape(-1, r, bpt), idx.reshape(-1, r, bpt, idx.shape[-1])
-    lib = _lib.load()
-    blob = np.ascontiguousarray(blob, dtype=np.uint8)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    n = offsets.size - 1
-    hdr = np.zeros((n, 9), dtype=np.uint32)
-    K = np.zeros((n, n_res_blocks, blocks_per_res), dtype=np.int32)
-    idx = np.zeros((n, n_res_blocks, blocks_per_res, max(max_K, 1)), dtype=np.int32)
-    st = lib.irec_rec_decode_files(blob.ctypes.data, offsets.ctypes.data, n, int(n_res_blocks), int(blocks_per_res), int(max_K),
-                                   hdr.ctypes.data, K.ctypes.data, idx.ctypes.data, int(n_threads))
-    if st != 0:
-        raise ValueError(lib.irec_io_last_error().decode())
-    return hdr, K, idx[..., :max_K]
-
-
-# ---- the same two calls on the device (csrc/irec_rec.hip: one lane per stream over csrc/irec_rec_core.h) -----------------------------
+# ---- N containers at once: csrc/irec_io.cpp on the host, csrc/irec_rec.hip (one lane per stream over csrc/irec_rec_core.h) on the device
+#      and, host or device, under symbol tables ----------------------------------------------------------------------------------------
+# Every call works over rows: K [N, T], idx [N, T, max_K], T rows per image, block j of residual block r of image i at row
+# i T + first[r] + j.  The [N, R, bpt] of a call whose residual blocks are all of one size are the same rows seen as [N, R bpt].
 # irec_rec_status of include/irec.h -> the text the host coder gives for that cause
 _REC_STATUS_TEXT = {
     1: "irec_rec_encode_files: K out of range",
@@ -216,50 +166,289 @@ _REC_STATUS_TEXT = {
 }
 
 
+def _rec_status_text(status):
+    return _REC_STATUS_TEXT.get(status, "irec_rec: status %d" % status)
+
+
 def _raise_first_status(status):
     """ValueError with the host's text and its "(image i)" suffix for the first image whose status is nonzero."""
-    bad = np.flatnonzero(status)
-    if bad.size:
-        i = int(bad[0])
-        raise ValueError(f"{_REC_STATUS_TEXT.get(int(status[i]), 'irec_rec: status %d' % int(status[i]))} (image {i})")
+    _files.raise_first_status(status, _rec_status_text)
 
 
-def _block_strides(K, idx):
-    """(K, k_stride, idx, idx_stride) of include/irec.h: block b = (i R + r) bpt + j at K[b k_stride], idx[b idx_stride + t].  Views of
-    the packed arrays and of one joined [rows][1 + width] tensor pass as they are; anything else is made contiguous."""
+class _Layout:
+    """The blocks per residual block of a call: R residual blocks of bpt blocks each (uniform: any R the container holds), or one count
+    per residual block (ragged: the two-level lossy model codes 13 blocks at level 2 and 302 at level 1).  bpr int32 [R] either way,
+    T = sum(bpr) rows per image."""
+
+    def __init__(self, R, bpt=None, bpr=None):
+        self.R, self.bpt = int(R), bpt
+        self.bpr = np.full(self.R, bpt, dtype=np.int32) if bpr is None else bpr
+        self.T = self.R * bpt if bpr is None else int(bpr.sum())
+
+    @classmethod
+    def ragged(cls, blocks_per_res, what):
+        if isinstance(blocks_per_res, cls):
+            return blocks_per_res
+        bpr = np.ascontiguousarray(np.asarray(blocks_per_res, dtype=np.int64).reshape(-1))
+        if bpr.size < 1 or (bpr < 1).any() or int(bpr.sum()) > _lib.INT32_MAX:
+            raise ValueError(f"{what}: blocks_per_res must hold at least one entry, every entry >= 1, their sum an int32 (got {list(bpr)})")
+        return cls(bpr.size, bpr=bpr.astype(np.int32))
+
+    def entry(self, tables):
+        """(the suffix of the library entry a call of this layout reaches, its blocks_per_res argument): the entries without a suffix
+        take one count, `_ragged` an array; any tables go to `_tables`, which takes the array (at most REC_RAGGED_MAX_RES entries)."""
+        if tables is not None:
+            return "_tables", self.bpr.ctypes.data
+        return ("", self.bpt) if self.bpt is not None else ("_ragged", self.bpr.ctypes.data)
+
+
+def _block_rows(K, idx):
+    """K [N, R, bpt], idx [N, R, bpt, max_K] as rows [N, R bpt], [N, R bpt, max_K]: views with the block stride kept as the row stride
+    where the blocks of an image lie that far apart (a dimension of one included), copies otherwise."""
     n, r, bpt = K.shape
-    max_K = idx.shape[3]
-    ks = K.stride(2) if K.numel() else 1
-    if K.numel() and (ks < 1 or K.stride() != (r * bpt * ks, bpt * ks, ks)):
+    T, ks, ist = r * bpt, K.stride(2), idx.stride(2)
+    K = K.as_strided((n, T), (T * ks, ks)) if K.stride()[:2] == (T * ks, bpt * ks) else K.reshape(n, T)
+    if idx.stride()[:2] == (T * ist, bpt * ist):
+        return K, idx.as_strided((n, T, idx.shape[3]), (T * ist, ist, idx.stride(3)))
+    return K, idx.reshape(n, T, idx.shape[3])
+
+
+# ---- host ---------------------------------------------------------------------------------------------------------------------------------
+def _encode_rows_host(seed, image_shape, block_size, K, idx, max_index, layout, n_threads, tables, who):
+    """irec_rec_encode_files[_ragged|_tables] over contiguous rows: (blob uint8, offsets int64 [N + 1])."""
+    lib = _lib.load()
+    n, max_K = K.shape[0], idx.shape[2]
+    h, w, c = (int(v) for v in image_shape)
+    suffix, blocks = layout.entry(tables)
+    encode = getattr(lib, "irec_rec_encode_files" + suffix)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    status = np.zeros(max(n, 1), dtype=np.int32)               # (per-image statuses: the entry with tables only)
+    tb = () if tables is None else tables.host_args(layout.R, who)
+    last_error = lib.irec_io_last_error if tables is None else lib.irec_last_error
+
+    def call(out):
+        total = encode(int(seed), int(block_size), int(max_index), h, w, c, n, layout.R, blocks, max_K, K.ctypes.data,
+                       idx.ctypes.data if idx.size else None, *tb, out.ctypes.data, out.size, offsets.ctypes.data,
+                       *(() if tables is None else (status.ctypes.data,)), int(n_threads))
+        if total < 0:
+            raise ValueError(last_error().decode())
+        _raise_first_status(status[:n])
+        return total
+    return _files.encode_host(call, n * (64 + 16 * layout.R) + 2 * int(K.sum()) + 16 * K.size + 1024), offsets
+
+
+def _decode_rows_host(blob, offsets, layout, max_K, n_threads):
+    """irec_rec_decode_files[_ragged]: (headers [N, 9] uint32, K [N, T], idx [N, T, max_K] with rows zero-filled past K)."""
+    lib = _lib.load()
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n = offsets.size - 1
+    hdr = np.zeros((n, 9), dtype=np.uint32)
+    K = np.zeros((n, layout.T), dtype=np.int32)
+    idx = np.zeros((n, layout.T, max(max_K, 1)), dtype=np.int32)
+    suffix, blocks = layout.entry(None)
+    st = getattr(lib, "irec_rec_decode_files" + suffix)(blob.ctypes.data, offsets.ctypes.data, n, layout.R, blocks, int(max_K), hdr.ctypes.data,
+                                                        K.ctypes.data, idx.ctypes.data, int(n_threads))
+    if st != 0:
+        raise ValueError(lib.irec_io_last_error().decode())
+    return hdr, K, idx[..., :max_K]
+
+
+def encode_files(seed, image_shape, block_size, K, idx, max_index, n_threads=0, tables=None):
+    """N containers at once from a packed read-back (irec_rec_encode_files): K [N, R, bpt] int32, idx [N, R, bpt, max_K] int32.
+    Returns (blob uint8, offsets int64 [N + 1]): file i = blob[offsets[i]:offsets[i + 1]], byte for byte what
+    write_compressed_code writes for image i (rec/io/utils.py:7-106, default symbol models).
+    tables: a SymbolTables -- the files as write_compressed_code writes them with those count files (irec_rec_encode_files_tables)."""
+    K = np.ascontiguousarray(K, dtype=np.int32)
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    n, r, bpt = K.shape
+    assert idx.shape[:3] == K.shape
+    idx = idx.reshape(n, r * bpt, idx.shape[3]) if idx.ndim == 4 else np.zeros((n, r * bpt, 0), dtype=np.int32)
+    if tables is not None:
+        return encode_files_ragged(seed, image_shape, block_size, K.reshape(n, r * bpt), idx, max_index, [bpt] * r, n_threads, tables=tables)
+    return _encode_rows_host(seed, image_shape, block_size, K.reshape(n, r * bpt), idx, max_index, _Layout(r, bpt), n_threads, None, "encode_files")
+
+
+def decode_files(blob, offsets, n_res_blocks, blocks_per_res, max_K, n_threads=0, tables=None):
+    """The inverse of encode_files (irec_rec_decode_files): (headers [N, 9] uint32 -- seed, block_size, max_index, height,
+    width, channels, two flags, R --, K [N, R, bpt], idx [N, R, bpt, max_K] with rows zero-filled past K).
+    tables: a SymbolTables for the files whose header flags ask for one (irec_rec_decode_files_tables); files without flags decode
+    under the default models in the same call."""
+    r, bpt = int(n_res_blocks), int(blocks_per_res)
+    if tables is not None:
+        hdr, K, idx = decode_files_ragged(blob, offsets, [bpt] * r, max_K, n_threads, tables=tables)
+    else:
+        hdr, K, idx = _decode_rows_host(blob, offsets, _Layout(r, bpt), max_K, n_threads)
+    return hdr, K.reshape(K.shape[0], r, bpt), idx.reshape(K.shape[0], r, bpt, idx.shape[-1])
+
+
+def encode_files_ragged(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, n_threads=0, tables=None):
+    """encode_files for residual blocks of differing sizes (irec_rec_encode_files_ragged): K [N, T] int32, idx [N, T, max_K] int32,
+    T = sum(blocks_per_res).  Returns (blob uint8, offsets int64 [N + 1]); file i is byte for byte what write_compressed_code writes for
+    image i's lists."""
+    layout = _Layout.ragged(blocks_per_res, "encode_files_ragged")
+    K = np.ascontiguousarray(K, dtype=np.int32)
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    if K.ndim != 2 or K.shape[1] != layout.T or idx.ndim != 3 or idx.shape[:2] != K.shape:
+        raise ValueError(f"encode_files_ragged: K {K.shape} and idx {idx.shape} are not [N, {layout.T}] and [N, {layout.T}, max_K]")
+    return _encode_rows_host(seed, image_shape, block_size, K, idx, max_index, layout, n_threads, tables, "encode_files_ragged")
+
+
+def decode_files_ragged(blob, offsets, blocks_per_res, max_K, n_threads=0, tables=None):
+    """The inverse of encode_files_ragged (irec_rec_decode_files_ragged): (headers [N, 9] uint32, K [N, T], idx [N, T, max_K] with rows
+    zero-filled past K); ValueError naming the first file that is damaged or of another structure."""
+    layout = _Layout.ragged(blocks_per_res, "decode_files_ragged")
+    if tables is None:
+        return _decode_rows_host(blob, offsets, layout, max_K, n_threads)
+    hdr, K, idx, status = _decode_files_tables_status(blob, offsets, layout, max_K, tables, n_threads)
+    _raise_first_status(status)
+    return hdr, K, idx
+
+
+def _decode_files_tables_status(blob, offsets, blocks_per_res, max_K, tables, n_threads=0):
+    """irec_rec_decode_files_tables: (headers [N, 9] uint32, K [N, T], idx [N, T, max_K], status int32 [N]) -- a verdict per file, the
+    outputs of a refused one zero."""
+    lib = _lib.load()
+    layout = _Layout.ragged(blocks_per_res, "decode_files_ragged")
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    offsets = _files.host_offsets(offsets, blob.size, "decode_files_ragged")
+    n = offsets.size - 1
+    hdr = np.zeros((n, 9), dtype=np.uint32)
+    K = np.zeros((n, layout.T), dtype=np.int32)
+    idx = np.zeros((n, layout.T, int(max_K)), dtype=np.int32)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    pad = np.zeros(1, dtype=np.uint8)
+    st = lib.irec_rec_decode_files_tables(blob.ctypes.data if blob.size else pad.ctypes.data, offsets.ctypes.data, n, layout.R,
+                                          layout.bpr.ctypes.data, int(max_K), *tables.host_args(layout.R, "decode_files_ragged"),
+                                          hdr.ctypes.data, K.ctypes.data, idx.ctypes.data if idx.size else None, status.ctypes.data,
+                                          int(n_threads))
+    if st != 0:
+        raise ValueError(lib.irec_last_error().decode())
+    return hdr, K, idx, status[:n]
+
+
+# ---- device: CUDA tensors in and out, the launches on the current stream -----------------------------------------------------------------
+def _row_strides(K, idx):
+    """(K, k_stride, idx, idx_stride) of include/irec.h for K [N, T], idx [N, T, max_K]: row b = i T + t at K[b k_stride],
+    idx[b idx_stride + .].  Views of the packed arrays and of one joined [rows][1 + width] tensor pass as they are; anything else is
+    made contiguous."""
+    n, T = K.shape
+    max_K = idx.shape[2]
+    row = 1 if T > 1 else 0                            # (T = 1: the next row is the next image, and a dimension of one has no stride to speak of)
+    ks = K.stride(row) if K.numel() else 1
+    if K.numel() and (ks < 1 or K.stride(0) != T * ks):
         K, ks = K.contiguous(), 1
-    ist = idx.stride(2) if idx.numel() else max(max_K, 1)
-    if idx.numel() and (ist < max_K or idx.stride(3) != 1 or idx.stride()[:2] != (r * bpt * ist, bpt * ist)):
+    ist = idx.stride(row) if idx.numel() else max(max_K, 1)
+    if idx.numel() and (ist < max_K or idx.stride(2) != 1 or idx.stride(0) != T * ist):
         idx, ist = idx.contiguous(), max_K
     return K, int(ks), idx, int(ist)
 
 
-def _encode_files_device_launch(seed, image_shape, block_size, K, idx, max_index, out):
-    """One irec_rec_encode_files_device call on the current stream, nothing read back: (offsets int64 [N + 1], status int32 [N], both views
-    of `both`, which one copy fetches).  The bytes are in `out` only if offsets[N] <= out.numel()."""
+def _block_strides(K, idx):
+    """_row_strides for K [N, R, bpt], idx [N, R, bpt, max_K]: block b = (i R + r) bpt + j at K[b k_stride], idx[b idx_stride + t]."""
+    K2, ks, idx2, ist = _row_strides(*_block_rows(K, idx))
+    return K2.view(K.shape), ks, idx2.view(idx.shape), ist
+
+
+def _encode_rows_device_launch(seed, image_shape, block_size, K, idx, max_index, layout, out, tables, who):
+    """One irec_rec_encode_files_device[_ragged|_tables] call on the current stream over rows K [N, T], idx [N, T, max_K], nothing read
+    back: (offsets int64 [N + 1], status int32 [N], both views of `both`, which one copy fetches).  The bytes are in `out` only if
+    offsets[N] <= out.numel()."""
     import torch
     lib = _lib.load()
-    n, r, bpt = K.shape
-    max_K = idx.shape[3]
+    n, max_K = K.shape[0], idx.shape[2]
     h, w, c = (int(v) for v in image_shape)
-    K, ks, idx, ist = _block_strides(K, idx)
+    K, ks, idx, ist = _row_strides(K, idx)
     dev = K.device
+    suffix, blocks = layout.entry(tables)
     with torch.cuda.device(dev):
-        ws = torch.empty(lib.irec_rec_device_workspace_bytes(n, r), dtype=torch.uint8, device=dev)
-        both = torch.empty(n + 1 + (n + 1) // 2, dtype=torch.int64, device=dev)          # offsets, then status: one read-back
-        offsets, status = both[:n + 1], both[n + 1:].view(torch.int32)[:n]
-        st = lib.irec_rec_encode_files_device(int(seed), int(block_size), int(max_index), h, w, c, n, r, bpt, max_K, K.data_ptr(), ks,
-                                              idx.data_ptr() if idx.numel() else None, ist, out.data_ptr() if out.numel() else None,
-                                              out.numel(), offsets.data_ptr(), status.data_ptr() if n else None, ws.data_ptr(), ws.numel(),
-                                              torch.cuda.current_stream().cuda_stream)
-    if st == _lib.IREC_E_INVALID:
-        raise ValueError(lib.irec_last_error().decode())
-    _lib.check(st, "irec_rec_encode_files_device")
+        ws = torch.empty(max(lib.irec_rec_device_workspace_bytes(n, layout.R), 8), dtype=torch.uint8, device=dev)
+        offsets, status, both = _files.offsets_and_status(n, dev)
+        tb = () if tables is None else tables.to(dev).device_args(layout.R, who)
+        st = getattr(lib, "irec_rec_encode_files_device" + suffix)(
+            int(seed), int(block_size), int(max_index), h, w, c, n, layout.R, blocks, max_K, K.data_ptr(), ks,
+            idx.data_ptr() if idx.numel() else None, ist, *tb, out.data_ptr() if out.numel() else None, out.numel(), offsets.data_ptr(),
+            status.data_ptr() if n else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    _files.check_status(st, "irec_rec_encode_files_device" + suffix)
     return offsets, status, both
+
+
+def _decode_rows_device_launch(blob, offsets, layout, max_K, on_device, tables, who):
+    """One irec_rec_decode_files_device[_ragged|_tables] call on the current stream: (headers int32 [N, 9] holding the uint32 words,
+    K [N, T], idx [N, T, max_K], status int32 [N]) on the device.  Nothing is read back: host `offsets` are checked against the blob
+    before any kernel sees them, and with on_device those that are on the device stay there (_files.device_offsets)."""
+    import torch
+    lib = _lib.load()
+    if not (blob.is_cuda and blob.dtype == torch.uint8):
+        raise ValueError(f"{who} takes a CUDA uint8 tensor")
+    blob = blob.contiguous()
+    dev = blob.device
+    max_K = int(max_K)
+    offsets = _files.device_offsets(offsets, blob, dev, on_device, who)
+    n = offsets.numel() - 1
+    suffix, blocks = layout.entry(tables)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(lib.irec_rec_device_workspace_bytes(n, layout.R), 8), dtype=torch.uint8, device=dev)
+        hdr = torch.zeros((n, 9), dtype=torch.int32, device=dev)
+        K = torch.empty((n, layout.T), dtype=torch.int32, device=dev)
+        idx = torch.empty((n, layout.T, max_K), dtype=torch.int32, device=dev)
+        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        tb = () if tables is None else tables.to(dev).device_args(layout.R, who)
+        st = getattr(lib, "irec_rec_decode_files_device" + suffix)(
+            blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, layout.R, blocks, max_K, *tb, hdr.data_ptr(),
+            K.data_ptr(), idx.data_ptr() if idx.numel() else None, status.data_ptr(), ws.data_ptr(), ws.numel(),
+            torch.cuda.current_stream().cuda_stream)
+    _files.check_status(st, "irec_rec_decode_files_device" + suffix)
+    return hdr, K, idx, status[:n]
+
+
+def _encode_files_device_launch(seed, image_shape, block_size, K, idx, max_index, out):
+    """_encode_rows_device_launch for K [N, R, bpt], idx [N, R, bpt, max_K] (irec_rec_encode_files_device)."""
+    return _encode_rows_device_launch(seed, image_shape, block_size, *_block_rows(K, idx), max_index, _Layout(K.shape[1], K.shape[2]), out, None,
+                                      "encode_files_device")
+
+
+def _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, out, tables=None):
+    """_encode_rows_device_launch for checked rows (irec_rec_encode_files_device_ragged, or _tables with tables)."""
+    import torch
+    layout = _Layout.ragged(blocks_per_res, "encode_files_device_ragged")
+    if not (K.is_cuda and idx.is_cuda and K.dtype == torch.int32 and idx.dtype == torch.int32):
+        raise ValueError("encode_files_device_ragged takes CUDA int32 tensors")
+    if K.dim() != 2 or K.shape[1] != layout.T or idx.dim() != 3 or tuple(idx.shape[:2]) != tuple(K.shape):
+        raise ValueError(f"encode_files_device_ragged: K {tuple(K.shape)} and idx {tuple(idx.shape)} are not [N, {layout.T}] and [N, {layout.T}, max_K]")
+    return _encode_rows_device_launch(seed, image_shape, block_size, K, idx, max_index, layout, out, tables, "encode_files_device_ragged")
+
+
+def _decode_files_device_ragged_launch(blob, offsets, blocks_per_res, max_K, on_device=False, tables=None):
+    """_decode_rows_device_launch for blocks_per_res (irec_rec_decode_files_device_ragged, or _tables with tables)."""
+    layout = _Layout.ragged(blocks_per_res, "decode_files_device_ragged")
+    return _decode_rows_device_launch(blob, offsets, layout, max_K, on_device, tables, "decode_files_device_ragged")
+
+
+def _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K, on_device=False, tables=None):
+    """_decode_rows_device_launch for R residual blocks of bpt blocks (irec_rec_decode_files_device): K [N, R, bpt], idx [N, R, bpt, max_K]."""
+    r, bpt = int(n_res_blocks), int(blocks_per_res)
+    if tables is not None:                             # (the entry point with tables takes the ragged layout: R equal entries)
+        hdr, K, idx, status = _decode_files_device_ragged_launch(blob, offsets, [bpt] * r, max_K, on_device=on_device, tables=tables)
+    else:
+        hdr, K, idx, status = _decode_rows_device_launch(blob, offsets, _Layout(r, bpt), max_K, on_device, None, "decode_files_device")
+    return hdr, K.view(K.shape[0], r, bpt), idx.view(K.shape[0], r, bpt, int(max_K)), status
+
+
+def _device_out(out, first_cap, dev, who):
+    """The buffer a device writer writes into: the caller's, or a first allowance."""
+    import torch
+    if out is None:
+        return torch.empty(max(first_cap(), 1), dtype=torch.uint8, device=dev)
+    if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == dev):
+        raise ValueError(f"{who}: out must be a contiguous CUDA uint8 tensor on the indices' device")
+    return out
+
+
+def _first_cap(n, layout, max_K):
+    """irec_io.cpp's own first allowance: 64 + 40 bits per symbol and terminator, per stream."""
+    b = layout.bpr.astype(np.int64)
+    return n * (28 + 16 * layout.R + int(((64 + 40 * (b + 1)) // 8 + 1 + (64 + 40 * (b * max_K + 1)) // 8 + 1).sum()))
 
 
 def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=None, tables=None):
@@ -273,71 +462,11 @@ def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=No
     if K.dim() != 3 or idx.dim() != 4 or tuple(idx.shape[:3]) != tuple(K.shape):
         raise ValueError(f"encode_files_device: K {tuple(K.shape)} and idx {tuple(idx.shape)} are not [N, R, bpt] and [N, R, bpt, max_K]")
     n, r, bpt = K.shape
-    max_K = idx.shape[3]
     if tables is not None:                             # (R <= IREC_REC_RAGGED_MAX_RES: the entry point with tables takes the ragged layout)
-        K, ks, idx, ist = _block_strides(K, idx)
-        return encode_files_device_ragged(seed, image_shape, block_size, K.as_strided((n, r * bpt), (r * bpt * ks, ks)),
-                                          idx.as_strided((n, r * bpt, max_K), (r * bpt * ist, ist, 1)), max_index, [bpt] * r, out, tables=tables)
-    if out is None:
-        # irec_io.cpp's own first allowance: 64 + 40 bits per symbol and terminator, per stream
-        cap = n * (28 + 16 * r + r * ((64 + 40 * (bpt + 1)) // 8 + 1 + (64 + 40 * (bpt * max_K + 1)) // 8 + 1))
-        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=K.device)
-    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == K.device):
-        raise ValueError("encode_files_device: out must be a contiguous CUDA uint8 tensor on the indices' device")
-    for _attempt in range(2):
-        offsets, _, both = _encode_files_device_launch(seed, image_shape, block_size, K, idx, max_index, out)
-        host = both.cpu().numpy()
-        _raise_first_status(host[n + 1:].view(np.int32)[:n])
-        total = int(host[n])
-        if total <= out.numel():
-            return out[:total], offsets
-        out = torch.empty(total, dtype=torch.uint8, device=K.device)                       # exactly what the first run asked for
-    raise ValueError("irec_rec_encode_files_device: the files did not fit the size the call itself reported")
-
-
-def _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K, on_device=False, tables=None):
-    """One irec_rec_decode_files_device call on the current stream: (headers int32 [N, 9] holding the uint32 words, K, idx, status int32 [N])
-    on the device, nothing read back but `offsets` (checked against the blob before any kernel sees them).
-    on_device: offsets that ARE on the device stay there -- instead of the check on the host they are clamped into the blob and made
-    non-decreasing by two small device operations, so that no file's range leaves the blob whatever they hold (a range that was
-    wrong reads as a damaged file); nothing is read back and the call can be captured in a HIP graph."""
-    import torch
-    lib = _lib.load()
-    if tables is not None:                             # (the entry point with tables takes the ragged layout: R equal entries)
-        r, bpt = int(n_res_blocks), int(blocks_per_res)
-        hdr, K, idx, status = _decode_files_device_ragged_launch(blob, offsets, [bpt] * r, max_K, on_device=on_device, tables=tables)
-        return hdr, K.view(-1, r, bpt), idx.view(-1, r, bpt, int(max_K)), status
-    if not (blob.is_cuda and blob.dtype == torch.uint8):
-        raise ValueError("decode_files_device takes a CUDA uint8 tensor")
-    blob = blob.contiguous()
-    dev = blob.device
-    r, bpt, max_K = int(n_res_blocks), int(blocks_per_res), int(max_K)
-    off_dev = None
-    if on_device and hasattr(offsets, "is_cuda") and offsets.is_cuda:
-        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
-            raise ValueError("decode_files_device: device offsets must be int64 [N + 1]")
-        n = offsets.numel() - 1
-        off_dev = torch.cummax(offsets.to(dev).clamp(0, blob.numel()), dim=0).values.contiguous()
-    else:
-        off_host = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
-        n = off_host.size - 1
-        # the kernels read no byte outside [offsets[i], offsets[i + 1]): those ranges must lie inside the blob
-        if n < 0 or off_host[0] < 0 or (np.diff(off_host) < 0).any() or off_host[-1] > blob.numel():
-            raise ValueError("decode_files_device: offsets must be non-decreasing and end inside the blob")
-    with torch.cuda.device(dev):
-        offsets = off_dev if off_dev is not None else torch.from_numpy(off_host.copy()).to(dev)   # (a copy: the caller's array may be read-only)
-        ws = torch.empty(lib.irec_rec_device_workspace_bytes(n, r), dtype=torch.uint8, device=dev)
-        hdr = torch.zeros((n, 9), dtype=torch.int32, device=dev)
-        K = torch.empty((n, r, bpt), dtype=torch.int32, device=dev)
-        idx = torch.empty((n, r, bpt, max_K), dtype=torch.int32, device=dev)
-        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        st = lib.irec_rec_decode_files_device(blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, r, bpt, max_K,
-                                              hdr.data_ptr(), K.data_ptr(), idx.data_ptr() if idx.numel() else None, status.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
-    if st == _lib.IREC_E_INVALID:
-        raise ValueError(lib.irec_last_error().decode())
-    _lib.check(st, "irec_rec_decode_files_device")
-    return hdr, K, idx, status[:n]
+        return encode_files_device_ragged(seed, image_shape, block_size, *_block_rows(K, idx), max_index, [bpt] * r, out, tables=tables)
+    out = _device_out(out, lambda: _first_cap(n, _Layout(r, bpt), idx.shape[3]), K.device, "encode_files_device")
+    return _files.encode_device(lambda o: _encode_files_device_launch(seed, image_shape, block_size, K, idx, max_index, o), n, out,
+                                _rec_status_text, "irec_rec_encode_files_device")
 
 
 def decode_files_device(blob, offsets, n_res_blocks, blocks_per_res, max_K, tables=None):
@@ -345,8 +474,8 @@ def decode_files_device(blob, offsets, n_res_blocks, blocks_per_res, max_K, tabl
     Returns CUDA tensors (headers [N, 9] int64 -- seed, block_size, max_index, height, width, channels, two flags, R --,
     K [N, R, bpt] int32, idx [N, R, bpt, max_K] int32 with rows zero-filled past K); ValueError naming the first damaged file."""
     import torch
+    r, bpt = int(n_res_blocks), int(blocks_per_res)
     if tables is not None:
-        r, bpt = int(n_res_blocks), int(blocks_per_res)
         hdr, K, idx = decode_files_device_ragged(blob, offsets, [bpt] * r, max_K, tables=tables)
         return hdr, K.view(-1, r, bpt), idx.view(-1, r, bpt, int(max_K))
     hdr, K, idx, status = _decode_files_device_launch(blob, offsets, n_res_blocks, blocks_per_res, max_K)
@@ -354,227 +483,16 @@ def decode_files_device(blob, offsets, n_res_blocks, blocks_per_res, max_K, tabl
     return hdr.to(torch.int64) & 0xFFFFFFFF, K, idx
 
 
-# ---- residual blocks of differing sizes ("ragged": the two-level lossy model codes 13 blocks at level 2 and 302 at level 1) ---------------
-# K [N, T], idx [N, T, max_K], T = sum(blocks_per_res); block j of residual block r of image i is row i T + first[r] + j.
-def _ragged_layout(blocks_per_res, what):
-    bpr = np.ascontiguousarray(np.asarray(blocks_per_res, dtype=np.int64).reshape(-1))
-    if bpr.size < 1 or (bpr < 1).any() or int(bpr.sum()) > _lib.INT32_MAX:
-        raise ValueError(f"{what}: blocks_per_res must hold at least one entry, every entry >= 1, their sum an int32 (got {list(bpr)})")
-    return bpr.astype(np.int32), int(bpr.sum())
-
-
-def encode_files_ragged(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, n_threads=0, tables=None):
-    """encode_files for residual blocks of differing sizes (irec_rec_encode_files_ragged): K [N, T] int32, idx [N, T, max_K] int32,
-    T = sum(blocks_per_res).  Returns (blob uint8, offsets int64 [N + 1]); file i is byte for byte what write_compressed_code writes for
-    image i's lists."""
-    lib = _lib.load()
-    bpr, T = _ragged_layout(blocks_per_res, "encode_files_ragged")
-    K = np.ascontiguousarray(K, dtype=np.int32)
-    idx = np.ascontiguousarray(idx, dtype=np.int32)
-    if K.ndim != 2 or K.shape[1] != T or idx.ndim != 3 or idx.shape[:2] != K.shape:
-        raise ValueError(f"encode_files_ragged: K {K.shape} and idx {idx.shape} are not [N, {T}] and [N, {T}, max_K]")
-    n, max_K = K.shape[0], idx.shape[2]
-    h, w, c = (int(v) for v in image_shape)
-    offsets = np.zeros(n + 1, dtype=np.int64)
-    cap = n * (64 + 16 * bpr.size) + 2 * int(K.sum()) + 16 * K.size + 1024
-    while tables is not None:                          # (per-image statuses; the size a short buffer needs comes back with them)
-        out = np.empty(cap, dtype=np.uint8)
-        status = np.zeros(max(n, 1), dtype=np.int32)
-        total = lib.irec_rec_encode_files_tables(int(seed), int(block_size), int(max_index), h, w, c, n, bpr.size, bpr.ctypes.data, max_K,
-                                                 K.ctypes.data, idx.ctypes.data if idx.size else None,
-                                                 *tables.host_args(bpr.size, "encode_files_ragged"), out.ctypes.data, cap,
-                                                 offsets.ctypes.data, status.ctypes.data, int(n_threads))
-        if total < 0:
-            raise ValueError(lib.irec_last_error().decode())
-        _raise_first_status(status[:n])
-        if total <= cap:
-            return out[:total], offsets
-        cap = int(total)
-    while True:
-        out = np.empty(cap, dtype=np.uint8)
-        total = lib.irec_rec_encode_files_ragged(int(seed), int(block_size), int(max_index), h, w, c, n, bpr.size, bpr.ctypes.data, max_K,
-                                                 K.ctypes.data, idx.ctypes.data if idx.size else None, out.ctypes.data, cap,
-                                                 offsets.ctypes.data, int(n_threads))
-        if total < 0:
-            raise ValueError(lib.irec_io_last_error().decode())
-        if total <= cap:
-            return out[:total], offsets
-        cap = int(total)
-
-
-def decode_files_ragged(blob, offsets, blocks_per_res, max_K, n_threads=0, tables=None):
-    """The inverse of encode_files_ragged (irec_rec_decode_files_ragged): (headers [N, 9] uint32, K [N, T], idx [N, T, max_K] with rows
-    zero-filled past K); ValueError naming the first file that is damaged or of another structure."""
-    lib = _lib.load()
-    bpr, T = _ragged_layout(blocks_per_res, "decode_files_ragged")
-    blob = np.ascontiguousarray(blob, dtype=np.uint8)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    n = offsets.size - 1
-    hdr = np.zeros((n, 9), dtype=np.uint32)
-    K = np.zeros((n, T), dtype=np.int32)
-    idx = np.zeros((n, T, max(max_K, 1)), dtype=np.int32)
-    if tables is not None:
-        hdr, K, idx, status = _decode_files_tables_status(blob, offsets, bpr, max_K, tables, n_threads)
-        _raise_first_status(status)
-        return hdr, K, idx
-    st = lib.irec_rec_decode_files_ragged(blob.ctypes.data, offsets.ctypes.data, n, bpr.size, bpr.ctypes.data, int(max_K), hdr.ctypes.data,
-                                          K.ctypes.data, idx.ctypes.data, int(n_threads))
-    if st != 0:
-        raise ValueError(lib.irec_io_last_error().decode())
-    return hdr, K, idx[..., :max_K]
-
-
-def _decode_files_tables_status(blob, offsets, blocks_per_res, max_K, tables, n_threads=0):
-    """irec_rec_decode_files_tables: (headers [N, 9] uint32, K [N, T], idx [N, T, max_K], status int32 [N]) -- a verdict per file, the
-    outputs of a refused one zero."""
-    lib = _lib.load()
-    bpr, T = _ragged_layout(blocks_per_res, "decode_files_ragged")
-    blob = np.ascontiguousarray(blob, dtype=np.uint8)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    n = offsets.size - 1
-    if n < 0 or offsets[0] < 0 or (np.diff(offsets) < 0).any() or offsets[-1] > blob.size:
-        raise ValueError("decode_files_ragged: offsets must be non-decreasing and end inside the blob")
-    hdr = np.zeros((n, 9), dtype=np.uint32)
-    K = np.zeros((n, T), dtype=np.int32)
-    idx = np.zeros((n, T, int(max_K)), dtype=np.int32)
-    status = np.zeros(max(n, 1), dtype=np.int32)
-    pad = np.zeros(1, dtype=np.uint8)
-    st = lib.irec_rec_decode_files_tables(blob.ctypes.data if blob.size else pad.ctypes.data, offsets.ctypes.data, n, bpr.size,
-                                          bpr.ctypes.data, int(max_K), *tables.host_args(bpr.size, "decode_files_ragged"),
-                                          hdr.ctypes.data, K.ctypes.data, idx.ctypes.data if idx.size else None, status.ctypes.data,
-                                          int(n_threads))
-    if st != 0:
-        raise ValueError(lib.irec_last_error().decode())
-    return hdr, K, idx, status[:n]
-
-
-def _row_strides(K, idx):
-    """_block_strides for [N, T] and [N, T, max_K]: row b = i T + t at K[b k_stride], idx[b idx_stride + .]."""
-    n, T = K.shape
-    max_K = idx.shape[2]
-    ks = K.stride(1) if K.numel() else 1
-    if K.numel() and (ks < 1 or K.stride() != (T * ks, ks)):
-        K, ks = K.contiguous(), 1
-    ist = idx.stride(1) if idx.numel() else max(max_K, 1)
-    if idx.numel() and (ist < max_K or idx.stride(2) != 1 or idx.stride(0) != T * ist):
-        idx, ist = idx.contiguous(), max_K
-    return K, int(ks), idx, int(ist)
-
-
-def _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, out, tables=None):
-    """One irec_rec_encode_files_device_ragged call on the current stream, nothing read back: (offsets int64 [N + 1], status int32 [N], both
-    views of `both`, which one copy fetches).  The bytes are in `out` only if offsets[N] <= out.numel()."""
-    import torch
-    lib = _lib.load()
-    bpr, T = _ragged_layout(blocks_per_res, "encode_files_device_ragged")
-    if not (K.is_cuda and idx.is_cuda and K.dtype == torch.int32 and idx.dtype == torch.int32):
-        raise ValueError("encode_files_device_ragged takes CUDA int32 tensors")
-    if K.dim() != 2 or K.shape[1] != T or idx.dim() != 3 or tuple(idx.shape[:2]) != tuple(K.shape):
-        raise ValueError(f"encode_files_device_ragged: K {tuple(K.shape)} and idx {tuple(idx.shape)} are not [N, {T}] and [N, {T}, max_K]")
-    n, max_K = K.shape[0], idx.shape[2]
-    h, w, c = (int(v) for v in image_shape)
-    K, ks, idx, ist = _row_strides(K, idx)
-    dev = K.device
-    with torch.cuda.device(dev):
-        ws = torch.empty(max(lib.irec_rec_device_workspace_bytes(n, bpr.size), 8), dtype=torch.uint8, device=dev)
-        both = torch.empty(n + 1 + (n + 1) // 2, dtype=torch.int64, device=dev)          # offsets, then status: one read-back
-        offsets, status = both[:n + 1], both[n + 1:].view(torch.int32)[:n]
-        if tables is not None:
-            st = lib.irec_rec_encode_files_device_tables(int(seed), int(block_size), int(max_index), h, w, c, n, bpr.size, bpr.ctypes.data, max_K,
-                                                         K.data_ptr(), ks, idx.data_ptr() if idx.numel() else None, ist,
-                                                         *tables.to(dev).device_args(bpr.size, "encode_files_device_ragged"),
-                                                         out.data_ptr() if out.numel() else None, out.numel(), offsets.data_ptr(),
-                                                         status.data_ptr() if n else None, ws.data_ptr(), ws.numel(),
-                                                         torch.cuda.current_stream().cuda_stream)
-            if st == _lib.IREC_E_INVALID:
-                raise ValueError(lib.irec_last_error().decode())
-            _lib.check(st, "irec_rec_encode_files_device_tables")
-            return offsets, status, both
-        st = lib.irec_rec_encode_files_device_ragged(int(seed), int(block_size), int(max_index), h, w, c, n, bpr.size, bpr.ctypes.data, max_K,
-                                                     K.data_ptr(), ks, idx.data_ptr() if idx.numel() else None, ist,
-                                                     out.data_ptr() if out.numel() else None, out.numel(), offsets.data_ptr(),
-                                                     status.data_ptr() if n else None, ws.data_ptr(), ws.numel(),
-                                                     torch.cuda.current_stream().cuda_stream)
-    if st == _lib.IREC_E_INVALID:
-        raise ValueError(lib.irec_last_error().decode())
-    _lib.check(st, "irec_rec_encode_files_device_ragged")
-    return offsets, status, both
-
-
 def encode_files_device_ragged(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, out=None, tables=None):
     """encode_files_ragged on the device (irec_rec_encode_files_device_ragged): K [N, T], idx [N, T, max_K] int32 CUDA tensors, contiguous
     or views of one joined [rows][1 + width] tensor (PendingCode.gather_packed_ragged_device).  Returns (blob uint8, offsets int64
     [N + 1]) as CUDA tensors, byte for byte what encode_files_ragged gives; the only host synchronisation is ONE read-back of offsets
     and status.  out: a CUDA uint8 buffer to write into (a short one costs a second run at the size the first one reports)."""
-    import torch
-    bpr, T = _ragged_layout(blocks_per_res, "encode_files_device_ragged")
-    if out is None:
-        n, max_K = (K.shape[0], idx.shape[2]) if K.dim() == 2 and idx.dim() == 3 else (0, 0)
-        # irec_io.cpp's own first allowance: 64 + 40 bits per symbol and terminator, per stream
-        cap = n * (28 + 16 * bpr.size + sum((64 + 40 * (int(b) + 1)) // 8 + 1 + (64 + 40 * (int(b) * max_K + 1)) // 8 + 1 for b in bpr))
-        out = torch.empty(max(cap, 1), dtype=torch.uint8, device=K.device)
-    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.device == K.device):
-        raise ValueError("encode_files_device_ragged: out must be a contiguous CUDA uint8 tensor on the indices' device")
-    n = K.shape[0]
-    for _attempt in range(2):
-        offsets, _, both = _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, bpr, out, tables)
-        host = both.cpu().numpy()
-        _raise_first_status(host[n + 1:].view(np.int32)[:n])
-        total = int(host[n])
-        if total <= out.numel():
-            return out[:total], offsets
-        out = torch.empty(total, dtype=torch.uint8, device=K.device)                       # exactly what the first run asked for
-    raise ValueError("irec_rec_encode_files_device_ragged: the files did not fit the size the call itself reported")
-
-
-def _decode_files_device_ragged_launch(blob, offsets, blocks_per_res, max_K, on_device=False, tables=None):
-    """One irec_rec_decode_files_device_ragged call on the current stream: (headers int32 [N, 9] holding the uint32 words, K [N, T],
-    idx [N, T, max_K], status int32 [N]) on the device; `offsets` and `on_device` as _decode_files_device_launch takes them."""
-    import torch
-    lib = _lib.load()
-    bpr, T = _ragged_layout(blocks_per_res, "decode_files_device_ragged")
-    if not (blob.is_cuda and blob.dtype == torch.uint8):
-        raise ValueError("decode_files_device_ragged takes a CUDA uint8 tensor")
-    blob = blob.contiguous()
-    dev = blob.device
-    max_K = int(max_K)
-    off_dev = None
-    if on_device and hasattr(offsets, "is_cuda") and offsets.is_cuda:
-        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
-            raise ValueError("decode_files_device_ragged: device offsets must be int64 [N + 1]")
-        n = offsets.numel() - 1
-        off_dev = torch.cummax(offsets.to(dev).clamp(0, blob.numel()), dim=0).values.contiguous()
-    else:
-        off_host = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
-        n = off_host.size - 1
-        # the kernels read no byte outside [offsets[i], offsets[i + 1]): those ranges must lie inside the blob
-        if n < 0 or off_host[0] < 0 or (np.diff(off_host) < 0).any() or off_host[-1] > blob.numel():
-            raise ValueError("decode_files_device_ragged: offsets must be non-decreasing and end inside the blob")
-    with torch.cuda.device(dev):
-        offsets = off_dev if off_dev is not None else torch.from_numpy(off_host.copy()).to(dev)   # (a copy: the caller's array may be read-only)
-        ws = torch.empty(max(lib.irec_rec_device_workspace_bytes(n, bpr.size), 8), dtype=torch.uint8, device=dev)
-        hdr = torch.zeros((n, 9), dtype=torch.int32, device=dev)
-        K = torch.empty((n, T), dtype=torch.int32, device=dev)
-        idx = torch.empty((n, T, max_K), dtype=torch.int32, device=dev)
-        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        if tables is not None:
-            st = lib.irec_rec_decode_files_device_tables(blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, bpr.size,
-                                                         bpr.ctypes.data, max_K,
-                                                         *tables.to(dev).device_args(bpr.size, "decode_files_device_ragged"),
-                                                         hdr.data_ptr(), K.data_ptr(), idx.data_ptr() if idx.numel() else None,
-                                                         status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
-            if st == _lib.IREC_E_INVALID:
-                raise ValueError(lib.irec_last_error().decode())
-            _lib.check(st, "irec_rec_decode_files_device_tables")
-            return hdr, K, idx, status[:n]
-        st = lib.irec_rec_decode_files_device_ragged(blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, bpr.size,
-                                                     bpr.ctypes.data, max_K, hdr.data_ptr(), K.data_ptr(),
-                                                     idx.data_ptr() if idx.numel() else None, status.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                     torch.cuda.current_stream().cuda_stream)
-    if st == _lib.IREC_E_INVALID:
-        raise ValueError(lib.irec_last_error().decode())
-    _lib.check(st, "irec_rec_decode_files_device_ragged")
-    return hdr, K, idx, status[:n]
+    layout = _Layout.ragged(blocks_per_res, "encode_files_device_ragged")
+    n, max_K = (K.shape[0], idx.shape[2]) if K.dim() == 2 and idx.dim() == 3 else (0, 0)
+    out = _device_out(out, lambda: _first_cap(n, layout, max_K), K.device, "encode_files_device_ragged")
+    return _files.encode_device(lambda o: _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, layout, o, tables),
+                                K.shape[0], out, _rec_status_text, "irec_rec_encode_files_device_ragged")
 
 
 def decode_files_device_ragged(blob, offsets, blocks_per_res, max_K, tables=None):

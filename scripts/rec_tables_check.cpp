@@ -1,6 +1,6 @@
 // rec_tables_check.cpp -- the .rec coder's core over empirical symbol tables (csrc/irec_rec_core.h: TableModel, Tables) under the host
 // sanitizers.  A stand-alone program in the pattern of scripts/rec_core_check.cpp: every line of the core that the kernels of
-// csrc/irec_rec_tables.hip run is compiled here by g++ and runs with AddressSanitizer and UndefinedBehaviorSanitizer.  Build and run
+// csrc/irec_rec.hip run is compiled here by g++ and runs with AddressSanitizer and UndefinedBehaviorSanitizer.  Build and run
 // from the repository root:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -Irelative-entropy-coding_amd/csrc \
 //       scripts/rec_tables_check.cpp -o /tmp/rec_tables_check -lpthread && /tmp/rec_tables_check

@@ -84,6 +84,53 @@ def test_device_errors_name_the_image(engine):
         U.decode_files_device(_cuda(blob), np.array([0, blob.size + 1]), 2, 2, 2)
 
 
+def test_one_layout_through_the_uniform_and_the_ragged_entries(engine):
+    """N = 3, R = 2, bpt = 3 through irec_rec_*_files_device and, as R equal entries, through irec_rec_*_files_device_ragged; then both
+    layouts with tables (irec_rec_*_files_device_tables either way): the same bytes, offsets and statuses, which without tables are the
+    core hook's on the CPU.  Image 1 holds a K of 3 > max_K = 2: status 1 and an empty file."""
+    from irec.io import SymbolTables, utils as U
+    rng = np.random.default_rng(23)
+    n, R, bpt, mk, S = 3, 2, 3, 2, 20
+    K = rng.integers(0, mk + 1, (n, R, bpt)).astype(np.int32)
+    K[1, 1, 2] = 3
+    idx = rng.integers(0, S, (n, R, bpt, mk)).astype(np.int32)
+    meta = (5, (8, 8, 3), 10)
+    out_c, off_c, st_c = C.core_encode(*meta, K, idx, S)
+    cap = C.first_allowance(n, R, bpt, mk)
+    assert st_c.tolist() == [0, 1, 0] and 0 < off_c[1] == off_c[2] < off_c[3] <= cap
+    Kd, idxd = _cuda(K), _cuda(idx)
+    rows, uniform, ragged = (Kd.view(n, R * bpt), idxd.view(n, R * bpt, mk)), U._Layout(R, bpt), U._Layout.ragged([bpt] * R, "test")
+    for tables in (None, SymbolTables(np.arange(1, S + 2), [np.arange(1, mk + 3)] * R)):
+        got = []
+        for launch in (lambda o: U._encode_rows_device_launch(*meta, *rows, S, uniform, o, tables, "test"),
+                       lambda o: U._encode_rows_device_launch(*meta, *rows, S, ragged, o, tables, "test"),
+                       lambda o: U._encode_files_device_ragged_launch(*meta, *rows, S, [bpt] * R, o, tables)):
+            out = torch.full((cap,), 0xAB, dtype=torch.uint8, device="cuda")
+            off, st, _ = launch(out)
+            got.append((out.cpu().numpy(), off.cpu().numpy(), st.cpu().numpy()))
+        if tables is None:                                     # the public-facing uniform launch, and the core on the CPU
+            out = torch.full((cap,), 0xAB, dtype=torch.uint8, device="cuda")
+            off, st, _ = U._encode_files_device_launch(*meta, Kd, idxd, S, out)
+            got += [(out.cpu().numpy(), off.cpu().numpy(), st.cpu().numpy()), (out_c[:cap], off_c, st_c)]
+        for blob, off, st in got[1:]:
+            assert np.array_equal(blob, got[0][0]) and np.array_equal(off, got[0][1]) and np.array_equal(st, got[0][2])
+        blob, off_d, st = got[0]
+        assert st.tolist() == [0, 1, 0] and 0 < off_d[1] == off_d[2] < off_d[3] <= cap and (blob[off_d[3]:] == 0xAB).all()
+        blob_d = torch.from_numpy(blob[:off_d[3]].copy()).cuda()
+        back = [U._decode_rows_device_launch(blob_d, off_d, layout, mk, False, tables, "test") for layout in (uniform, ragged)]
+        back.append(U._decode_files_device_ragged_launch(blob_d, off_d, [bpt] * R, mk, tables=tables))
+        hdr, K3, idx4, st = U._decode_files_device_launch(blob_d, off_d, R, bpt, mk, tables=tables)
+        assert K3.shape == (n, R, bpt) and idx4.shape == (n, R, bpt, mk)
+        back.append((hdr, K3.view(n, -1), idx4.view(n, -1, mk), st))
+        for hdr, K2, idx2, st in back:
+            assert all(torch.equal(a, b) for a, b in zip((hdr, K2, idx2, st), back[0]))
+        hdr, K2, idx2, st = (t.cpu().numpy() for t in back[0])
+        assert st.tolist() == [0, 4, 0] and not hdr[1].any() and not K2[1].any() and not idx2[1].any()   # the empty file: a truncated header
+        keep = [0, 2]
+        assert np.array_equal(K2[keep], K.reshape(n, -1)[keep])
+        assert np.array_equal(idx2[keep], np.where(np.arange(mk) < K[..., None], idx, 0).reshape(n, -1, mk)[keep])
+
+
 def test_device_reader_on_damaged_files_equals_the_core(engine):
     """The damaged set as ONE call of 1746 files.  Each file goes through the core hook on the CPU first (where it agrees with the host
     reader: tests/test_rec_device_host.py); the device's statuses and accepted outputs are the hook's."""

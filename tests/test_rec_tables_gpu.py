@@ -1,4 +1,4 @@
-"""GPU tests of the .rec coder under empirical symbol tables (csrc/irec_rec_tables.hip): the device entry points against the files of
+"""GPU tests of the .rec coder under empirical symbol tables (csrc/irec_rec.hip, csrc/irec_rec_tables.hip): the device entry points against the files of
 the reference-shaped Python writer, the host entry points and the core's host hooks (tests/rec_tables_cases.py: every file the device
 sees here has been through the same lane functions on a CPU first, and every table was made by irec_rec_tables_build), two calls in
 flight on two streams, the histogram kernel against its host twin, and the two models from fitted tables to pixels.  Every comparison

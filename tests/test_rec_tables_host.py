@@ -1,5 +1,5 @@
 """CPU tests of the .rec coder under empirical symbol tables: the host-thread entry points (irec_rec_encode_files_tables /
-irec_rec_decode_files_tables) and the core's host hooks (the lane functions of csrc/irec_rec_tables.hip's kernels over host memory in a
+irec_rec_decode_files_tables) and the core's host hooks (the lane functions of csrc/irec_rec.hip's kernels over host memory in a
 plain loop) against the reference-shaped Python writer and reader (_write_compressed_code_py / _read_compressed_code_py: one
 ArithmeticCoder call per stream, which tests/golden/rec_ac_vectors.npz pins to the compiled reference on non-uniform tables), the
 table builder, hostile tables, damaged flagged files, the histograms and the fitter.  Every comparison is byte or integer equality."""
