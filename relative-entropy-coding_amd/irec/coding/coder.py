@@ -12,6 +12,7 @@ import abc
 import numpy as np
 import torch
 
+from .pending import MorePartitionsNeeded, PendingCode
 from .utils import CodingError
 from .. import _lib
 from ..engine import Engine, FitError, NormalTableTooLarge, fit_aux_ratios_host, get_engine, tf_shuffle_perm
@@ -181,8 +182,12 @@ class GaussianCoder(Coder):
             self._initialized = False
         self.last_fit_iters = None   # SGD iterations of every step of the last ratio fit (ratio = M .. 2)
         self.table_steps = 0         # steps the normal proposal tables of a device call cover; 0 = the default window
+        self.engine = None           # an `irec.Engine` of the caller's own instead of the device's default (BeamSearchCoder's `engine=`)
+        # what PendingCode's checks keep for every coder that issues device calls
         self._max_K_hint = _lib.IREC_TABLE_STEPS_DEFAULT   # index slots per block of a device call (raised when a block needs more)
-        self._K_seen, self._K_reads, self._split_strikes = 28, 0, 0   # (PendingCode's bookkeeping, shared with the beam coder)
+        self._K_seen = 28            # what covers the bulk of the K read back so far (starts at the default window; shrinks with evidence)
+        self._K_reads = 0
+        self._split_strikes = 0      # consecutive give-ups of the cooperative encoders (SplitNotResident), BeamSearchCoder._split_gave_up
         self.last_path = None        # "device" / "host": which path the sequential coder's last encode / decode call took
 
     def set_auxiliary_variance_ratios(self, ratios, average_counts=None):
@@ -300,15 +305,26 @@ class GaussianCoder(Coder):
         if type(self.sampler) is ImportanceSampler:
             self.sampler._check_alpha()
 
+    # ---- device plumbing, shared with BeamSearchCoder ---------------------------------------------------------------------------
     def _engine_for(self, tensor):
+        if self.engine is not None and self.extrapolate_auxiliary_ratios:
+            return self.engine
         t = torch.as_tensor(tensor)
         if self.extrapolate_auxiliary_ratios:
             return get_engine(t.device if t.device.type == "cuda" else None)
-        self.get_auxiliary_ratio(0)      # fitted ratios: a context of this coder's own carries them (keyed on device and table bytes)
+        # fitted ratios (extrapolate_auxiliary_ratios=False, coder.py:203-231): a context of this coder's own carries them
+        # The context is keyed on what it was built from -- the device and the ratio table's bytes: assigning
+        # aux_variable_variance_ratios directly (the analogue of the reference restoring its tf.Variables from a checkpoint) or
+        # coding a tensor that lives on another GPU builds a new one instead of coding on a stale table.
+        self.get_auxiliary_ratio(0)
+        dev = t.device if t.device.type == "cuda" else (self.engine.device if self.engine is not None else
+                                                        torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None)
+        if dev is None:
+            raise _lib.IrecLibraryError("irec needs a HIP device (MI355X / gfx950); there is no CPU fallback")
         ratios = np.ascontiguousarray(np.asarray(self.aux_variable_variance_ratios, dtype=np.float32))
-        key = (str(t.device), ratios.tobytes())
+        key = (str(torch.device(dev)), ratios.tobytes())
         if getattr(self, "_ratio_engine", None) is None or getattr(self, "_ratio_engine_key", None) != key:
-            self._ratio_engine = Engine(t.device, aux_ratios=ratios)
+            self._ratio_engine = Engine(dev, lut=getattr(self.engine, "lut", None), aux_ratios=ratios)
             self._ratio_engine_key = key
         return self._ratio_engine
 
@@ -316,10 +332,45 @@ class GaussianCoder(Coder):
     def _dev(t, device):
         return torch.as_tensor(t).detach().to(device=device, dtype=torch.float32).contiguous()
 
+    def _rows_of_lists(self, lay, indices, min_indices, n_samples, device):
+        """indices[tensor][block] (host lists) as the rows of a decode call on `device`: K [n_blocks], idx [n_blocks, max_K] int32 in
+        layout order.  min_indices: the least a row may hold (the coder's MIN_INDICES)."""
+        bpt = lay.blocks_per_tensor
+        if len(indices) != lay.n_tensors or any(len(b) != bpt for b in indices):
+            raise CodingError("indices do not match the block structure of coding_dist")
+        if any(len(ix) < min_indices for b in indices for ix in b):
+            raise CodingError("every block of the sequential coder holds at least one index" if min_indices == 1 else
+                              f"every block holds at least {min_indices} indices")
+        max_K = max(1, max((len(ix) for b in indices for ix in b), default=1))
+        if not self.extrapolate_auxiliary_ratios:
+            # decode_block asks get_auxiliary_ratio(i) for i = len(indices) - 1 .. 0 (beam_search_coder.py:129-131): an index list longer
+            # than the fitted table raises the reference's error here -- the kernels would only mark such a row "not decodable" (p.loc)
+            self.get_auxiliary_ratio(max_K - 1)
+        K = np.zeros(lay.n_blocks, dtype=np.int32)
+        idx = np.zeros((lay.n_blocks, max_K), dtype=np.int32)
+        for i in range(lay.n_tensors):
+            for j in range(bpt):
+                row, ix = lay.natural[i * bpt + j], indices[i][j]
+                K[row] = len(ix)
+                idx[row, :len(ix)] = np.asarray(ix, dtype=np.int32)
+        if idx.size and (idx.min() < 0 or idx.max() >= n_samples):
+            raise CodingError("index out of range [0, n_samples)")
+        return torch.from_numpy(K).to(device), torch.from_numpy(idx).to(device)
+
+    def _device_rows(self, p_loc, p_scale, K, idx, seed, block_size, rows, status, n_samples):
+        """The prelude of decode_tensors_device: the engine, the layout, the coding distribution and the rows as the kernels take them
+        (eng, lay, pl, ps, Kf, ks, If, ist), with the row check launched into `status` (kept in `last_rows_status`)."""
+        src = torch.as_tensor(p_loc)
+        eng = self._engine_for(src)
+        pl, ps = (self._dev(t, eng.device) for t in (p_loc, p_scale))
+        lay = eng.layout(src.shape[0], src[0].numel(), block_size, seed)
+        Kf, ks, If, ist = self._flat_rows(K, idx)
+        self.last_rows_status = self._rows_check(eng, lay, Kf, ks, If, ist, rows, status, n_samples)
+        return eng, lay, pl, ps, Kf, ks, If, ist
+
     def encode_tensors_device(self, q_loc, q_scale, p_loc, p_scale, seed, block_size, max_K=None, table_steps=None):
         """Asynchronous core of the device path: one block-KL and one encode launch for all blocks of all tensors (leading dim
         = independent latent tensors); returns a `PendingCode`, nothing is copied to the host."""
-        from .beam_search_coder import PendingCode
         self._check_alpha()
         src = torch.as_tensor(q_loc)
         shapes = {tuple(torch.as_tensor(t).shape) for t in (q_loc, q_scale, p_loc, p_scale)}
@@ -345,7 +396,6 @@ class GaussianCoder(Coder):
         """Synchronous device path.  A block with more partitions than the window is coded again with a longer one -- a bounded
         number of times; one that needs more than the tables can cover (DEVICE_MAX_K) sends the call to the host loop
         (DeviceWindowExceeded, a NormalTableTooLarge: the callers fall back as for tables that do not fit)."""
-        from .beam_search_coder import MorePartitionsNeeded
         max_K, need = None, 0
         for _ in range(self.DEVICE_ATTEMPTS):
             pending = self.encode_tensors_device(q_loc, q_scale, p_loc, p_scale, seed, block_size, max_K)
@@ -365,27 +415,10 @@ class GaussianCoder(Coder):
         eng = self._engine_for(src)
         pl, ps = (self._dev(t, eng.device) for t in (p_loc, p_scale))
         lay = eng.layout(src.shape[0], src[0].numel(), block_size, seed)
-        bpt = lay.blocks_per_tensor
-        if len(indices) != src.shape[0] or any(len(b) != bpt for b in indices):
-            raise CodingError("indices do not match the block structure of coding_dist")
-        if any(len(ix) < 1 for b in indices for ix in b):
-            raise CodingError("every block of the sequential coder holds at least one index")
-        max_K = max(len(ix) for b in indices for ix in b)
-        if not self.extrapolate_auxiliary_ratios:
-            self.get_auxiliary_ratio(max_K - 1)   # (raises the reference's text for a list longer than the fitted table)
-        K = np.zeros(lay.n_blocks, dtype=np.int32)
-        idx = np.zeros((lay.n_blocks, max_K), dtype=np.int32)
-        for i in range(src.shape[0]):
-            for j in range(bpt):
-                row, ix = lay.natural[i * bpt + j], indices[i][j]
-                K[row] = len(ix)
-                idx[row, :len(ix)] = np.asarray(ix, dtype=np.int32)
         S = self.sampler.n_samples()
-        if idx.min() < 0 or idx.max() >= S:
-            raise CodingError("index out of range [0, n_samples)")
+        K, idx = self._rows_of_lists(lay, indices, self.MIN_INDICES, S, eng.device)
         self.last_path = "device"
-        sample = eng.gc_decode_blocks(lay, pl, ps, seed, S, torch.from_numpy(K).to(eng.device), torch.from_numpy(idx).to(eng.device),
-                                      max(self.table_window(), max_K))
+        sample = eng.gc_decode_blocks(lay, pl, ps, seed, S, K, idx, max(self.table_window(), idx.shape[1]))
         return sample.reshape(src.shape).to(src.device)
 
     # ---- rows that never leave the device (the output of irec.io.decode_files_device, PendingCode.gather_packed_device) ----------
@@ -440,17 +473,11 @@ class GaussianCoder(Coder):
         if not self._on_device(p_loc, block_size):
             raise CodingError("decode_tensors_device needs the device path: an ImportanceSampler (any alpha), tensors on the GPU, "
                               "and proposal tables that fit (IREC_TABLE_BYTES_HARD, IREC_TABLE_STEPS_MAX)")
-        src = torch.as_tensor(p_loc)
-        eng = self._engine_for(src)
-        pl, ps = (self._dev(t, eng.device) for t in (p_loc, p_scale))
-        lay = eng.layout(src.shape[0], src[0].numel(), block_size, seed)
-        Kf, ks, If, ist = self._flat_rows(K, idx)
-        max_K = If.shape[1]
-        S = self.sampler.n_samples()
-        self.last_rows_status = self._rows_check(eng, lay, Kf, ks, If, ist, rows, status, S)
+        src, S = torch.as_tensor(p_loc), self.sampler.n_samples()
+        eng, lay, pl, ps, Kf, _, If, _ = self._device_rows(p_loc, p_scale, K, idx, seed, block_size, rows, status, S)
         K_lay, idx_lay = self._rows_in_layout_order(lay, Kf, If, rows)
         self.last_path = "device"
-        sample = eng.gc_decode_blocks(lay, pl, ps, seed, S, K_lay, idx_lay, max(self.table_window(), max_K))
+        sample = eng.gc_decode_blocks(lay, pl, ps, seed, S, K_lay, idx_lay, max(self.table_window(), If.shape[1]))
         return sample.reshape(src.shape).to(src.device)
 
     # the reference's loop on the host, any Sampler object.  float32 numpy, one correctly rounded operation per operator of the
@@ -580,12 +607,17 @@ class GaussianCoder(Coder):
         return [ix for ix, _ in coded], sample
 
     def decode(self, coding_dist, indices, seed, **kwargs):
-        """coder.py:459-491 (`batched=True`: as `encode`; `packed=(K, idx, rows)`, `status=`: decode_tensors_device)."""
+        """coder.py:459-491, for both coders.  Extensions: `batched=True`, as `encode`; `packed=(K, idx, rows)` (and `status=`) -- rows
+        on the device, decode_tensors_device; `indices` is then ignored."""
         batched = kwargs.pop("batched", False)
         packed, status = kwargs.pop("packed", None), kwargs.pop("status", None)
         if packed is not None:       # (K, idx, rows) on the device: decode_tensors_device, nothing crosses to the host
             return self.decode_tensors_device(coding_dist.loc, coding_dist.scale, packed[0], packed[1], seed, self.block_size,
                                               rows=packed[2], status=status)
+        return self._decode_lists(coding_dist, indices, seed, batched)
+
+    def _decode_lists(self, coding_dist, indices, seed, batched):
+        """`decode` of host lists: the kernels where `_on_device` says so, the reference's loop on the host otherwise."""
         self._check_sampler()
         loc, scale = torch.as_tensor(coding_dist.loc), torch.as_tensor(coding_dist.scale)
         if self._on_device(loc, self.block_size):

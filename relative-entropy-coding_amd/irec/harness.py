@@ -441,7 +441,7 @@ def fit_symbol_tables(model, images, seed, batch=None, max_K=None):
     batches go through the model's packed device pass, their rows are histogrammed where they lie (irec.io.hist_rows) and the counts
     are read back once.  One index table over the coder's samples, one count table per residual block over K in [0, max_K]
     (default: the largest index-slot count a batch came with, doubled: a K the fit never saw still has a symbol)."""
-    from .coding.beam_search_coder import PendingCode, MorePartitionsNeeded, SplitNotResident
+    from .coding.pending import PendingCode, recode
     n = images.shape[0]
     step = n if not batch else int(batch)
     coder = model.residual_blocks[0].coder
@@ -449,15 +449,8 @@ def fit_symbol_tables(model, images, seed, batch=None, max_K=None):
     rows = []
     with torch.no_grad():
         for lo in range(0, n, step):
-            for _attempt in range(6):
-                pendings, _ = model._compress_device(images[lo:lo + step], seed, False)
-                try:
-                    K, idx = PendingCode.gather_packed_device(pendings)
-                    break
-                except (MorePartitionsNeeded, SplitNotResident):
-                    continue
-            else:
-                raise MorePartitionsNeeded(max(b.coder._max_K_hint for b in model.residual_blocks) + 1)
+            (K, idx), _ = recode(lambda: model._compress_device(images[lo:lo + step], seed, False), PendingCode.gather_packed_device,
+                                 [b.coder for b in model.residual_blocks])
             m, R, bpt = K.shape
             rows.append((K.reshape(m, R * bpt), idx.reshape(m, R * bpt, idx.shape[3]), [bpt] * R))
     if max_K is None:

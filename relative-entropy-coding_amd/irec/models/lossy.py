@@ -14,7 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
-from ..coding.beam_search_coder import MorePartitionsNeeded, PendingCode, SplitNotResident
+from ..coding.pending import PendingCode, recode
 from ..coding.utils import CodingError
 from ..io import read_compressed_code, write_compressed_code
 from .resnet_vae import STATUS_HEADER, STATUS_ROWS, STATUS_TABLE, ModelError, _Normal, _nchw, _nhwc, deterministic_transforms, status_text
@@ -142,16 +142,9 @@ class Large2LevelVAE(nn.Module):
         """(gather(pendings), reconstruction).  The rows are read back BEFORE the synthesis transform is launched, so that what the caller
         does with them on the host (the files' arithmetic coder) runs while the device computes the reconstruction, as the list path's
         write_compressed_code does; a pass that has to be coded again has not paid for a reconstruction either."""
-        for _attempt in range(6):
-            pendings, y = self._compress_device(images, seed, sampler)
-            try:
-                gathered = gather(pendings)
-            except (MorePartitionsNeeded, SplitNotResident):
-                continue
-            with deterministic_transforms():
-                return gathered, self.synthesis_transform(_nchw(y))   # a block needs more index slots than the coder's hint (now raised), or a shared block's partners were not
-                           # resident (the coder's next call goes out unshared): code again
-        raise MorePartitionsNeeded(sampler._max_K_hint + 1)
+        gathered, y = recode(lambda: self._compress_device(images, seed, sampler), gather, [sampler])
+        with deterministic_transforms():
+            return gathered, self.synthesis_transform(_nchw(y))
 
     @torch.no_grad()
     def compress_packed(self, images, seed, sampler):

@@ -19,6 +19,7 @@ import torch.nn.functional as F
 from .. import _lib
 from ..coding import BeamSearchCoder, CodingError, GaussianCoder, ImportanceSampler
 from ..coding.beam_search_coder import MorePartitionsNeeded, PendingCode, SplitNotResident
+from ..coding.pending import recode
 
 
 class ModelError(Exception):
@@ -402,16 +403,7 @@ class BidirectionalResNetVAE(nn.Module):
         Nothing is copied to the host until the last residual block has been coded: each block's `coder.encode(...,
         defer=True)` leaves its K / index rows on the device and hands the merged sample straight to the next block's
         convolutions; ONE device-to-host copy then fetches all indices of all blocks and images."""
-        for _attempt in range(6):
-            pendings, reconstruction = self._compress_device(image, seed, update_sampler)
-            try:
-                per_block = PendingCode.gather(pendings)     # [res_block][image][coder_block]; the only host sync
-                break
-            except (MorePartitionsNeeded, SplitNotResident):
-                continue   # some block's KL needs more index slots than the coders' hint (the hints are raised), or the split
-                           # encoder's partner workgroups were not resident (every coder's next call goes out unshared): code again
-        else:
-            raise MorePartitionsNeeded(max(b.coder._max_K_hint for b in self.residual_blocks) + 1)
+        per_block, reconstruction = self._recode(image, seed, update_sampler, PendingCode.gather)   # [res_block][image][coder_block]; the only host sync
         return self._indices_structure(per_block, image.shape[0]), reconstruction
 
     @torch.no_grad()
@@ -419,14 +411,8 @@ class BidirectionalResNetVAE(nn.Module):
         """`compress` for a batch, with the indices left packed: (K [N, R, bpt], idx [N, R, bpt, max_K] int32 numpy arrays,
         reconstruction) -- what irec.io.encode_files turns into N .rec files without one Python object per index.  Needs every
         residual block to share one block layout (they do: same latent shape and block_size)."""
-        for _attempt in range(6):
-            pendings, reconstruction = self._compress_device(image, seed, update_sampler)
-            try:
-                K, idx = PendingCode.gather_packed(pendings)
-                return K, idx, reconstruction
-            except (MorePartitionsNeeded, SplitNotResident):
-                continue
-        raise MorePartitionsNeeded(max(b.coder._max_K_hint for b in self.residual_blocks) + 1)
+        (K, idx), reconstruction = self._recode(image, seed, update_sampler, PendingCode.gather_packed)
+        return K, idx, reconstruction
 
     @torch.no_grad()
     def compress_rec(self, image, seed, update_sampler=False, block_size=None, return_pendings=False, tables=None):
@@ -439,19 +425,17 @@ class BidirectionalResNetVAE(nn.Module):
         the reference's writer flags them; decompress_rec needs the same tables."""
         from ..io import encode_files_device
         _, _, height, width = image.shape
-        for _attempt in range(6):
-            pendings, reconstruction = self._compress_device(image, seed, update_sampler)
-            try:
-                K, idx = PendingCode.gather_packed_device(pendings)
-            except (MorePartitionsNeeded, SplitNotResident):
-                continue
-            coder = self.residual_blocks[0].coder
-            # the header's max_index word: the samples a step chooses among (the sequential coder's are its sampler's)
-            n_samples = coder.sampler.n_samples() if coder.sampler is not None else coder.n_samples
-            blob, offsets = encode_files_device(seed, (height, width, 3), coder.block_size if block_size is None else block_size, K, idx,
-                                                max_index=n_samples, tables=tables)
-            return ((blob, offsets, reconstruction), (K, idx)) if return_pendings else (blob, offsets, reconstruction)
-        raise MorePartitionsNeeded(max(b.coder._max_K_hint for b in self.residual_blocks) + 1)
+        (K, idx), reconstruction = self._recode(image, seed, update_sampler, PendingCode.gather_packed_device)
+        coder = self.residual_blocks[0].coder
+        # the header's max_index word: the samples a step chooses among (the sequential coder's are its sampler's)
+        n_samples = coder.sampler.n_samples() if coder.sampler is not None else coder.n_samples
+        blob, offsets = encode_files_device(seed, (height, width, 3), coder.block_size if block_size is None else block_size, K, idx,
+                                            max_index=n_samples, tables=tables)
+        return ((blob, offsets, reconstruction), (K, idx)) if return_pendings else (blob, offsets, reconstruction)
+
+    def _recode(self, image, seed, update_sampler, gather):
+        """(gather(pendings), reconstruction) of a device pass that `gather` reads back whole (irec.coding.pending.recode)."""
+        return recode(lambda: self._compress_device(image, seed, update_sampler), gather, [b.coder for b in self.residual_blocks])
 
     def _compress_device(self, image, seed, update_sampler=False):
         """Everything of `compress` that runs on the device, with no host synchronisation: (PendingCode per residual
