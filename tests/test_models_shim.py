@@ -212,6 +212,183 @@ def test_handoff_kernels_against_plain_pytorch(engine):
     assert close(out2, torch.add(inp, t, alpha=0.1))
 
 
+# ---- the hand-off kernels at the shapes and values the test above leaves out ---------------------------------------------------------------
+SHIM_VALUES = [0.0, -0.0, -1e-8, -1e-4, -20.0, -100.0, np.inf, -np.inf, np.nan]
+SHIM_LOG_SCALE_VALUES = [88.0, 89.0]          # expf is finite / overflows
+SHIM_GRID_CAP = 4096 * 256                    # shim_grid (csrc/irec_shim.hip:81): at most 4096 workgroups of 256 threads, then the loop strides
+# smallest n at s = 8, d = 20, hw = 4096 whose element count exceeds the cap: 4 * n * hw * s (four statistics), n * (d + s) * hw, n * d * hw
+SHIM_WRAP_N = {"stats": 9, "cat_elu": 10, "residual_elu": 13}
+
+
+def _plant(rng, arr, values, where=None):
+    """Plant `values` at distinct random positions of arr (where: boolean mask of the positions allowed); -> boolean mask of the plants."""
+    flat = arr.reshape(-1)
+    allowed = np.flatnonzero(np.ones(flat.size, bool) if where is None else np.broadcast_to(where, arr.shape).reshape(-1))
+    at = rng.permutation(allowed)[:len(values)]
+    flat[at] = np.asarray(values[:at.size], dtype=np.float32)
+    mask = np.zeros(flat.size, bool)
+    mask[at] = True
+    return mask.reshape(arr.shape)
+
+
+def _ref_elu(v):
+    """tf.nn.elu of float32 values: expm1 in float64, rounded once."""
+    with np.errstate(all="ignore"):
+        return np.where(v > 0, v, np.expm1(v.astype(np.float64)).astype(np.float32)).astype(np.float32)
+
+
+def _ref_exp(v):
+    with np.errstate(all="ignore"):
+        return np.exp(v.astype(np.float64)).astype(np.float32)
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a[~np.isnan(a)], b[~np.isnan(b)])
+
+
+def _shim_close(got, want, planted, what):
+    """rtol 2e-6 (the tolerance of the test above: expf / expm1f differ from the float64 function in the last places), atol 1e-7 as
+    there -- but atol 0 where a planted value went in: at x = -1e-8 an atol of 1e-7 would accept exp(x) - 1 in place of expm1(x).
+    NaN and infinities must match in kind and sign."""
+    assert got.shape == want.shape == planted.shape, what
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), (what, "NaN positions")
+    inf = np.isinf(want)
+    assert np.array_equal(got[inf], want[inf]), (what, "infinities")
+    fin = ~(nan | inf)
+    assert np.isfinite(got[fin]).all(), (what, "an infinity where the reference is finite")
+    g, w = got[fin].astype(np.float64), want[fin].astype(np.float64)
+    err, tol = np.abs(g - w), 2e-6 * np.abs(w) + np.where(planted[fin], 0.0, 1e-7)
+    rel = err / np.maximum(np.abs(w), np.finfo(np.float32).tiny)
+    print(f"{what}: {int(fin.sum())} finite, max rel err {rel.max() if rel.size else 0:.3e}, on planted {rel[planted[fin]].max() if planted[fin].any() else 0:.3e}")
+    bad = np.flatnonzero(err > tol)
+    assert not bad.size, (what, bad.size, g[bad[:5]].tolist(), w[bad[:5]].tolist())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("biased", [False, True], ids=["bias NULL", "bias set"])
+@pytest.mark.parametrize("shape", [(1, 1, 1, 1), (3, 8, 20, 255), "wrap"], ids=["1x1x1x1", "3x8x20x255", "grid-stride wrap"])
+def test_handoff_kernels_shapes_and_planted_values(engine, shape, biased):
+    """csrc/irec_shim.hip through the C ABI, operands and outputs in a canary arena (tests/guarded.py), against a float64 reference on the
+    CPU: the float32 additions are the kernels' own IEEE operations in the kernels' order (an exp of a sum that was formed in float64
+    would differ from one formed in float32 by |x| * 6e-8, more than the tolerance at x = 88), the transcendental -- expm1 for the ELU,
+    exp for the scales -- is evaluated in float64 and rounded to float32 once.  `out` of the residual kernel is one multiply-add: either
+    IEEE evaluation of it (fused or not) is accepted, bit for bit."""
+    import ctypes
+    import guarded as G
+    from irec import _lib
+    lib, F32 = engine.lib, torch.float32
+    rng = np.random.default_rng(77)
+    wrap = shape == "wrap"
+    n0, s, d, hw = (None, 8, 20, 4096) if wrap else shape
+    if wrap:
+        for per_n, n_w in ((4 * hw * s, SHIM_WRAP_N["stats"]), ((d + s) * hw, SHIM_WRAP_N["cat_elu"]), (d * hw, SHIM_WRAP_N["residual_elu"])):
+            assert (n_w - 1) * per_n <= SHIM_GRID_CAP < n_w * per_n
+    f32 = lambda *sh: rng.standard_normal(sh).astype(np.float32)
+    P = lambda t: t.data_ptr() if t is not None else None
+    stream = engine._stream()
+
+    # ---- irec_shim_stats: four statistics, and two with infer_heads = NULL
+    n = SHIM_WRAP_N["stats"] if wrap else n0
+    Cy, Ci = 4 * s + d, 2 * s + d
+    y, yi, by, bi = f32(n, Cy, hw), f32(n, Ci, hw), f32(Cy), f32(Ci)
+    log_y = np.zeros((1, Cy, 1), bool); log_y[:, s:2 * s] = True; log_y[:, 3 * s:4 * s] = True
+    log_i = np.zeros((1, Ci, 1), bool); log_i[:, s:2 * s] = True
+    my = _plant(rng, y, SHIM_VALUES) | _plant(rng, y, SHIM_LOG_SCALE_VALUES, log_y)
+    mi = _plant(rng, yi, SHIM_VALUES) | _plant(rng, yi, SHIM_LOG_SCALE_VALUES, log_i)
+    pair = my[:, 2 * s:4 * s] & (rng.random((n, 2 * s, hw)) < 0.5)          # half of y's plants meet a zero on the inference side
+    yi[:, :2 * s][pair] = 0.0
+    mi[:, :2 * s] |= pair
+    mby, mbi = _plant(rng, by, SHIM_VALUES), _plant(rng, bi, SHIM_VALUES)
+    if not biased:
+        by = bi = None
+    with np.errstate(all="ignore"):
+        vy = y + by.reshape(1, -1, 1) if biased else y.copy()
+        vi = yi + bi.reshape(1, -1, 1) if biased else yi.copy()
+    py = my | (mby.reshape(1, -1, 1) if biased else False)
+    pi = mi | (mbi.reshape(1, -1, 1) if biased else False)
+
+    def stats_ref(n_stats):
+        v, p = vy[:, :n_stats * s].copy(), py[:, :n_stats * s].copy()
+        if n_stats == 4:
+            with np.errstate(all="ignore"):
+                v[:, 2 * s:] = v[:, 2 * s:] + vi[:, :2 * s]
+            p[:, 2 * s:] |= pi[:, :2 * s]
+        v = np.ascontiguousarray(v.reshape(n, n_stats, s, hw).transpose(1, 0, 3, 2))      # [k][n][hw][c]
+        p = np.ascontiguousarray(p.reshape(n, n_stats, s, hw).transpose(1, 0, 3, 2))
+        v[1::2] = _ref_exp(v[1::2])
+        return v, p
+
+    arena = G.Arena(G.slack(8) + 4 * (y.size + yi.size + Cy + Ci + 6 * n * hw * s), "cuda")
+    dy, dyi = arena.put(y, name="y"), arena.put(yi, name="infer_heads")
+    dby, dbi = (arena.put(by, name="bias_y"), arena.put(bi, name="bias_infer")) if biased else (None, None)
+    out4 = arena.region(F32, (4, n, hw, s), "out", name="out (4 statistics)")
+    out2 = arena.region(F32, (2, n, hw, s), "out", name="out (2 statistics)")
+    arena.arm()
+    _lib.check(lib.irec_shim_stats(engine.ctx, P(dy), P(dyi), P(out4), 4, n, Cy, Ci, s, hw, P(dby), P(dbi), stream), "irec_shim_stats")
+    _lib.check(lib.irec_shim_stats(engine.ctx, P(dy), None, P(out2), 2, n, Cy, 0, s, hw, P(dby), None, stream), "irec_shim_stats (2)")
+    torch.cuda.synchronize()
+    arena.check()
+    for out, n_stats in ((out4, 4), (out2, 2)):
+        got, (want, planted) = out.cpu().numpy(), stats_ref(n_stats)
+        _shim_close(got, want, planted, f"stats x{n_stats}")
+        assert _same_bits(got[0::2], want[0::2]), n_stats                             # the locs are exact
+    del arena
+
+    # ---- irec_shim_cat_elu: slice + latent, and the slice alone
+    n = SHIM_WRAP_N["cat_elu"] if wrap else n0
+    y, by, lat = f32(n, Cy, hw), f32(Cy), f32(n, hw, s)
+    my, mby, ml = _plant(rng, y, SHIM_VALUES, np.arange(Cy).reshape(1, -1, 1) >= 4 * s), _plant(rng, by[4 * s:], SHIM_VALUES), _plant(rng, lat, SHIM_VALUES)
+    if not biased:
+        by = None
+    with np.errstate(all="ignore"):
+        v = y[:, 4 * s:] + by[4 * s:].reshape(1, -1, 1) if biased else y[:, 4 * s:].copy()
+    p = my[:, 4 * s:] | (mby.reshape(1, -1, 1) if biased else False)
+    want_cat = _ref_elu(np.concatenate([v, lat.transpose(0, 2, 1)], axis=1))
+    plant_cat = np.concatenate([np.broadcast_to(p, v.shape), ml.transpose(0, 2, 1)], axis=1)
+    arena = G.Arena(G.slack(8) + 4 * (y.size + Cy + lat.size + 2 * n * (d + s) * hw), "cuda")
+    dy, dlat = arena.put(y, name="y"), arena.put(lat, name="latent")
+    dby = arena.put(by, name="bias_y") if biased else None
+    out_cat = arena.region(F32, (n, d + s, hw), "out", name="out (cat)")
+    out_slice = arena.region(F32, (n, d, hw), "out", name="out (slice)")
+    arena.arm()
+    _lib.check(lib.irec_shim_cat_elu(engine.ctx, P(dy), P(dlat), P(out_cat), n, Cy, 4 * s, d, s, hw, P(dby), stream), "irec_shim_cat_elu")
+    _lib.check(lib.irec_shim_cat_elu(engine.ctx, P(dy), None, P(out_slice), n, Cy, 4 * s, d, 0, hw, P(dby), stream), "irec_shim_cat_elu (slice)")
+    torch.cuda.synchronize()
+    arena.check()
+    _shim_close(out_cat.cpu().numpy(), want_cat, plant_cat, "cat_elu")
+    _shim_close(out_slice.cpu().numpy(), want_cat[:, :d], plant_cat[:, :d], "cat_elu (slice)")
+    del arena
+
+    # ---- irec_shim_residual_elu
+    n = SHIM_WRAP_N["residual_elu"] if wrap else n0
+    inp, t, bt = f32(n, d, hw), f32(n, d, hw), f32(d)
+    minp, mt, mbt = _plant(rng, inp, SHIM_VALUES), _plant(rng, t, SHIM_VALUES), _plant(rng, bt, SHIM_VALUES)
+    t[minp] = 0.0                                                                     # inp's plants reach the ELU as they are (bias NULL)
+    mt |= minp
+    if not biased:
+        bt = None
+    alpha = np.float32(0.1)
+    with np.errstate(all="ignore"):
+        tv = t + bt.reshape(1, -1, 1) if biased else t.copy()
+        unfused = (inp + (alpha * tv).astype(np.float32)).astype(np.float32)
+        fused = (inp.astype(np.float64) + np.float64(alpha) * tv.astype(np.float64)).astype(np.float32)
+    planted = minp | mt | (mbt.reshape(1, -1, 1) if biased else False)
+    arena = G.Arena(G.slack(8) + 4 * (4 * inp.size + d), "cuda")
+    dinp, dt = arena.put(inp, name="input"), arena.put(t, name="tensor")
+    dbt = arena.put(bt, name="bias_tensor") if biased else None
+    out, out_elu = arena.region(F32, (n, d, hw), "out", name="out"), arena.region(F32, (n, d, hw), "out", name="out_elu")
+    arena.arm()
+    _lib.check(lib.irec_shim_residual_elu(engine.ctx, P(dinp), P(dt), float(alpha), P(out), P(out_elu), n, d, hw, P(dbt), stream), "irec_shim_residual_elu")
+    torch.cuda.synchronize()
+    arena.check()
+    got = out.cpu().numpy()
+    which = [name for name, ref in (("fused", fused), ("unfused", unfused)) if _same_bits(got, ref)]
+    print("residual_elu: out is the", which, "multiply-add;", int((fused != unfused).sum()), "elements tell them apart")
+    assert which, "out is neither IEEE evaluation of inp + alpha * t"
+    _shim_close(out_elu.cpu().numpy(), _ref_elu(got), np.broadcast_to(planted, got.shape), "residual_elu")
+
+
 @pytest.mark.gpu
 def test_graphed_compress_replays_the_whole_pass(engine):
     """The device side of compress (convolutions + 4 sequential coder launches, no host sync) captured as one HIP graph:
