@@ -438,6 +438,11 @@ static int g_wrong_ties = 0, g_wrong_nan = 0;
  * (tests/test_tie_breaking.py).  ties_to_higher: exact ties of numbers go to the HIGHER flat index; nan_first: a NaN sorts BEFORE
  * every number.  (0, 0) is the contract. */
 void irec_oracle_set_wrong_order(int ties_to_higher, int nan_first) { g_wrong_ties = ties_to_higher; g_wrong_nan = nan_first; }
+/* TEST-ONLY: a deliberately WRONG selection, for tests that must prove a call would expose a kernel that never reads one of its beam
+ * slots (tests/test_kernel_corners.py): the candidates that descend from beam slot `slot` are never selected, in every step that has
+ * the slot and enough other candidates.  -1 is the contract. */
+static int g_masked_slot = -1;
+void irec_oracle_set_masked_slot(int slot) { g_masked_slot = slot; }
 static int cand_before(float va, int32_t fa, float vb, int32_t fb) {
   int na = isnan(va), nb = isnan(vb);
   if (na || nb) { if (na != nb) return g_wrong_nan ? na : nb; return fa < fb; }
@@ -578,6 +583,8 @@ int32_t irec_oracle_encode_block_ex(int mode, float omega, int S, int B, int D, 
     int Bnew = B < N ? B : N;
     memset(taken, 0, (size_t)N);
     float s_rank0 = 0.0f, s_rank1 = 0.0f, s_rankB = 0.0f;
+    if (g_masked_slot >= 0 && g_masked_slot < Bcur && S * (Bcur - 1) >= Bnew) /* (test only: see irec_oracle_set_masked_slot) */
+      for (int s = 0; s < S; ++s) taken[s * Bcur + g_masked_slot] = 1;
     for (int j = 0; j < Bnew; ++j) {
       int best = -1;
       for (int f = 0; f < N; ++f) {

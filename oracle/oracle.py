@@ -58,6 +58,8 @@ def lib():
         L.irec_oracle_set_lut.argtypes = [f32p]
         L.irec_oracle_set_wrong_order.argtypes = [ctypes.c_int, ctypes.c_int]
         L.irec_oracle_set_wrong_order.restype = None
+        L.irec_oracle_set_masked_slot.argtypes = [ctypes.c_int]
+        L.irec_oracle_set_masked_slot.restype = None
         L.irec_oracle_py_first_randint31.argtypes = [ctypes.c_int64]
         L.irec_oracle_py_first_randint31.restype = ctypes.c_int64
         L.irec_oracle_py_randint31_nth.argtypes = [ctypes.c_int64, ctypes.c_int64]
@@ -161,6 +163,13 @@ def set_wrong_order(ties_to_higher=False, nan_first=False):
     number -- so that a test can prove its inputs would expose a kernel that does (tests/test_tie_breaking.py).  No arguments: the
     contract."""
     lib().irec_oracle_set_wrong_order(int(bool(ties_to_higher)), int(bool(nan_first)))
+
+
+def set_masked_slot(slot=None):
+    """TEST-ONLY: makes the coder functions select WRONGLY -- no candidate that descends from beam slot `slot` is ever selected -- so
+    that a test can prove its calls would expose a kernel that never reads that slot (tests/test_kernel_corners.py).  None: the
+    contract."""
+    lib().irec_oracle_set_masked_slot(-1 if slot is None else int(slot))
 
 
 def py_first_randint31(seed):

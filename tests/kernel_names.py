@@ -92,6 +92,67 @@ def rejects_by_step_two(B, S):
     return S > B or S * min(B, S) > B
 
 
+def _planner():
+    """(lib, _lib, Engine) of the product's host library: what enumerate_plans and enumerate_ranges ask."""
+    import sys
+    for p in (ROOT, os.path.join(ROOT, "relative-entropy-coding_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    from irec import _lib
+    from irec.engine import Engine
+    return _lib.load(), _lib, Engine
+
+
+def plan_name(n_cu, B, S, dim, max_K, n_blocks, flags, omega=3.0):
+    """(canonical kernel name, team slots = workgroups * teams per workgroup) of one call on a device of n_cu compute units."""
+    lib, _lib, Engine = _planner()
+    info, det = _lib.IrecPlanInfo(), _lib.IrecPlanDetail()
+    p = Engine.params(omega, S, B, flags, [dim])
+    st = lib.irec_test_plan(n_cu, 2400, ctypes.byref(p), n_blocks, dim, max_K, ctypes.byref(info), ctypes.byref(det))
+    assert st == 0, (B, S, dim, flags, n_blocks, lib.irec_last_error())
+    return canonical(info.kernel.decode(), info.split), int(det.grid) * int(det.teams_per_wg)
+
+
+# the finer dim grid of enumerate_ranges: (block dims, max_K).  1, 63 .. 65, 257, 1023 and 1024 for the builds of at most 1024 dims;
+# 1025, 2049 (a last chunk of one dim) and 5000 for the chunk builds
+RANGE_DIMS = ((1, 32), (63, 32), (64, 32), (65, 32), (192, 32), (257, 32), (1000, 32), (1023, 32), (1024, 32),
+              (1025, 64), (2048, 64), (2049, 64), (5000, 64))
+_ranges = {}
+
+
+def enumerate_ranges(n_cu=256):
+    """canonical kernel name -> every call of the grid BEAMS x SAMPLES x RANGE_DIMS x BLOCKS x flag_sets that launches it: an int64
+    array [n, 6] of rows (B, S, dim, n_blocks, flags, over), over = 1 where the call has more blocks than team slots (workgroups *
+    teams per workgroup: some team codes a second block).  About 15 s on one CPU thread; cached per n_cu."""
+    import numpy as np
+    if n_cu in _ranges:
+        return _ranges[n_cu]
+    lib, _lib, Engine = _planner()
+    info, det = _lib.IrecPlanInfo(), _lib.IrecPlanDetail()
+    rows = {}
+    for B in BEAMS:
+        for S in SAMPLES:
+            if S * B >= 1 << 24:
+                continue
+            for dim, max_K in RANGE_DIMS:
+                for flags in flag_sets(_lib):
+                    p = Engine.params(3.0, S, B, flags, [dim])
+                    for nb in BLOCKS:
+                        st = lib.irec_test_plan(n_cu, 2400, ctypes.byref(p), nb, dim, max_K, ctypes.byref(info), ctypes.byref(det))
+                        assert st == 0, (B, S, dim, flags, nb, lib.irec_last_error())
+                        rows.setdefault((info.kernel, info.split), []).append((B, S, dim, nb, flags, nb > det.grid * det.teams_per_wg))
+    out = {}
+    for (kernel, split), r in rows.items():
+        out.setdefault(canonical(kernel.decode(), split), []).extend(r)
+    _ranges[n_cu] = {name: np.array(sorted(set(r)), dtype=np.int64) for name, r in out.items()}
+    return _ranges[n_cu]
+
+
+def max_K_of(dim):
+    """The max_K the grids pair with a block dim (DIMS, RANGE_DIMS): 32 up to 1024 dims, 64 beyond."""
+    return 32 if dim <= 1024 else 64
+
+
 def enumerate_plans(n_cu=256, dims=DIMS, blocks=BLOCKS, accept=None):
     """canonical kernel name -> the cheapest call of the grid that launches it: dict(B, S, n_blocks, dim, max_K, flags, plan).
     accept(B, S): only calls of these beams and samples count (tests/test_tie_breaking.py: calls whose selection rejects a candidate)."""
@@ -120,3 +181,151 @@ def enumerate_plans(n_cu=256, dims=DIMS, blocks=BLOCKS, accept=None):
                             best[name] = dict(B=B, S=S, n_blocks=nb, dim=dim, max_K=max_K, flags=flags, cost=cost,
                                               kernel=info.kernel.decode(), split=int(info.split))
     return best
+
+
+# ---- the corner calls of a name (tests/test_kernel_corners.py) -------------------------------------------------------------------
+SEED = 42                                  # the coding seed of every corner call
+BUDGET = 4e8                               # proposal evaluations per call, at most: scripts/soak_parity.py's per-block cap
+# ... except the `blocks` corner of the names none of whose calls of more blocks than team slots fits BUDGET (one-team chunk builds: 257
+# blocks of 1025 dims or more): such a call spreads over the oracle's 16 threads at 1.5e8 evaluations a second each, 8e9 take 3.3 s
+BUDGET_BLOCKS = 8e9
+OMEGAS = (3.0, 1.0, 0.5, 0.25, 0.1, 10.0)  # the ladder a call's Omega is taken from; the last rung is for blocks of 5000 dims
+CHUNK = 1024                               # dims per chunk of encode_chunk_kernel (csrc/irec_chunk.h)
+_stats, _corners = {}, {}
+
+
+def rank_of_dim(dim):
+    """How ragged a block dim is: 2 a last wave / chunk of one dim short or one dim long (1023, 2049), 1 any other dim beyond 64 that
+    is no multiple of 64, 0 the rest."""
+    return 2 if dim in (1023, 2049) else int(dim > 64 and dim % 64 != 0)
+
+
+def corner_inputs(oracle, call, seed=None):
+    """The host arrays (mq, sq, mp, sp), each [n_blocks, dim], of a corner call.  source 'synthetic': case_inputs; 'families' (dims too
+    small for synthetic_latent to reach four partitions on the ladder): tests/latent_families.py, sharp on the even blocks, the
+    members of mixed in turn on the odd ones."""
+    import latent_families as L
+    seed = call["seed"] if seed is None else seed
+    if call["source"] == "synthetic":
+        return case_inputs(oracle, call, seed=seed)
+    dim, max_K, pools, bl = call["dim"], call["max_K"], {}, []
+    for j in range(call["n_blocks"]):
+        if j % 2 == 0:
+            bl.append(L.block("sharp", dim, 1000 * seed + j, 1.0, max_K))
+        else:
+            k = seed + j // 20
+            if k not in pools:
+                pools[k] = L.mixed(dim, k, 1.0, max_K)
+            bl.append(pools[k][(j // 2) % len(pools[k])])
+    return list(L.stack(bl))
+
+
+def call_stats(oracle, dim, n_blocks):
+    """(Omega, source, K of every block) of the calls of n_blocks blocks of dim dims, on the inputs of seed 7: the first Omega of the
+    ladder, on synthetic_latent and failing that on the families, at which no block exceeds max_K, the median K is at most 16 and at
+    least a third of the blocks have 4 <= K <= 16 (synthetic_latent's blocks of one dim lie within two partitions of each other: all
+    of them do).  Several steps of such a block run with B_cur = B."""
+    import numpy as np
+    key = (dim, n_blocks)
+    if key not in _stats:
+        perm = oracle.tf_shuffle_perm(SEED, dim)
+        found = None
+        for source in ("synthetic", "families"):
+            call = dict(dim=dim, n_blocks=n_blocks, max_K=max_K_of(dim), source=source, seed=7)
+            host = corner_inputs(oracle, call)
+            kl = [oracle.block_kl(*(a[i][perm] for a in host)) for i in range(n_blocks)]
+            for omega in OMEGAS:
+                Ks = np.array([oracle.num_aux(v, omega) for v in kl])
+                if Ks.max() <= call["max_K"] and np.median(Ks) <= 16 and 3 * int(((Ks >= 4) & (Ks <= 16)).sum()) >= n_blocks:
+                    found = (omega, source, Ks)
+                    break
+            if found:
+                break
+        assert found, f"no Omega of the ladder gives blocks of {dim} dims 4 to 16 partitions"
+        _stats[key] = found
+    return _stats[key]
+
+
+def call_cost(oracle, B, S, dim, n_blocks):
+    """sum over the blocks of S * D * (1 + (K - 1) * B): the proposal evaluations of the call (step 1 scores S candidates, every later
+    step at most S * B)."""
+    Ks = call_stats(oracle, dim, n_blocks)[2]
+    Ks = Ks[Ks >= 1]
+    return float(S) * dim * float((1 + (Ks - 1) * B).sum())
+
+
+def is_shared(name):
+    """The shared-row builds of the team encoder: the sixth template argument."""
+    m = re.match(r"encode_team_kernel<\d+,\d+,\d+,\w+,\w+,(\w+),\w+>$", name)
+    return bool(m) and m.group(1) == "true"
+
+
+def range_calls(rng):
+    """The rejecting calls of a name's range (enumerate_ranges): {(B, S, dim, n_blocks): (smallest flags, over)}, S >= 2."""
+    out = {}
+    for B, S, dim, nb, flags, over in rng.tolist():
+        if S >= 2 and rejects_by_step_two(B, S) and (B, S, dim, nb) not in out:        # (rows are sorted: the smallest flags first)
+            out[(B, S, dim, nb)] = (flags, over)
+    return out
+
+
+def corner_cases(n_cu=256):
+    """canonical kernel name -> at most 4 calls from the edges of the range the name serves (enumerate_ranges), each a dict(B, S, dim,
+    max_K, n_blocks, flags, omega, source, seed = 7, roles, cost), every one with S >= 2 and rejecting by its second step; and the corners
+    left out or beyond the budget: (dropped_S, over_budget), see tests/test_kernel_corners.py.  Every choice is `the first call, in an
+    order of preference, that fits BUDGET`:
+      full    the largest B, then the largest dim, the fewest blocks, the largest S;
+      small   the smallest B, then the smallest S, the smallest dim, the fewest blocks;
+      wide    the largest S of the range that fits at all, at the most ragged dim (rank_of_dim), then the largest B and dim;
+      blocks  shared-row builds: the other end of their block window.  Names whose range has calls of more blocks than team slots:
+              the smallest such count -- where none fits BUDGET, the first that fits BUDGET_BLOCKS (over_budget lists those names).
+              The others: their largest block count.  Then the largest B, the smallest S and dim.
+    Cached per n_cu."""
+    if n_cu in _corners:
+        return _corners[n_cu]
+    from oracle import oracle as O
+    O.lib()
+    cases, dropped_S, over_budget = {}, [], []
+    for name, rng in sorted(enumerate_ranges(n_cu).items()):
+        calls = range_calls(rng)
+        # (a third of a call's blocks have four partitions or more: calls far beyond the budget are turned down without their inputs)
+        fits = lambda c: c[1] * c[2] * (1 + 3 * c[0]) * (c[3] // 3) <= BUDGET and call_cost(O, *c) <= BUDGET
+        first = lambda cs, key: next((c for c in sorted(cs, key=key) if fits(c)), None)
+        picked = []
+
+        def take(c, role):
+            if c is None:
+                return
+            for p in picked:
+                if p[0] == c:
+                    p[1].append(role)
+                    return
+            picked.append((c, [role]))
+        take(first(calls, lambda c: (-c[0], -c[2], c[3], -c[1])), "full")
+        take(first(calls, lambda c: (c[0], c[1], c[2], c[3])), "small")
+        for S in sorted({c[1] for c in calls}, reverse=True):
+            c = first([c for c in calls if c[1] == S], lambda c: (-rank_of_dim(c[2]), -c[0], -c[2], c[3]))
+            if c is not None:
+                take(c, "wide")
+                break
+            dropped_S.append((name, S))
+        nb_min, nb_max = min(c[3] for c in calls), max(c[3] for c in calls)
+        over = [c for c in calls if calls[c][1]]
+        if is_shared(name):
+            take(first([c for c in calls if c[3] == nb_max], lambda c: (-c[0], c[1], c[2])), "blocks")
+        elif over:
+            c = first(over, lambda c: (c[3], -c[0], c[1], c[2]))
+            if c is None:
+                c = next(c for c in sorted(over, key=lambda c: (c[3], -c[0], c[1], c[2])) if call_cost(O, *c) <= BUDGET_BLOCKS)
+                over_budget.append(name)
+            take(c, "blocks")
+        elif nb_max > nb_min:
+            take(first([c for c in calls if c[3] > nb_min], lambda c: (-c[3], -c[0], c[1], c[2])), "blocks")
+        cases[name] = []
+        for (B, S, dim, nb), roles in picked:
+            omega, source, _ = call_stats(O, dim, nb)
+            cases[name].append(dict(B=B, S=S, dim=dim, max_K=max_K_of(dim), n_blocks=nb, flags=calls[(B, S, dim, nb)][0], omega=omega,
+                                    source=source, seed=7, roles=tuple(roles), cost=call_cost(O, B, S, dim, nb)))
+    _corners[n_cu] = (cases, dropped_S, over_budget)
+    return _corners[n_cu]
+

@@ -273,7 +273,8 @@ def _encode_gpu(engine, params, lay, host, max_K, margins=False):
 @pytest.mark.parametrize("name", _names())
 def test_every_planned_kernel_on_model_shaped_latents(engine, oracle, name):
     """Every kernel name the planner can launch (the cheapest call of tests/kernel_names.py's grid), on every non-benign family:
-    K, indices and sample equal to oracle.encode_tensors_omp bit for bit, and the GPU's index paths pass the referee."""
+    K, indices and sample equal to oracle.encode_tensors_omp bit for bit, and the GPU's index paths pass the referee.  The calls at the
+    edges of a name's range, with the referee on the call of the most beams that it can afford, are tests/test_kernel_corners.py's."""
     from irec import _lib
     ex = _plans()[name]
     B, S, n_blocks, dim, max_K, flags = ex["B"], ex["S"], ex["n_blocks"], ex["dim"], ex["max_K"], ex["flags"]

@@ -44,6 +44,8 @@ def _names():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", _names())
 def test_every_planned_kernel_matches_the_oracle(engine, oracle, name):
+    """Reachability, cheaply: the cheapest call of the grid behind every name.  The calls that decide something -- full beam sets, partial
+    last waves, ragged dims, more blocks than team slots -- are tests/test_kernel_corners.py's."""
     import torch
     from irec import _lib
     ex = _plans(engine.plan(engine.params(3.0, 36, 20), engine.layout(1, 192, 192, 42), 8)["n_cu"])[name]
