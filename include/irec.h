@@ -680,6 +680,33 @@ irec_status irec_res_decode_files(const uint8_t *bytes, const int64_t *offsets, 
 irec_status irec_res_model_counts(int32_t m, float scale, uint32_t *cumulative /*[257]*/);
 irec_status irec_res_symbol_counts(const uint8_t *pixels, const float *loc, float scale, int64_t n, uint32_t *count /*[n]*/);
 
+/* Distortion of a batch (csrc/irec_quality.hip over csrc/irec_quality_core.h): what PSNR and MS-SSIM are made from, for a
+ * (reconstruction) and b (original), float32 [n][c][h][w] each.  A pixel is v * mul + add, clamped to [0, max_val] where the image's
+ * clip flag is set; MS-SSIM is tf.image.ssim_multiscale of TF 2.1 with filter_size 11 and filter_sigma 1.5 (INTEGRATION.md has the
+ * definition), n_scales 1 .. 5 scales, every scale at least 11 x 11.  Outputs:
+ *   per_scale [n][c][n_scales][2]  the means over the VALID filter outputs of lum * cs and of cs, NOT clamped at 0
+ *   sse [n]                        the sum over the image's c * h * w pixels of (pixel_a - pixel_b)^2
+ * The caller finishes: psnr = 20 log10(max_val) - 10 log10(sse / (c h w)); ms_ssim = mean over channels of
+ * prod_{k < last} max(cs_k, 0)^pf_k * max(ssim_last, 0)^pf_last.
+ * The device entry follows irec_res_encode_files_device: device pointers, asynchronous on hip_stream, no allocation, synchronisation
+ * or copy inside (n_scales + 1 launches); it writes exactly per_scale and sse, and the workspace (256-byte aligned, at least
+ * irec_quality_workspace_bytes, which is 0 for a shape the entries refuse).  A result is the same bits from run to run and for an
+ * image alone or inside any batch; an image with a NaN pixel has non-finite results and changes no other image's.
+ * irec_quality_host runs the same core over host memory on n_threads threads (0 = one per core, at most 32): the same outputs
+ * whatever n_threads is.  Null pointers, n_scales outside 1 .. 5, an image below 11 x 11 at one of its scales, a max_val that is
+ * not positive: IREC_E_INVALID; a workspace smaller than sized: IREC_E_WORKSPACE; no launch either way. */
+typedef struct {
+  float mul_a, add_a, mul_b, add_b; /* pixel = v * mul + add                                   */
+  int32_t clip_a, clip_b;           /* nonzero: the pixel is clamped to [0, max_val]           */
+  float max_val, k1, k2;            /* c1 = (k1 max_val)^2, c2 = (k2 max_val)^2; TF: .01, .03  */
+} irec_quality_params;
+size_t irec_quality_workspace_bytes(int32_t n, int32_t c, int32_t h, int32_t w, int32_t n_scales);
+irec_status irec_quality_device(const float *a, const float *b, int32_t n, int32_t c, int32_t h, int32_t w, int32_t n_scales,
+                                const irec_quality_params *params, float *per_scale, float *sse, void *workspace,
+                                size_t workspace_bytes, void *hip_stream);
+irec_status irec_quality_host(const float *a, const float *b, int32_t n, int32_t c, int32_t h, int32_t w, int32_t n_scales,
+                              const irec_quality_params *params, float *per_scale, float *sse, int32_t n_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,13 @@ class IrecFitParams(ctypes.Structure):
                 ("max_iters", ctypes.c_int32)]
 
 
+class IrecQualityParams(ctypes.Structure):
+    """irec_quality_params of include/irec.h: the pixel transform of both images and the SSIM constants."""
+    _fields_ = [("mul_a", ctypes.c_float), ("add_a", ctypes.c_float), ("mul_b", ctypes.c_float), ("add_b", ctypes.c_float),
+                ("clip_a", ctypes.c_int32), ("clip_b", ctypes.c_int32), ("max_val", ctypes.c_float), ("k1", ctypes.c_float),
+                ("k2", ctypes.c_float)]
+
+
 class IrecPlanInfo(ctypes.Structure):
     """irec_plan_info of include/irec.h."""
     _fields_ = [("kernel", ctypes.c_char * 64), ("table_kernel", ctypes.c_char * 32), ("grid", ctypes.c_int32),
@@ -203,6 +210,9 @@ SIGNATURES = {
     "irec_res_decode_files": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _i32] + [ctypes.c_uint32] * 4 + [_vp, _vp, _i32]),
     "irec_res_model_counts": (ctypes.c_int, [_i32, ctypes.c_float, _vp]),
     "irec_res_symbol_counts": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _i64, _vp]),
+    "irec_quality_workspace_bytes": (ctypes.c_size_t, [_i32] * 5),
+    "irec_quality_device": (ctypes.c_int, [_vp, _vp] + [_i32] * 5 + [ctypes.POINTER(IrecQualityParams), _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_quality_host": (ctypes.c_int, [_vp, _vp] + [_i32] * 5 + [ctypes.POINTER(IrecQualityParams), _vp, _vp, _i32]),
     "irec_decode_rows_status": (ctypes.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "irec_test_rows_status_host": (ctypes.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "irec_device_uniform_int": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),

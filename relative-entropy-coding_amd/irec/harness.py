@@ -314,13 +314,38 @@ def _decompress_images(model, paths, batch, strict, lossless, tables=None):
 
 
 # ---- the two-level lossy model (irec.models.lossy.Large2LevelVAE): the same two drivers over ragged files -------------------------
-def compress_images_lossy(model, sampler, images, names, seed, block_size, out_dir, batch=None, rec_on_device=False, tables=None):
+def _gaussian_kl_per_image(posterior, prior):
+    """sum over an image's latent dims of KL(N(loc_q, scale_q) || N(loc_p, scale_p)), closed form, float64 on the device: [N]."""
+    mq, sq, mp, sp = (t.to(torch.float64) for t in (posterior.loc, posterior.scale, prior.loc, prior.scale))
+    kl = torch.log(sp / sq) + (sq * sq + (mq - mp) ** 2) / (2.0 * sp * sp) - 0.5
+    return kl.reshape(kl.shape[0], -1).sum(dim=1)
+
+
+def _lossy_quality_columns(model, chunk, reconstruction, image_range):
+    """float64 [3, m] on the device: psnr, ms_ssim of the reconstruction against the chunk (irec.metrics, the reference's convention
+    for images in image_range) and the two levels' KL in nats, from the distributions the model's last pass left.  No synchronisation."""
+    from . import metrics
+    psnr, ms_ssim, _ = metrics.quality(reconstruction, chunk, **metrics.transform_for(image_range))
+    kld = _gaussian_kl_per_image(model.level_1_posterior, model.level_1_prior) + \
+        _gaussian_kl_per_image(model.level_2_posterior, model.level_2_prior)
+    return torch.stack([psnr, ms_ssim, kld])
+
+
+def compress_images_lossy(model, sampler, images, names, seed, block_size, out_dir, batch=None, rec_on_device=False, tables=None,
+                          quality=False, image_range=(0., 1.)):
     """compress_images for Large2LevelVAE and its coder `sampler`: images [n, 3, H, W] on the model's device, in batches through
     model.compress_rec (two coder launches per batch, one read-back), one NAME.rec per image -- byte for byte the file
     model.compress(file_path, ...) writes for it -- read back and compared with the rows the files were built from.
     rec_on_device: the files are built and checked on the device (irec.io.encode_files_device_ragged / decode_files_device_ragged)
     instead of on host threads, the default.  tables: an irec.io.SymbolTables (fit_symbol_tables_lossy) the files are coded under.
-    Returns one dict per image with compress_images' keys."""
+    Returns one dict per image with compress_images' keys.
+    quality=True: every row also carries the distortion half of the reference's results row
+    (examples/lossy/compress_with_lossy_model.py:192-270) -- `psnr` and `ms_ssim` of compress_rec's reconstruction against the
+    image (irec.metrics on the device: tf.image.psnr / tf.image.ssim_multiscale of clip(reconstruction) * 255 against image * 255 for
+    images in image_range, (0, 1) as the reference has them, (-0.5, 0.5) as the shim's tests do; images of at least 161 x 161),
+    `kld`, the closed-form Gaussian KL of both levels in nats (float64 on the device), and `lossy_bpp` = kld / (h w ln 2) -- all
+    of it in ONE extra read-back per batch.  The reference's ideal_PSNR / ideal_MS_SSIM columns are left out: they come from an
+    unseeded sampling forward pass, which the compression shim does not have.  quality=False: the rows and the work are as before."""
     from .io import decode_files_device_ragged, decode_files_ragged
     os.makedirs(out_dir, exist_ok=True)
     n = images.shape[0]
@@ -332,11 +357,12 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
         m, _, h, w = chunk.shape
         t0 = time.perf_counter()
         try:
-            (blob, off, _), (K, idx, bpr) = model.compress_rec(chunk, seed, sampler, block_size=block_size, rec_on_device=rec_on_device,
-                                                               return_pendings=True, tables=tables)
+            (blob, off, reconstruction), (K, idx, bpr) = model.compress_rec(chunk, seed, sampler, block_size=block_size,
+                                                                            rec_on_device=rec_on_device, return_pendings=True, tables=tables)
         except CodingError as e:                         # compression_performance.py:375-377: log and move on
             rows += [{"name": names[lo + i], "error": str(e)} for i in range(m)]
             continue
+        columns = _lossy_quality_columns(model, chunk, reconstruction, image_range) if quality else None   # (launched; read below)
         t_compress = time.perf_counter() - t0
         t1 = time.perf_counter()
         host, off_host = (blob.cpu().numpy(), off.cpu().numpy()) if rec_on_device else (blob, off)
@@ -365,6 +391,11 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
         rows += [{"name": names[lo + i], "comp_codelength": int(sizes[i]) * 8, "comp_lossy_bpp": int(sizes[i]) * 8 / (h * w),
                   "comp_code_bpd": int(sizes[i]) * 8 / (h * w * 3), "code_nats": int(n_idx[i]) * float(np.log(S)),
                   "n_indices": int(n_idx[i]), "indices_recovered": bool(same[i]), "comp_time": t_compress / m + t_host} for i in range(m)]
+        if quality:
+            psnr, ms_ssim, kld = columns.cpu().numpy()           # the one extra read-back
+            for i, row in enumerate(rows[-m:]):
+                row.update({"psnr": float(psnr[i]), "ms_ssim": float(ms_ssim[i]), "kld": float(kld[i]),
+                            "lossy_bpp": float(kld[i]) / (h * w * float(np.log(2.0)))})
     return rows
 
 
