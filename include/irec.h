@@ -520,7 +520,10 @@ typedef enum {
   IREC_REC_E_MISMATCH = 16,         /* decode: counts or indices do not match the header (also: more values than allowed) */
   IREC_REC_E_STRUCTURE = 17,        /* decode: not n_res_blocks residual blocks of the call's blocks_per_res blocks        */
   IREC_REC_E_MAX_K = 18,            /* decode: a block with more partitions than max_K                                    */
-  IREC_REC_E_TABLE = 19             /* a symbol table whose entries cannot be coded under (the *_tables entry points only) */
+  IREC_REC_E_TABLE = 19,            /* a symbol table whose entries cannot be coded under (the *_tables entry points only) */
+  IREC_REC_E_SEG_MAGIC = 20,        /* decode, segmented: not the magic "IRSG", version 1, reserved 0                       */
+  IREC_REC_E_SEG_DIRECTORY = 21,    /* decode, segmented: header + directory + the streams it lists are not the file's length */
+  IREC_REC_E_SEG_BLOCKS = 22        /* decode, segmented: segment_blocks is 0 or not the call's                             */
 } irec_rec_status;
 size_t irec_rec_device_workspace_bytes(int32_t n_images, int32_t n_res_blocks);
 irec_status irec_rec_encode_files_device(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
@@ -602,6 +605,46 @@ irec_status irec_rec_decode_files_device_tables(const uint8_t *bytes, const int6
                                                 const uint32_t *index_cum, int32_t n_index_symbols, const uint32_t *count_cum,
                                                 const int32_t *count_first, int64_t n_count_cum, uint32_t *headers /*[n][9]*/, int32_t *K,
                                                 int32_t *idx, int32_t *status, void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Segmented files (NAME.recs): an opt-in second container for few, long streams.  The rows of every residual block
+ * are cut into segments of segment_blocks coder blocks (the last one of a residual block may be shorter); every segment is a pair of
+ * ordinary streams -- exactly what the plain container holds for those blocks alone, the count model's nav_max the segment's largest
+ * K -- and one lane, or one host thread's turn, codes one stream of one segment.  Default symbol models only.
+ *   0 "IRSG" | 4 version u16 = 1, reserved u16 = 0 | 8 the 28-byte static header of .rec, both flags 0 | 36 segment_blocks u32 |
+ *   40 R x u32 blocks | directory: for r, for s < ceil(blocks[r] / segment_blocks): max_part, count_bytes, index_bytes as u32 |
+ *   the streams in directory order, a segment's count stream before its index stream.
+ * All four take the ragged layout (blocks_per_res, a HOST array of n_res_blocks <= IREC_REC_RAGGED_MAX_RES entries; the uniform case
+ * is a constant array) and rows K [n][T], idx [n][T][max_K]; at most 2^22 segments per image.  They report per image: offsets
+ * [n_images + 1] and status [n_images] always written, a file with a nonzero status has no bytes, nothing at all is written when the
+ * files do not fit cap (offsets still say what they take); the reader zeroes headers, K and idx of an image with a nonzero status.
+ * The reader holds magic, version, flags, R, the block counts and segment_blocks against the call, wants header + directory + the
+ * listed streams to be the file's length exactly and every max_part <= max_K, and never reads outside a file's own range.
+ * The host forms run on n_threads threads over (image, segment) and give byte for byte what the device forms give; the writer
+ * returns the total, -1 for bad arguments.  The device forms follow irec_rec_encode_files_device_ragged: device pointers under the
+ * same stride conventions, asynchronous on hip_stream, no allocation, no copy; workspace of irec_rec_seg_workspace_bytes (0 for
+ * arguments the calls would refuse), 8-byte aligned.  The plain readers refuse such a file (its bytes 26..27, their R, are the high
+ * half of a width below 65536: no residual blocks). */
+size_t irec_rec_seg_workspace_bytes(int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res, int32_t segment_blocks);
+int64_t irec_rec_encode_files_segmented(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                        uint32_t channels, int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res,
+                                        int32_t segment_blocks, int32_t max_K, const int32_t *K /*[n][T]*/,
+                                        const int32_t *idx /*[n][T][max_K]*/, uint8_t *out, int64_t cap,
+                                        int64_t *offsets /*[n_images + 1]*/, int32_t *status /*[n_images]*/, int32_t n_threads);
+irec_status irec_rec_decode_files_segmented(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                            const int32_t *blocks_per_res, int32_t segment_blocks, int32_t max_K,
+                                            uint32_t *headers /*[n][9]*/, int32_t *K /*[n][T]*/, int32_t *idx /*[n][T][max_K]*/,
+                                            int32_t *status /*[n]*/, int32_t n_threads);
+irec_status irec_rec_encode_files_device_segmented(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                                   uint32_t channels, int32_t n_images, int32_t n_res_blocks,
+                                                   const int32_t *blocks_per_res /*host [n_res_blocks]*/, int32_t segment_blocks,
+                                                   int32_t max_K, const int32_t *K, int64_t k_stride, const int32_t *idx,
+                                                   int64_t idx_stride, uint8_t *out, int64_t cap, int64_t *offsets /*[n_images + 1]*/,
+                                                   int32_t *status /*[n_images]*/, void *workspace, size_t workspace_bytes,
+                                                   void *hip_stream);
+irec_status irec_rec_decode_files_device_segmented(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                                   const int32_t *blocks_per_res /*host [n_res_blocks]*/, int32_t segment_blocks,
+                                                   int32_t max_K, uint32_t *headers /*[n][9]*/, int32_t *K, int32_t *idx, int32_t *status,
+                                                   void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Histograms of packed rows, to fit tables from: K [n_images][T] and idx [n_images][T][max_K] under the stride conventions above, added
  * INTO uint64 arrays (a corpus is fed batch by batch; zero them first):
  *   index_hist [n_index_values]                  the first K indices of every row whose K lies in [0, min(max_K, n_count_values - 1)];

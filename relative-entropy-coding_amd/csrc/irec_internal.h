@@ -110,6 +110,16 @@ irec_status irec_rec_test_core_decode_files_tables(const uint8_t *bytes, const i
                                                    const int32_t *blocks_per_res, int32_t max_K, const uint32_t *index_cum, int32_t n_index_symbols,
                                                    const uint32_t *count_cum, const int32_t *count_first, int64_t n_count_cum, uint32_t *headers,
                                                    int32_t *K, int32_t *idx, int32_t *status);
+/* The same of irec_rec_encode_files_device_segmented / irec_rec_decode_files_device_segmented (csrc/irec_rec_seg.hip): the host
+ * runner of csrc/irec_rec_seg_core.h, every pointer a host pointer, one thread. */
+irec_status irec_rec_test_core_encode_files_segmented(uint32_t seed, uint32_t block_size, uint32_t max_index, uint32_t height, uint32_t width,
+                                                      uint32_t channels, int32_t n_images, int32_t n_res_blocks, const int32_t *blocks_per_res,
+                                                      int32_t segment_blocks, int32_t max_K, const int32_t *K, int64_t k_stride,
+                                                      const int32_t *idx, int64_t idx_stride, uint8_t *out, int64_t cap, int64_t *offsets,
+                                                      int32_t *status);
+irec_status irec_rec_test_core_decode_files_segmented(const uint8_t *bytes, const int64_t *offsets, int32_t n_images, int32_t n_res_blocks,
+                                                      const int32_t *blocks_per_res, int32_t segment_blocks, int32_t max_K, uint32_t *headers,
+                                                      int32_t *K, int32_t *idx, int32_t *status);
 /* irec_decode_rows_status (csrc/irec_rows_core.h) over HOST memory: the same lane function, group after group in a plain loop. */
 irec_status irec_test_rows_status_host(int64_t n_groups, int32_t blocks_per_group, const int32_t *block_row, const int32_t *K,
                                        int64_t k_stride, const int32_t *idx, int64_t idx_stride, int32_t max_K, int32_t min_K,

@@ -38,6 +38,8 @@ REC_RAGGED_MAX_RES = 64          # IREC_REC_RAGGED_MAX_RES
 IREC_REC_E_COUNT_FILES = 5       # irec_rec_status: a file that uses count tables the call did not bring
 IREC_REC_E_TABLE = 19            # irec_rec_status: a symbol table whose entries cannot be coded under
 REC_TABLE_LDS_SYMBOLS = 4096     # IREC_REC_TABLE_LDS_SYMBOLS
+IREC_REC_E_SEG_MAGIC, IREC_REC_E_SEG_DIRECTORY, IREC_REC_E_SEG_BLOCKS = 20, 21, 22   # irec_rec_status: the segmented reader's own causes
+REC_SEG_MAGIC = b"IRSG"          # the first four bytes of a segmented file (NAME.recs)
 INT32_MAX = 2 ** 31 - 1
 
 
@@ -110,7 +112,8 @@ _REC_WORKSPACE = [_vp, ctypes.c_size_t, _vp]   # workspace, workspace_bytes, hip
 
 
 def _rec_batched():
-    """irec_rec_{encode,decode}_files[_device | (hook) test_core][ | _ragged | _tables]: eighteen entries, one set of fragments."""
+    """irec_rec_{encode,decode}_files[_device | (hook) test_core][ | _ragged | _tables]: eighteen entries, one set of fragments;
+    and the seven of the segmented container."""
     rows = {}
     for suffix, blocks_per_res, tables in (("", _i32, False), ("_ragged", _vp, False), ("_tables", _vp, True)):
         tb = _REC_TABLES if tables else []
@@ -125,6 +128,16 @@ def _rec_batched():
         # the host forms: packed rows, a thread count; a status per image only under tables (the others name the file in their error)
         rows[f"irec_rec_encode_files{suffix}"] = (_i64, enc + [_vp, _vp] + tb + files[:3 + tables] + [_i32])
         rows[f"irec_rec_decode_files{suffix}"] = (ctypes.c_int, dec + outputs[:3 + tables] + [_i32])
+    # the segmented container (csrc/irec_rec_seg.hip): the ragged layout and segment_blocks, a status per image in every form
+    enc = _REC_HEADER + [_i32, _i32, _vp, _i32, _i32]                 # ..., n_images, n_res_blocks, blocks_per_res, segment_blocks, max_K
+    dec = [_vp, _vp, _i32, _i32, _vp, _i32, _i32]                     # bytes, offsets, n_images, n_res_blocks, blocks_per_res, segment_blocks, max_K
+    rows["irec_rec_encode_files_device_segmented"] = (ctypes.c_int, enc + _REC_ROWS + files + _REC_WORKSPACE)
+    rows["irec_rec_decode_files_device_segmented"] = (ctypes.c_int, dec + outputs + _REC_WORKSPACE)
+    rows["irec_rec_test_core_encode_files_segmented"] = (ctypes.c_int, enc + _REC_ROWS + files)
+    rows["irec_rec_test_core_decode_files_segmented"] = (ctypes.c_int, dec + outputs)
+    rows["irec_rec_encode_files_segmented"] = (_i64, enc + [_vp, _vp] + files + [_i32])
+    rows["irec_rec_decode_files_segmented"] = (ctypes.c_int, dec + outputs + [_i32])
+    rows["irec_rec_seg_workspace_bytes"] = (ctypes.c_size_t, [_i32, _i32, _vp, _i32])
     return rows
 
 

@@ -207,19 +207,40 @@ def compress_images(model, images, names, seed, block_size, out_dir, batch=None,
     return rows
 
 
+def _segmented_words(data):
+    """rec_header_words' dict for a segmented file's bytes, or None for bytes too short to hold the fixed part and the block counts."""
+    from .io import segmented_header_words
+    from .io.segmented import FIXED_BYTES
+    w = segmented_header_words(data)
+    if w is None or w["bpt"] is None:
+        return None
+    g, at = w["segment_blocks"], FIXED_BYTES + 4 * w["R"]
+    n_seg = min(sum(-(-b // g) for b in w["bpt"]) if g else 0, (len(data) - at) // 12)
+    w["max_partitions"] = np.frombuffer(data[at:at + 12 * n_seg], dtype="<u4")[::3].tolist() if n_seg > 0 else []
+    return w
+
+
 def rec_file_groups(datas):
     """The header grouping of decompress_images, a pure function over the files' bytes: (infos, groups).  infos[i]: the header words of
     file i (irec.io.rec_header_words: seed, image_shape, block_size, max_index, R, bpt, max_partitions), None for bytes too short to
     hold their header.  groups: {(seed, image_shape, R, bpt): [file indices, in the order given]} -- the files one decompress_rec call
     takes together; bpt is the one block count of every residual block, or the tuple of counts of a ragged file (which the device
-    reader does not take)."""
+    reader does not take).
+    A file that begins with the segmented container's magic (NAME.recs) has the words of
+    irec.io.segmented_header_words -- `segment_blocks` among them, max_partitions the max_part words of its directory -- and its bpt
+    in the key is ("segmented", segment_blocks, *counts): the two containers never share a group, and a driver that reads plain files
+    only sees a block structure it does not take."""
+    from .io import is_segmented
     infos, groups = [], {}
     for i, data in enumerate(datas):
-        w = rec_header_words(data)
+        w = _segmented_words(data) if is_segmented(data) else rec_header_words(data)
         infos.append(w)
         if w is None:
             continue
-        bpt = w["bpt"][0] if len(set(w["bpt"])) == 1 else tuple(w["bpt"])
+        if "segment_blocks" in w:
+            bpt = ("segmented", w["segment_blocks"], *w["bpt"])
+        else:
+            bpt = w["bpt"][0] if len(set(w["bpt"])) == 1 else tuple(w["bpt"])
         groups.setdefault((w["seed"], w["image_shape"], w["R"], bpt), []).append(i)
     return infos, groups
 
@@ -332,7 +353,7 @@ def _lossy_quality_columns(model, chunk, reconstruction, image_range):
 
 
 def compress_images_lossy(model, sampler, images, names, seed, block_size, out_dir, batch=None, rec_on_device=False, tables=None,
-                          quality=False, image_range=(0., 1.)):
+                          quality=False, image_range=(0., 1.), segment_blocks=None):
     """compress_images for Large2LevelVAE and its coder `sampler`: images [n, 3, H, W] on the model's device, in batches through
     model.compress_rec (two coder launches per batch, one read-back), one NAME.rec per image -- byte for byte the file
     model.compress(file_path, ...) writes for it -- read back and compared with the rows the files were built from.
@@ -345,8 +366,13 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
     images in image_range, (0, 1) as the reference has them, (-0.5, 0.5) as the shim's tests do; images of at least 161 x 161),
     `kld`, the closed-form Gaussian KL of both levels in nats (float64 on the device), and `lossy_bpp` = kld / (h w ln 2) -- all
     of it in ONE extra read-back per batch.  The reference's ideal_PSNR / ideal_MS_SSIM columns are left out: they come from an
-    unseeded sampling forward pass, which the compression shim does not have.  quality=False: the rows and the work are as before."""
-    from .io import decode_files_device_ragged, decode_files_ragged
+    unseeded sampling forward pass, which the compression shim does not have.  quality=False: the rows and the work are as before.
+    segment_blocks: None for the reference's files; g >= 1 writes NAME.recs, the segmented container (model.compress_rec has the
+    description; default symbol models only, so together with tables it is a ValueError), on host threads or on the device alike."""
+    from .io import decode_files_device_ragged, decode_files_device_segmented, decode_files_ragged, decode_files_segmented
+    if segment_blocks is not None and tables is not None:
+        raise ValueError("compress_images_lossy: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
+    extension = "rec" if segment_blocks is None else "recs"
     os.makedirs(out_dir, exist_ok=True)
     n = images.shape[0]
     batch = n if not batch else int(batch)
@@ -358,7 +384,8 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
         t0 = time.perf_counter()
         try:
             (blob, off, reconstruction), (K, idx, bpr) = model.compress_rec(chunk, seed, sampler, block_size=block_size,
-                                                                            rec_on_device=rec_on_device, return_pendings=True, tables=tables)
+                                                                            rec_on_device=rec_on_device, return_pendings=True, tables=tables,
+                                                                            segment_blocks=segment_blocks)
         except CodingError as e:                         # compression_performance.py:375-377: log and move on
             rows += [{"name": names[lo + i], "error": str(e)} for i in range(m)]
             continue
@@ -366,7 +393,7 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
         t_compress = time.perf_counter() - t0
         t1 = time.perf_counter()
         host, off_host = (blob.cpu().numpy(), off.cpu().numpy()) if rec_on_device else (blob, off)
-        paths = [os.path.join(out_dir, f"{nm}.rec") for nm in names[lo:lo + m]]
+        paths = [os.path.join(out_dir, f"{nm}.{extension}") for nm in names[lo:lo + m]]
         mv = memoryview(host)
         for i, path in enumerate(paths):
             with open(path, "wb") as fh:
@@ -377,13 +404,16 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
         blob2 = np.frombuffer(b"".join(back), dtype=np.uint8)
         want = np.array([seed, block_size, h, w, 3], dtype=np.int64)
         if rec_on_device:
-            hdr, K2, idx2 = decode_files_device_ragged(torch.from_numpy(blob2.copy()).to(blob.device), off2, bpr, idx.shape[2], tables=tables)
+            blob2 = torch.from_numpy(blob2.copy()).to(blob.device)
+            hdr, K2, idx2 = decode_files_device_ragged(blob2, off2, bpr, idx.shape[2], tables=tables) if segment_blocks is None else \
+                decode_files_device_segmented(blob2, off2, bpr, idx.shape[2], segment_blocks)
             live = torch.arange(idx.shape[2], device=idx.device)[None, None, :] < K[..., None]
             same = ((K2 == K).all(dim=1) & ((idx2 == idx) | ~live).all(dim=2).all(dim=1) &
                     (hdr[:, [0, 1, 3, 4, 5]] == torch.from_numpy(want).to(hdr.device)).all(dim=1)).cpu().numpy()
             n_idx = K.sum(dim=1).cpu().numpy()
         else:
-            hdr, K2, idx2 = decode_files_ragged(blob2, off2, bpr, idx.shape[2], tables=tables)
+            hdr, K2, idx2 = decode_files_ragged(blob2, off2, bpr, idx.shape[2], tables=tables) if segment_blocks is None else \
+                decode_files_segmented(blob2, off2, bpr, idx.shape[2], segment_blocks)
             live = np.arange(idx.shape[2])[None, None, :] < K[..., None]
             same = (K2 == K).all(axis=1) & ((idx2 == idx) | ~live).all(axis=(1, 2)) & (hdr[:, [0, 1, 3, 4, 5]].astype(np.int64) == want).all(axis=1)
             n_idx = K.sum(axis=1)
@@ -403,7 +433,9 @@ def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_
     """decompress_images for Large2LevelVAE and its coder `sampler`: .rec files -> (images, rows), the files grouped by header (seed,
     shape, block structure) and each group decoded in batches by model.decompress_rec -- on host threads, or with rec_on_device on
     the device -- with one read-back per batch, the per-image status.  images, rows and strict as decompress_images has them.
-    tables: the irec.io.SymbolTables the files were written under (files without header flags decode in the same call)."""
+    tables: the irec.io.SymbolTables the files were written under (files without header flags decode in the same call).
+    Segmented files (NAME.recs) are told from the reference's by their magic and decoded in groups of their own, under the
+    segment_blocks their headers name and the default symbol models."""
     dev = next(model.parameters()).device
     datas = []
     for path in paths:
@@ -415,7 +447,8 @@ def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_
         if w is None:
             rows[i] = {"name": os.path.basename(paths[i]), "status": 4, "error": status_text(4)}     # IREC_REC_E_TRUNCATED_HEADER
     for (seed, (h, w_, c), R, bpt), members in groups.items():
-        fits = R == 2 and c == 3 and h % 64 == 0 and w_ % 64 == 0 and h > 0 and w_ > 0 and \
+        g = infos[members[0]].get("segment_blocks")      # None: the reference's container
+        fits = R == 2 and c == 3 and h % 64 == 0 and w_ % 64 == 0 and h > 0 and w_ > 0 and g != 0 and \
             list(infos[members[0]]["bpt"]) == model.blocks_per_res((1, c, h, w_), sampler.block_size)
         step = len(members) if not batch else int(batch)
         for lo in range(0, len(members), step):
@@ -430,7 +463,7 @@ def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_
                     max_K = max(max_K, tables.max_K)
                 blob = torch.from_numpy(host.copy()).to(dev) if rec_on_device else host
                 rec, status = model.decompress_rec(blob, off, seed, (len(part), c, h, w_), sampler, max_K=max_K, strict=False,
-                                                   rec_on_device=rec_on_device, tables=tables)
+                                                   rec_on_device=rec_on_device, tables=tables if g is None else None, segment_blocks=g)
                 texts = [status_text(int(st)) if st else "" for st in status]
             else:                                                       # IREC_REC_E_STRUCTURE: not this model's block structure
                 rec, status = torch.zeros((len(part), 3, h, w_), device=dev), [17] * len(part)

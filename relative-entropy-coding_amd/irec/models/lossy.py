@@ -17,7 +17,7 @@ from .. import _lib
 from ..coding.pending import PendingCode, recode
 from ..coding.utils import CodingError
 from ..io import read_compressed_code, write_compressed_code
-from .resnet_vae import STATUS_HEADER, STATUS_ROWS, STATUS_TABLE, ModelError, _Normal, _nchw, _nhwc, deterministic_transforms, status_text
+from .resnet_vae import STATUS_HEADER, STATUS_ROWS, STATUS_TABLE, ModelError, segmented_rows, _Normal, _nchw, _nhwc, deterministic_transforms, status_text
 
 
 def _down(cin, cout, n):
@@ -154,7 +154,7 @@ class Large2LevelVAE(nn.Module):
         return K, idx, bpr, reconstruction
 
     @torch.no_grad()
-    def compress_rec(self, images, seed, sampler, block_size=None, rec_on_device=False, return_pendings=False, tables=None):
+    def compress_rec(self, images, seed, sampler, block_size=None, rec_on_device=False, return_pendings=False, tables=None, segment_blocks=None):
         """A batch to its .rec files: (blob uint8, offsets int64 [N + 1], reconstruction), image i's file blob[offsets[i]:offsets[i + 1]]
         byte for byte what `compress(file_path, ...)` writes for it.  rec_on_device=False (the default: an arithmetic coder's stream is
         serial, and Kodak-size streams are long): one packed read-back, then irec.io.encode_files_ragged on host threads; blob and
@@ -163,15 +163,25 @@ class Large2LevelVAE(nn.Module):
         block_size: the header's block-size word (default: the coder's own; 0 for a coder without one).
         return_pendings: also the rows the files were built from, ((blob, offsets, reconstruction), (K, idx, blocks_per_res)).
         tables: an irec.io.SymbolTables (harness.fit_symbol_tables_lossy) -- the streams coded under its count tables on either leg, the
-        files flagged as the reference's writer flags them; decompress_rec needs the same tables."""
-        from ..io import encode_files_device_ragged, encode_files_ragged
+        files flagged as the reference's writer flags them; decompress_rec needs the same tables.
+        segment_blocks: None for the reference's file; g >= 1 for the segmented container (NAME.recs, INTEGRATION.md §8: each level's rows
+        in segments of g coder blocks, lanes and host threads over segments -- irec.io.encode_files_segmented on host threads,
+        encode_files_device_segmented with rec_on_device), which decompress_rec reads under the same segment_blocks.  Default symbol
+        models only: together with tables it is a ValueError."""
+        from ..io import encode_files_device_ragged, encode_files_device_segmented, encode_files_ragged, encode_files_segmented
+        if segment_blocks is not None and tables is not None:
+            raise ValueError("compress_rec: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
         _, _, height, width = images.shape
         gather = PendingCode.gather_packed_ragged_device if rec_on_device else PendingCode.gather_packed_ragged
         (K, idx, bpr), reconstruction = self._compress_gather(images, seed, sampler, gather)
         if block_size is None:
             block_size = sampler.block_size if sampler.block_size is not None else 0
-        encode = encode_files_device_ragged if rec_on_device else encode_files_ragged
-        blob, offsets = encode(seed, (height, width, 3), block_size, K, idx, self._max_index(sampler), bpr, tables=tables)
+        if segment_blocks is not None:
+            encode = encode_files_device_segmented if rec_on_device else encode_files_segmented
+            blob, offsets = encode(seed, (height, width, 3), block_size, K, idx, self._max_index(sampler), bpr, segment_blocks)
+        else:
+            encode = encode_files_device_ragged if rec_on_device else encode_files_ragged
+            blob, offsets = encode(seed, (height, width, 3), block_size, K, idx, self._max_index(sampler), bpr, tables=tables)
         return ((blob, offsets, reconstruction), (K, idx, bpr)) if return_pendings else (blob, offsets, reconstruction)
 
     def _packed_rows(self, n, bpr, device):
@@ -275,7 +285,8 @@ class Large2LevelVAE(nn.Module):
         return rec_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb, tables)
 
     @torch.no_grad()
-    def decompress_rec(self, blob, offsets, seed, image_shape, sampler, max_K=None, strict=True, rec_on_device=False, tables=None):
+    def decompress_rec(self, blob, offsets, seed, image_shape, sampler, max_K=None, strict=True, rec_on_device=False, tables=None,
+                       segment_blocks=None):
         """The inverse of compress_rec: N .rec files (file i = blob[offsets[i]:offsets[i + 1]]) to reconstructions [N, 3, H, W].
         rec_on_device=False: the files are read on host threads (irec.io.decode_files_ragged; blob / offsets numpy or tensors) and the
         rows uploaded once; rec_on_device=True: blob is a CUDA tensor and the rows never leave the device
@@ -286,12 +297,21 @@ class Large2LevelVAE(nn.Module):
         (reconstruction, status int32 numpy [N]), the images with status 0 being what they would be without the others.
         max_K: index slots per block (None: the largest max_partitions word of the files' headers; with count tables, their largest K).
         tables: the irec.io.SymbolTables the files were written under; a file whose header asks for tables the call did not bring has
-        status 5 (IREC_REC_E_COUNT_FILES), one without flags decodes under the default models."""
+        status 5 (IREC_REC_E_COUNT_FILES), one without flags decodes under the default models.
+        segment_blocks: None for the reference's files; g for segmented files written with compress_rec(segment_blocks=g) (max_K None:
+        the largest max_part word of their directories).  The segmented reader's own causes (irec_rec_status 20 .. 22: magic or
+        version, directory, segment size) are STATUS_SEGMENTED + 0 .. 2 in the joined status; a plain file read as a segmented one has
+        the first of them, and a segmented file read without segment_blocks has status 5."""
         from ..io.utils import _decode_files_device_ragged_launch, rec_files_max_K
         n, _, height, width = image_shape
         bpr = self.blocks_per_res(image_shape, sampler.block_size)
         device = self._prior_base.device
-        if rec_on_device:
+        if segment_blocks is not None:
+            if tables is not None:
+                raise ValueError("decompress_rec: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
+            hdr, K, idx, rec_status = segmented_rows(blob, offsets, bpr, segment_blocks, max_K, rec_on_device, device)
+            words = hdr.to(torch.int64).bitwise_and_(0xFFFFFFFF)
+        elif rec_on_device:
             if max_K is None:
                 max_K = self._files_max_K_device(blob, offsets, tables=tables)
             hdr, K, idx, rec_status = _decode_files_device_ragged_launch(blob, offsets, bpr, int(max_K), on_device=True, tables=tables)

@@ -29,8 +29,32 @@ class ModelError(Exception):
 # the joined per-image status of decompress_rec / decompress_packed beside irec_rec_status (1 .. 18)
 STATUS_HEADER = 19      # the file's seed, height, width, channels or R differ from the call's
 STATUS_TABLE = 20       # IREC_REC_E_TABLE (19 on the wire, which STATUS_HEADER has here): a symbol table that cannot be coded under
+STATUS_SEGMENTED = 21   # + (irec_rec_status - 20): IREC_REC_E_SEG_MAGIC, _SEG_DIRECTORY, _SEG_BLOCKS (20 .. 22 on the wire) as 21 .. 23
 STATUS_ROWS = 32        # + irec_rows_status (1 K_RANGE, 2 INDEX_RANGE, 3 RATIO_TABLE)
 STATUS_RESIDUAL = 48    # + irec_res_status (decompress_lossless: the .res file of an image whose .rec file decoded)
+
+
+def segmented_rows(blob, offsets, blocks_per_res, segment_blocks, max_K, rec_on_device, device):
+    """The rows of N segmented files (NAME.recs) on `device`, for the models' decompress_rec: (headers [N, 9] int32 holding the uint32
+    words, K [N, T], idx [N, T, max_K], status int32 [N]).  rec_on_device: blob is a CUDA tensor and nothing but the directories (for
+    max_K None) is copied to the host -- irec.io's launch form of the device reader; otherwise the files are read on host threads and
+    the rows uploaded once.  The status is irec_rec_status with the segmented reader's own causes moved to STATUS_SEGMENTED + 0 .. 2."""
+    from ..io import segmented as SG
+    if rec_on_device:
+        if max_K is None:
+            max_K = SG.segmented_files_max_K_device(blob, offsets, blocks_per_res, segment_blocks)
+        hdr, K, idx, status = SG._decode_files_device_segmented_launch(blob, offsets, blocks_per_res, segment_blocks, int(max_K), on_device=True)
+    else:
+        blob_h = np.ascontiguousarray(blob.cpu().numpy() if hasattr(blob, "cpu") else blob, dtype=np.uint8)
+        off_h = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
+        if max_K is None:
+            max_K = SG.segmented_files_max_K(blob_h, off_h)
+        hdr, K, idx, status = SG._decode_files_segmented_status(blob_h, off_h, blocks_per_res, segment_blocks, int(max_K))
+        both = torch.from_numpy(np.concatenate([K[..., None], idx], axis=2)).to(device)           # one upload for the rows
+        K, idx = both[..., 0], both[..., 1:]
+        hdr, status = torch.from_numpy(hdr.view(np.int32)).to(device), torch.from_numpy(status).to(device)
+    moved = status + (STATUS_SEGMENTED - _lib.IREC_REC_E_SEG_MAGIC)
+    return hdr, K, idx, torch.where(status >= _lib.IREC_REC_E_SEG_MAGIC, moved, status)
 
 
 def status_text(status, table_length=None, requested=None):
@@ -46,6 +70,9 @@ def status_text(status, table_length=None, requested=None):
         if table_length is not None and requested is not None:
             return RATIO_TABLE_TEXT.format(table_length, requested)
         return RATIO_TABLE_TEXT.split(".")[0] + "."
+    if STATUS_SEGMENTED <= status <= STATUS_SEGMENTED + 2:
+        from ..io.segmented import seg_status_text
+        return seg_status_text(status - STATUS_SEGMENTED + _lib.IREC_REC_E_SEG_MAGIC)
     own = {STATUS_HEADER: "decompress_rec: the file's header (seed, image shape, residual blocks) differs from the arguments",
            STATUS_TABLE: _REC_STATUS_TEXT[_lib.IREC_REC_E_TABLE],
            STATUS_ROWS + _lib.IREC_ROWS_E_K_RANGE: "partition count out of range [min_K, max_K]",
@@ -415,22 +442,32 @@ class BidirectionalResNetVAE(nn.Module):
         return K, idx, reconstruction
 
     @torch.no_grad()
-    def compress_rec(self, image, seed, update_sampler=False, block_size=None, return_pendings=False, tables=None):
+    def compress_rec(self, image, seed, update_sampler=False, block_size=None, return_pendings=False, tables=None, segment_blocks=None):
         """`compress_packed` with the indices never leaving the device: (blob uint8, offsets int64 [N + 1], reconstruction), CUDA tensors
         -- image i's .rec file is blob[offsets[i]:offsets[i + 1]], byte for byte what irec.io.encode_files makes of compress_packed's
         arrays (irec.io.encode_files_device: the arithmetic coder runs on the device, one lane per stream).  Only the partition counts
         and the files' offsets are read back.  block_size: the header's block-size word (default: the coders' own).
         return_pendings: also the device K / idx views the files were built from, ((blob, offsets, reconstruction), (K, idx)).
         tables: an irec.io.SymbolTables (harness.fit_symbol_tables) -- the streams coded under its count tables, the files flagged as
-        the reference's writer flags them; decompress_rec needs the same tables."""
-        from ..io import encode_files_device
+        the reference's writer flags them; decompress_rec needs the same tables.
+        segment_blocks: None for the reference's file; g >= 1 for the segmented container (NAME.recs, INTEGRATION.md §8: every residual
+        block's rows in segments of g coder blocks, one lane per stream of a segment -- irec.io.encode_files_device_segmented), which
+        decompress_rec_segmented reads.  Default symbol models only: together with tables it is a ValueError."""
+        from ..io import encode_files_device, encode_files_device_segmented
+        from ..io.utils import _block_rows
+        if segment_blocks is not None and tables is not None:
+            raise ValueError("compress_rec: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
         _, _, height, width = image.shape
         (K, idx), reconstruction = self._recode(image, seed, update_sampler, PendingCode.gather_packed_device)
         coder = self.residual_blocks[0].coder
         # the header's max_index word: the samples a step chooses among (the sequential coder's are its sampler's)
         n_samples = coder.sampler.n_samples() if coder.sampler is not None else coder.n_samples
-        blob, offsets = encode_files_device(seed, (height, width, 3), coder.block_size if block_size is None else block_size, K, idx,
-                                            max_index=n_samples, tables=tables)
+        block_size = coder.block_size if block_size is None else block_size
+        if segment_blocks is not None:
+            blob, offsets = encode_files_device_segmented(seed, (height, width, 3), block_size, *_block_rows(K, idx), n_samples,
+                                                          [K.shape[2]] * K.shape[1], segment_blocks)
+        else:
+            blob, offsets = encode_files_device(seed, (height, width, 3), block_size, K, idx, max_index=n_samples, tables=tables)
         return ((blob, offsets, reconstruction), (K, idx)) if return_pendings else (blob, offsets, reconstruction)
 
     def _recode(self, image, seed, update_sampler, gather):
@@ -573,12 +610,16 @@ class BidirectionalResNetVAE(nn.Module):
             return reconstruction
         return reconstruction, host
 
-    def _decompress_rec_device(self, blob, offsets, seed, image_shape, max_K, tables=None):
+    def _decompress_rec_device(self, blob, offsets, seed, image_shape, max_K, tables=None, segment_blocks=None):
         """Everything of decompress_rec that runs on the device: the three launches of the .rec reader, the header check, the pass,
         the joined status.  Returns (reconstruction, status int32 [N] on the device, K).  No host synchronisation."""
         from ..io.utils import _decode_files_device_launch
         n, R, bpt = int(image_shape[0]), self.num_res_blocks, self.blocks_per_tensor(image_shape)
-        hdr, K, idx, rec_status = _decode_files_device_launch(blob, offsets, R, bpt, max_K, on_device=True, tables=tables)
+        if segment_blocks is not None:
+            hdr, K, idx, rec_status = segmented_rows(blob, offsets, [bpt] * R, segment_blocks, max_K, True, blob.device)
+            K, idx = K.view(n, R, bpt), idx.view(n, R, bpt, max_K)
+        else:
+            hdr, K, idx, rec_status = _decode_files_device_launch(blob, offsets, R, bpt, max_K, on_device=True, tables=tables)
         if tables is not None:
             rec_status = torch.where(rec_status == _lib.IREC_REC_E_TABLE, torch.full_like(rec_status, STATUS_TABLE), rec_status)
         words = hdr.to(torch.int64).bitwise_and_(0xFFFFFFFF)
@@ -607,11 +648,14 @@ class BidirectionalResNetVAE(nn.Module):
         return rec_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb, tables)
 
     @torch.no_grad()
-    def _decompress_rec_status(self, blob, offsets, seed, image_shape, max_K=None, tables=None):
+    def _decompress_rec_status(self, blob, offsets, seed, image_shape, max_K=None, tables=None, segment_blocks=None):
         """decompress_rec up to its read-back: (reconstruction, status int32 numpy [N], K on the device)."""
-        if max_K is None:
+        if max_K is None and segment_blocks is not None:
+            from ..io.segmented import segmented_files_max_K_device
+            max_K = segmented_files_max_K_device(blob, offsets, [self.blocks_per_tensor(image_shape)] * self.num_res_blocks, segment_blocks)
+        elif max_K is None:
             max_K = self.files_max_K(blob, offsets, tables)
-        reconstruction, joined, K = self._decompress_rec_device(blob, offsets, seed, image_shape, int(max_K), tables)
+        reconstruction, joined, K = self._decompress_rec_device(blob, offsets, seed, image_shape, int(max_K), tables, segment_blocks)
         return reconstruction, joined.cpu().numpy(), K
 
     @torch.no_grad()
@@ -641,6 +685,24 @@ class BidirectionalResNetVAE(nn.Module):
         call's table, or has status 5 (IREC_REC_E_COUNT_FILES) if the call brought none; a file without flags decodes under the
         default models, so one call reads both sorts.  max_K None: the largest of the headers' words and the count tables' K."""
         reconstruction, host, K = self._decompress_rec_status(blob, offsets, seed, image_shape, max_K, tables)
+        if strict:
+            self._raise_status(host, K)
+            return reconstruction
+        return reconstruction, host
+
+    @torch.no_grad()
+    def decompress_rec_segmented(self, blob, offsets, seed, image_shape, segment_blocks=None, max_K=None, strict=True):
+        """decompress_rec for segmented files (compress_rec(segment_blocks=g), NAME.recs); a method of its own because decompress_rec's
+        signature is pinned.  segment_blocks None: the word of the first file's header (a 40-byte read-back).  The segmented reader's
+        own causes (irec_rec_status 20 .. 22: magic or version, directory, segment size) are STATUS_SEGMENTED + 0 .. 2 in the joined
+        status.  max_K None: the largest max_part word of the files' directories."""
+        if segment_blocks is None:
+            from ..io.segmented import FIXED_BYTES, segment_blocks_of
+            first = int(offsets[0])
+            segment_blocks = segment_blocks_of(blob[first:first + FIXED_BYTES].cpu().numpy().tobytes())
+            if not segment_blocks:
+                raise CodingError("decompress_rec_segmented: the first file is not a segmented file (no magic, or segment_blocks 0)")
+        reconstruction, host, K = self._decompress_rec_status(blob, offsets, seed, image_shape, max_K, None, segment_blocks)
         if strict:
             self._raise_status(host, K)
             return reconstruction
