@@ -25,65 +25,128 @@ from .io import decode_files, decode_files_device, encode_files, read_compressed
 from .models.resnet_vae import STATUS_RESIDUAL, status_text
 
 
-def _host_leg(chunk_shape, names, seed, block_size, out_dir, S, K, idx, t_compress, tables=None):
-    """Write / read back / compare the .rec files of one batch from its packed read-back (compression_performance.py:350-375
-    per image): the containers are built natively for all images at once (irec_rec_encode_files, host threads), written, read
-    back, decoded together (irec_rec_decode_files) and compared as arrays."""
-    n, _, h, w = chunk_shape
-    t1 = time.perf_counter()
-    blob, off = encode_files(seed, (h, w, 3), block_size, K, idx, max_index=S, tables=tables)   # the reference passes 20 < S = 36 (SURVEY §7 quirks)
-    paths = [os.path.join(out_dir, f"{nm}.rec") for nm in names]
-    mv = memoryview(blob)
+# ---- what every leg of the drivers does: files written and read back, rows compared, one result row per image ----------------------------
+def _joined(datas):
+    """N files' bytes as (blob uint8, offsets int64 [N + 1])."""
+    sizes = np.array([len(d) for d in datas], dtype=np.int64)
+    return np.frombuffer(b"".join(datas), dtype=np.uint8), np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
+def _upload(host, dev):
+    return torch.from_numpy(host.copy()).to(dev)              # (a copy: bytes objects are read-only)
+
+
+def _write_and_read_back(out_dir, names, ext, blob, offsets):
+    """File i = blob[offsets[i]:offsets[i + 1]] (numpy, or device tensors: one copy each) written as NAME.ext and all of them read back:
+    (back_blob uint8 numpy, off2 int64 [N + 1], sizes int64 [N])."""
+    host, off = (blob.cpu().numpy(), offsets.cpu().numpy()) if hasattr(blob, "cpu") else (blob, offsets)
+    paths = [os.path.join(out_dir, f"{nm}.{ext}") for nm in names]
+    mv = memoryview(host)
     for i, path in enumerate(paths):
         with open(path, "wb") as fh:
             fh.write(mv[off[i]:off[i + 1]])
-    back = [open(path, "rb").read() for path in paths]
-    sizes = np.array([len(b) for b in back], dtype=np.int64)
-    off2 = np.concatenate([[0], np.cumsum(sizes)])
-    hdr, K2, idx2 = decode_files(np.frombuffer(b"".join(back), dtype=np.uint8), off2, K.shape[1], K.shape[2], idx.shape[3], tables=tables)
-    live = np.arange(idx.shape[3])[None, None, None, :] < K[..., None]
-    same = (K2 == K).all(axis=(1, 2)) & ((idx2 == idx) | ~live).all(axis=(1, 2, 3)) & \
-        (hdr[:, [0, 1, 3, 4, 5]] == np.array([seed, block_size, h, w, 3], dtype=np.uint32)).all(axis=1)
-    n_idx = K.sum(axis=(1, 2))
+    datas = []
+    for path in paths:
+        with open(path, "rb") as fh:
+            datas.append(fh.read())
+    back, off2 = _joined(datas)
+    return back, off2, np.diff(off2)
+
+
+def _rows_match(hdr, K2, idx2, K, idx, want_words):
+    """bool [N]: the files of a batch decoded to what they were built from -- K2 [N, T] equals K, idx2 [N, T, max_K] equals idx in the
+    K live slots of every row (what lies past them does not count) and the header words seed, block_size, height, width, channels
+    equal want_words.  numpy arrays give a numpy array, torch tensors a tensor on their device (nothing is read back here)."""
+    if isinstance(K, np.ndarray):
+        slots, want = np.arange(idx.shape[2]), np.asarray(want_words, dtype=np.int64)
+    else:
+        slots, want = torch.arange(idx.shape[2], device=idx.device), torch.tensor(want_words, dtype=torch.int64, device=hdr.device)
+    live = slots[None, None, :] < K[..., None]
+    return (K2 == K).all(1) & ((idx2 == idx) | ~live).all(2).all(1) & (hdr[:, [0, 1, 3, 4, 5]] == want).all(1)
+
+
+def _rec_row(name, size_bytes, h, w, n_idx, S, recovered, comp_time):
+    """The result row of one image (reference CSV columns where they apply) from its file's size and its index count."""
+    bits = int(size_bytes) * 8
+    return {"name": name, "comp_codelength": bits, "comp_lossy_bpp": bits / (h * w), "comp_code_bpd": bits / (h * w * 3),
+            "code_nats": int(n_idx) * float(np.log(S)), "n_indices": int(n_idx), "indices_recovered": bool(recovered), "comp_time": comp_time}
+
+
+def _in_batches(n, batch, names, fn):
+    """[fn(lo, hi) for the batches of n images in order]; a batch the coder refuses (CodingError) is the error rows of its images
+    instead (compression_performance.py:375-377: log and move on).  What fn returns is the caller's: rows, or a future of rows."""
+    out = []
+    for lo in range(0, n, batch):
+        hi = min(lo + batch, n)
+        try:
+            out.append(fn(lo, hi))
+        except CodingError as e:
+            out.append([{"name": names[i], "error": str(e)} for i in range(lo, hi)])
+    return out
+
+
+def _check_leg(out_dir, names, ext, blob, offsets, K, idx, decode, want_words, S, t_compress, t1):
+    """The file half of a batch (compression_performance.py:350-375 per image): the files blob / offsets written, read back, decoded
+    together by decode(back_blob, off2) -> (headers, K2, idx2) and compared with the rows K [N, T], idx [N, T, max_K] they were built
+    from (or both as [N, R, bpt], [N, R, bpt, max_K]) -- numpy rows on the host, device rows on the device (the bytes uploaded once,
+    the verdicts and the index counts read back once each).  t1: when this half began.  One _rec_row per image."""
+    n, (_, _, h, w, _) = len(names), want_words
+    back, off2, sizes = _write_and_read_back(out_dir, names, ext, blob, offsets)
+    on_device = not isinstance(K, np.ndarray)
+    hdr, K2, idx2 = decode(_upload(back, K.device) if on_device else back, off2)
+    same, n_idx = _rows_match(hdr, *_as_rows(K2, idx2), *_as_rows(K, idx), want_words), K.reshape(n, -1).sum(1)
+    if on_device:
+        same, n_idx = same.cpu().numpy(), n_idx.cpu().numpy()
     t_host = (time.perf_counter() - t1) / n
-    return [{"name": names[i], "comp_codelength": int(sizes[i]) * 8, "comp_lossy_bpp": int(sizes[i]) * 8 / (h * w),
-             "comp_code_bpd": int(sizes[i]) * 8 / (h * w * 3), "code_nats": int(n_idx[i]) * float(np.log(S)),
-             "n_indices": int(n_idx[i]), "indices_recovered": bool(same[i]), "comp_time": t_compress / n + t_host}
-            for i in range(n)]
+    return [_rec_row(names[i], sizes[i], h, w, n_idx[i], S, same[i], t_compress / n + t_host) for i in range(n)]
+
+
+def _as_rows(K, idx):
+    """K [N, R, bpt], idx [N, R, bpt, max_K] as the rows [N, R bpt], [N, R bpt, max_K] they are (rows stay as they are)."""
+    K = K.reshape(K.shape[0], -1)
+    return K, idx.reshape(*K.shape, idx.shape[-1])
+
+
+def _host_leg(chunk_shape, names, seed, block_size, out_dir, S, K, idx, t_compress, tables=None):
+    """_check_leg for one batch's packed read-back: the containers are built natively for all images at once (irec_rec_encode_files,
+    host threads), and decoded together (irec_rec_decode_files)."""
+    _, _, h, w = chunk_shape
+    t1 = time.perf_counter()
+    blob, off = encode_files(seed, (h, w, 3), block_size, K, idx, max_index=S, tables=tables)   # the reference passes 20 < S = 36 (SURVEY §7 quirks)
+    decode = lambda b, o: decode_files(b, o, K.shape[1], K.shape[2], idx.shape[3], tables=tables)  # noqa: E731
+    return _check_leg(out_dir, names, "rec", blob, off, K, idx, decode, (seed, block_size, h, w, 3), S, t_compress, t1)
 
 
 def _device_leg(model, chunk, names, seed, block_size, out_dir, S, tables=None):
     """_host_leg with the files built and checked on the device: the batch's files come from model.compress_rec (the arithmetic coder
     runs on the device), are written, read back, decoded on the device (irec_rec_decode_files_device) and compared there with the
     indices that compress_rec's coders left.  The rows carry the same keys."""
+    _, _, h, w = chunk.shape
+    t0 = time.perf_counter()
+    (blob, off, _), (K, idx) = model.compress_rec(chunk, seed=seed, update_sampler=False, block_size=block_size, return_pendings=True,
+                                                  tables=tables)   # K, idx: views of the joined device tensor the files were built from
+    t_compress, t1 = time.perf_counter() - t0, time.perf_counter()
+    decode = lambda b, o: decode_files_device(b, o, K.shape[1], K.shape[2], idx.shape[3], tables=tables)  # noqa: E731
+    return _check_leg(out_dir, names, "rec", blob, off, K, idx, decode, (seed, block_size, h, w, 3), S, t_compress, t1)
+
+
+def _lists_leg(model, chunk, names, seed, block_size, out_dir, S):
+    """The per-image form: model.compress's nested lists through the reference's write_compressed_code / read_compressed_code."""
     n, _, h, w = chunk.shape
     t0 = time.perf_counter()
-    (blob, off, _), pendings = model.compress_rec(chunk, seed=seed, update_sampler=False, block_size=block_size, return_pendings=True,
-                                                  tables=tables)
+    block_indices, _ = model.compress(chunk, seed=seed, update_sampler=False)
     t_compress = time.perf_counter() - t0
-    t1 = time.perf_counter()
-    K, idx = pendings                                             # views of the joined device tensor the files were built from
-    host, off_host = blob.cpu().numpy(), off.cpu().numpy()
-    paths = [os.path.join(out_dir, f"{nm}.rec") for nm in names]
-    mv = memoryview(host)
-    for i, path in enumerate(paths):
-        with open(path, "wb") as fh:
-            fh.write(mv[off_host[i]:off_host[i + 1]])
-    back = [open(path, "rb").read() for path in paths]
-    sizes = np.array([len(b) for b in back], dtype=np.int64)
-    off2 = np.concatenate([[0], np.cumsum(sizes)])
-    blob2 = torch.from_numpy(np.frombuffer(b"".join(back), dtype=np.uint8).copy()).to(blob.device)
-    hdr, K2, idx2 = decode_files_device(blob2, off2, K.shape[1], K.shape[2], idx.shape[3], tables=tables)
-    live = torch.arange(idx.shape[3], device=idx.device)[None, None, None, :] < K[..., None]
-    want = torch.tensor([seed, block_size, h, w, 3], dtype=torch.int64, device=hdr.device)
-    same = ((K2 == K).all(dim=2).all(dim=1) & ((idx2 == idx) | ~live).all(dim=3).all(dim=2).all(dim=1) &
-            (hdr[:, [0, 1, 3, 4, 5]] == want).all(dim=1)).cpu().numpy()
-    n_idx = K.sum(dim=(1, 2)).cpu().numpy()
-    t_host = (time.perf_counter() - t1) / n
-    return [{"name": names[i], "comp_codelength": int(sizes[i]) * 8, "comp_lossy_bpp": int(sizes[i]) * 8 / (h * w),
-             "comp_code_bpd": int(sizes[i]) * 8 / (h * w * 3), "code_nats": int(n_idx[i]) * float(np.log(S)),
-             "n_indices": int(n_idx[i]), "indices_recovered": bool(same[i]), "comp_time": t_compress / n + t_host}
-            for i in range(n)]
+    rows = []
+    for name, bi in zip(names, [block_indices] if n == 1 else block_indices):
+        t1 = time.perf_counter()
+        path = os.path.join(out_dir, f"{name}.rec")
+        write_compressed_code(file_path=path, seed=seed, image_shape=(h, w, 3), block_size=block_size,
+                              block_indices=bi, max_index=S)       # the reference passes 20 < S = 36 (SURVEY §7 quirks)
+        size = os.path.getsize(path)
+        s, shape, bs, bi_ = read_compressed_code(file_path=path)
+        ok = (s, tuple(shape), bs) == (seed, (h, w, 3), block_size) and bi_ == bi
+        rows.append(_rec_row(name, size, h, w, sum(len(ix) for blk in bi for ix in blk), S, ok, t_compress / n + (time.perf_counter() - t1)))
+    return rows
 
 
 def _lossless_leg(model, chunk, names, seed, block_size, out_dir, S, stream_len):
@@ -97,32 +160,21 @@ def _lossless_leg(model, chunk, names, seed, block_size, out_dir, S, stream_len)
     t0 = time.perf_counter()
     (blob, off, res_blob, res_off, rec), (K, _) = model.compress_lossless(chunk, seed=seed, stream_len=stream_len, block_size=block_size,
                                                                            return_pendings=True)
-    t_compress = time.perf_counter() - t0
-    t1 = time.perf_counter()
-    backs = []
-    for ext, b, o in ((".rec", blob, off), (".res", res_blob, res_off)):
-        mv, oh = memoryview(b.cpu().numpy()), o.cpu().numpy()
-        paths = [os.path.join(out_dir, f"{nm}{ext}") for nm in names]
-        for i, path in enumerate(paths):
-            with open(path, "wb") as fh:
-                fh.write(mv[oh[i]:oh[i + 1]])
-        backs.append([open(path, "rb").read() for path in paths])
-    sizes = [np.array([len(b) for b in back], dtype=np.int64) for back in backs]
-    offs = [np.concatenate([[0], np.cumsum(sz)]) for sz in sizes]
-    blobs = [torch.from_numpy(np.frombuffer(b"".join(back), dtype=np.uint8).copy()).to(chunk.device) for back in backs]
-    pixels, status = model.decompress_lossless(blobs[0], offs[0], blobs[1], offs[1], seed, tuple(chunk.shape), max_K=max(int(K.max()), 1),
-                                               strict=False, stream_len=stream_len)
+    t_compress, t1 = time.perf_counter() - t0, time.perf_counter()
+    back, off2, sizes = _write_and_read_back(out_dir, names, "rec", blob, off)
+    res_back, res_off2, res_sizes = _write_and_read_back(out_dir, names, "res", res_blob, res_off)
+    pixels, status = model.decompress_lossless(_upload(back, chunk.device), off2, _upload(res_back, chunk.device), res_off2, seed, tuple(chunk.shape),
+                                               max_K=max(int(K.max()), 1), strict=False, stream_len=stream_len)
     same = ((pixels == chunk).reshape(n, -1).all(dim=1)).cpu().numpy() & (status == 0)
     ideal = residual_model_bits(chunk, rec, model.likelihood_scale())
     n_idx = K.sum(dim=(1, 2)).cpu().numpy()
     t_host = (time.perf_counter() - t1) / n
     rows = []
     for i in range(n):
-        rec_bits, res_bits = int(sizes[0][i]) * 8, int(sizes[1][i]) * 8
-        rows.append({"name": names[i], "comp_codelength": rec_bits, "comp_lossy_bpp": rec_bits / (h * w), "comp_code_bpd": rec_bits / (h * w * 3),
-                     "code_nats": int(n_idx[i]) * float(np.log(S)), "n_indices": int(n_idx[i]), "indices_recovered": bool(status[i] == 0 or status[i] > STATUS_RESIDUAL),
-                     "comp_residual": res_bits, "comp_lossless_bpp": (rec_bits + res_bits) / (h * w), "comp_bpd": (rec_bits + res_bits) / (h * w * 3),
-                     "residual_model_bits": float(ideal[i]), "pixels_recovered": bool(same[i]), "comp_time": t_compress / n + t_host})
+        total = (int(sizes[i]) + int(res_sizes[i])) * 8
+        rows.append(_rec_row(names[i], sizes[i], h, w, n_idx[i], S, status[i] == 0 or status[i] > STATUS_RESIDUAL, t_compress / n + t_host))
+        rows[-1].update({"comp_residual": int(res_sizes[i]) * 8, "comp_lossless_bpp": total / (h * w), "comp_bpd": total / (h * w * 3),
+                         "residual_model_bits": float(ideal[i]), "pixels_recovered": bool(same[i])})
     return rows
 
 
@@ -146,65 +198,23 @@ def compress_images(model, images, names, seed, block_size, out_dir, batch=None,
     n = images.shape[0]
     batch = n if not batch else int(batch)
     S = model.residual_blocks[0].coder.n_samples
-    rows = []
     if lossless:
-        for lo in range(0, n, batch):
-            chunk = images[lo:lo + batch]
-            try:
-                rows += _lossless_leg(model, chunk, names[lo:lo + chunk.shape[0]], seed, block_size, out_dir, S, stream_len)
-            except CodingError as e:                     # compression_performance.py:375-377: log and move on
-                rows += [{"name": names[lo + i], "error": str(e)} for i in range(chunk.shape[0])]
-        return rows
-    if rec_on_device:
-        for lo in range(0, n, batch):
-            chunk = images[lo:lo + batch]
-            try:
-                rows += _device_leg(model, chunk, names[lo:lo + chunk.shape[0]], seed, block_size, out_dir, S, tables)
-            except CodingError as e:                     # compression_performance.py:375-377: log and move on
-                rows += [{"name": names[lo + i], "error": str(e)} for i in range(chunk.shape[0])]
-        return rows
-    if packed and hasattr(model, "compress_packed"):
+        leg = lambda lo, hi: _lossless_leg(model, images[lo:hi], names[lo:hi], seed, block_size, out_dir, S, stream_len)  # noqa: E731
+    elif rec_on_device:
+        leg = lambda lo, hi: _device_leg(model, images[lo:hi], names[lo:hi], seed, block_size, out_dir, S, tables)  # noqa: E731
+    elif packed and hasattr(model, "compress_packed"):
         from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=1) as pool:
-            jobs = []
-            for lo in range(0, n, batch):
-                chunk = images[lo:lo + batch]
+        with ThreadPoolExecutor(max_workers=1) as pool:         # the host leg of a batch runs while the device codes the next one
+
+            def leg(lo, hi):
                 t0 = time.perf_counter()
-                try:
-                    K, idx, _ = model.compress_packed(chunk, seed=seed, update_sampler=False)
-                except CodingError as e:                 # compression_performance.py:375-377: log and move on
-                    jobs.append([{"name": names[lo + i], "error": str(e)} for i in range(chunk.shape[0])])
-                    continue
-                jobs.append(pool.submit(_host_leg, tuple(chunk.shape), names[lo:lo + chunk.shape[0]], seed, block_size, out_dir,
-                                        S, K, idx, time.perf_counter() - t0, tables))
-            for j in jobs:
-                rows += j if isinstance(j, list) else j.result()
-        return rows
-    for lo in range(0, n, batch):
-        chunk = images[lo:lo + batch]
-        t0 = time.perf_counter()
-        try:
-            block_indices, _ = model.compress(chunk, seed=seed, update_sampler=False)
-        except CodingError as e:                     # compression_performance.py:375-377: log and move on
-            rows += [{"name": names[lo + i], "error": str(e)} for i in range(chunk.shape[0])]
-            continue
-        t_compress = time.perf_counter() - t0
-        per_image = [block_indices] if chunk.shape[0] == 1 else block_indices
-        for i, bi in enumerate(per_image):
-            t1 = time.perf_counter()
-            _, _, h, w = chunk.shape
-            path = os.path.join(out_dir, f"{names[lo + i]}.rec")
-            write_compressed_code(file_path=path, seed=seed, image_shape=(h, w, 3), block_size=block_size,
-                                  block_indices=bi, max_index=S)       # the reference passes 20 < S = 36
-            bits = os.path.getsize(path) * 8
-            s, shape, bs, bi_ = read_compressed_code(file_path=path)
-            ok = (s, tuple(shape), bs) == (seed, (h, w, 3), block_size) and bi_ == bi
-            n_idx = sum(len(ix) for blk in bi for ix in blk)
-            rows.append({"name": names[lo + i], "comp_codelength": bits, "comp_lossy_bpp": bits / (h * w),
-                         "comp_code_bpd": bits / (h * w * 3), "code_nats": n_idx * float(np.log(S)), "n_indices": n_idx,
-                         "indices_recovered": bool(ok),
-                         "comp_time": t_compress / chunk.shape[0] + (time.perf_counter() - t1)})
-    return rows
+                K, idx, _ = model.compress_packed(images[lo:hi], seed=seed, update_sampler=False)
+                return pool.submit(_host_leg, tuple(images[lo:hi].shape), names[lo:hi], seed, block_size, out_dir, S, K, idx,
+                                   time.perf_counter() - t0, tables)
+            return [row for job in _in_batches(n, batch, names, leg) for row in (job if isinstance(job, list) else job.result())]
+    else:
+        leg = lambda lo, hi: _lists_leg(model, images[lo:hi], names[lo:hi], seed, block_size, out_dir, S)  # noqa: E731
+    return [row for rows in _in_batches(n, batch, names, leg) for row in rows]
 
 
 def _segmented_words(data):
@@ -245,24 +255,14 @@ def rec_file_groups(datas):
     return infos, groups
 
 
-def decompress_images(model, paths, batch=None, strict=True):
-    """The read side of compress_images (_decompress_images has the description)."""
-    return _decompress_images(model, paths, batch, strict, False)
+def _read(path, missing=None):
+    if missing is not None and not os.path.exists(path):
+        return missing
+    with open(path, "rb") as fh:
+        return fh.read()
 
 
-def decompress_images_tables(model, paths, tables, batch=None, strict=True):
-    """decompress_images for files written under an irec.io.SymbolTables (compress_images(tables=)); files without header flags decode
-    in the same call.  A function of its own: decompress_images' signature is pinned."""
-    return _decompress_images(model, paths, batch, strict, False, tables)
-
-
-def decompress_images_lossless(model, paths, batch=None, strict=True):
-    """The read side of compress_images(lossless=True): decompress_images over NAME.rec + NAME.res pairs (`paths` names the .rec
-    files), the images being the uint8 pixels.  A function of its own: decompress_images' signature is pinned."""
-    return _decompress_images(model, paths, batch, strict, True)
-
-
-def _decompress_images(model, paths, batch, strict, lossless, tables=None):
+def _decompress_groups(model, paths, batch, strict, fits, decode, tables=None, res=False):
     """The read side of compress_images: .rec files -> (images, rows).  The files are read and their headers parsed on the host
     (RecHeader over the 28 + 16 R header bytes), files of equal (seed, shape, R, bpt) are grouped, each group's bytes are uploaded
     once per batch and decoded by model.decompress_rec -- the arithmetic decoder, the row checks and the generative pass on the
@@ -272,50 +272,33 @@ def _decompress_images(model, paths, batch, strict, lossless, tables=None):
     header could be read seed, image_shape, block_size, decomp_time; `error` with the coder's text where status != 0).
     strict: CodingError for the first file, in the order of `paths`, that cannot be decoded; strict=False reports it in its row and
     leaves its image zero.
-    lossless: beside every NAME.rec lies NAME.res (a missing one reads as an empty file); the images are the uint8 pixels of
-    model.decompress_lossless, and status may be STATUS_RESIDUAL + irec_res_status."""
-    from .io.residual import stream_len_of
+    What is the model's: fits(info, key) -- whether the model decodes the group `key` of rec_file_groups, info being the header words
+    of its first file -- and decode(part, info, blob, off, seed, shape, max_K) -> (images [n, 3, H, W], status [n], the texts of the
+    nonzero ones) for the files `part` (indices into paths) of such a group: blob / off their bytes on the host, max_K their headers'
+    largest word or the largest K of `tables` (a file under count tables says 0xFFFFFFFF).
+    res: the images are uint8 pixels (decompress_images_lossless): the dtype of a refused group's zeros."""
     dev = next(model.parameters()).device
-    res_datas = []
-    for path in paths if lossless else []:
-        res_path = os.path.splitext(path)[0] + ".res"
-        res_datas.append(open(res_path, "rb").read() if os.path.exists(res_path) else b"")
-    datas = []
-    for path in paths:
-        with open(path, "rb") as fh:
-            datas.append(fh.read())
+    datas = [_read(path) for path in paths]
     infos, groups = rec_file_groups(datas)
     images, rows = [None] * len(paths), [None] * len(paths)
     for i, w in enumerate(infos):
         if w is None:
             rows[i] = {"name": os.path.basename(paths[i]), "status": 4, "error": status_text(4)}     # IREC_REC_E_TRUNCATED_HEADER
-    for (seed, (h, w_, c), R, bpt), members in groups.items():
-        fits = isinstance(bpt, int) and R == model.num_res_blocks and c == 3 and h % 2 == 0 and w_ % 2 == 0 and \
-            bpt == model.blocks_per_tensor((1, c, h, w_))
+    for key, members in groups.items():
+        seed, (h, w_, c), R, bpt = key
+        ok = fits(infos[members[0]], key)
         step = len(members) if not batch else int(batch)
         for lo in range(0, len(members), step):
             part = members[lo:lo + step]
             t0 = time.perf_counter()
-            if fits:
-                sizes = np.array([len(datas[i]) for i in part], dtype=np.int64)
-                off = np.concatenate([[0], np.cumsum(sizes)])
-                host = np.frombuffer(b"".join(datas[i] for i in part), dtype=np.uint8)
+            if ok:
+                blob, off = _joined([datas[i] for i in part])
                 max_K = max([1] + [m for i in part for m in infos[i]["max_partitions"] if m <= 65536])
                 if tables is not None and tables.max_K is not None:
-                    max_K = max(max_K, tables.max_K)          # (a file under count tables says 0xFFFFFFFF: the bound is the tables')
-                blob = torch.from_numpy(host.copy()).to(dev)
-                if lossless:
-                    res_off = np.concatenate([[0], np.cumsum([len(res_datas[i]) for i in part])]).astype(np.int64)
-                    res_host = np.frombuffer(b"".join(res_datas[i] for i in part), dtype=np.uint8)
-                    res_blob = torch.from_numpy(res_host.copy()).to(dev)
-                    L = stream_len_of(res_datas[part[0]])
-                    rec, status, K = model._decompress_lossless_status(blob, off, res_blob, res_off, seed, (len(part), c, h, w_), max_K,
-                                                                       L if L and 1 <= L <= 4096 else None)
-                else:
-                    rec, status, K = model._decompress_rec_status(blob, off, seed, (len(part), c, h, w_), max_K, tables)
-                texts = [model.status_text(st, K[k]) if st else "" for k, st in enumerate(status)]
+                    max_K = max(max_K, tables.max_K)
+                rec, status, texts = decode(part, infos[members[0]], blob, off, seed, (len(part), c, h, w_), max_K)
             else:                                                       # IREC_REC_E_STRUCTURE: not this model's block structure
-                rec, status = torch.zeros((len(part), 3, h, w_), device=dev, dtype=torch.uint8 if lossless else None), [17] * len(part)
+                rec, status = torch.zeros((len(part), 3, h, w_), device=dev, dtype=torch.uint8 if res else None), [17] * len(part)
                 texts = [f"{status_text(17)}: {R} residual blocks of {bpt} blocks for a {h} x {w_} x {c} image do not match the model"] * len(part)
             dt = (time.perf_counter() - t0) / len(part)
             for k, i in enumerate(part):
@@ -332,6 +315,48 @@ def _decompress_images(model, paths, batch, strict, lossless, tables=None):
     if len(shapes) == 1 and all(im is not None for im in images):
         return torch.stack(images, dim=0), rows
     return images, rows
+
+
+def _decompress_images(model, paths, batch, strict, lossless, tables=None):
+    """_decompress_groups for BidirectionalResNetVAE: the files' bytes uploaded once per batch and decoded by model.decompress_rec[_tables]
+    -- the arithmetic decoder, the row checks and the generative pass on the device, one read-back (the per-image status) per batch.
+    lossless: beside every NAME.rec lies NAME.res (a missing one reads as an empty file); the images are the uint8 pixels of
+    model.decompress_lossless, and status may be STATUS_RESIDUAL + irec_res_status."""
+    from .io.residual import stream_len_of
+    dev = next(model.parameters()).device
+
+    def fits(info, key):
+        _, (h, w, c), R, bpt = key
+        return isinstance(bpt, int) and R == model.num_res_blocks and c == 3 and h % 2 == 0 and w % 2 == 0 and bpt == model.blocks_per_tensor((1, c, h, w))
+
+    def decode(part, info, blob, off, seed, shape, max_K):
+        if lossless:
+            res = [_read(os.path.splitext(paths[i])[0] + ".res", missing=b"") for i in part]
+            res_blob, res_off = _joined(res)
+            L = stream_len_of(res[0])
+            rec, status, K = model._decompress_lossless_status(_upload(blob, dev), off, _upload(res_blob, dev), res_off, seed, shape, max_K,
+                                                               L if L and 1 <= L <= 4096 else None)
+        else:
+            rec, status, K = model._decompress_rec_status(_upload(blob, dev), off, seed, shape, max_K, tables)
+        return rec, status, [model.status_text(st, K[k]) if st else "" for k, st in enumerate(status)]
+    return _decompress_groups(model, paths, batch, strict, fits, decode, tables, lossless)
+
+
+def decompress_images(model, paths, batch=None, strict=True):
+    """The read side of compress_images (_decompress_groups has the description)."""
+    return _decompress_images(model, paths, batch, strict, False)
+
+
+def decompress_images_tables(model, paths, tables, batch=None, strict=True):
+    """decompress_images for files written under an irec.io.SymbolTables (compress_images(tables=)); files without header flags decode
+    in the same call.  A function of its own: decompress_images' signature is pinned."""
+    return _decompress_images(model, paths, batch, strict, False, tables)
+
+
+def decompress_images_lossless(model, paths, batch=None, strict=True):
+    """The read side of compress_images(lossless=True): decompress_images over NAME.rec + NAME.res pairs (`paths` names the .rec
+    files), the images being the uint8 pixels.  A function of its own: decompress_images' signature is pinned."""
+    return _decompress_images(model, paths, batch, strict, True)
 
 
 # ---- the two-level lossy model (irec.models.lossy.Large2LevelVAE): the same two drivers over ragged files -------------------------
@@ -372,61 +397,33 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
     from .io import decode_files_device_ragged, decode_files_device_segmented, decode_files_ragged, decode_files_segmented
     if segment_blocks is not None and tables is not None:
         raise ValueError("compress_images_lossy: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
-    extension = "rec" if segment_blocks is None else "recs"
     os.makedirs(out_dir, exist_ok=True)
     n = images.shape[0]
     batch = n if not batch else int(batch)
     S = model._max_index(sampler)
-    rows = []
-    for lo in range(0, n, batch):
-        chunk = images[lo:lo + batch]
-        m, _, h, w = chunk.shape
+    ragged, segmented = (decode_files_device_ragged, decode_files_device_segmented) if rec_on_device else (decode_files_ragged, decode_files_segmented)
+
+    def leg(lo, hi):
+        chunk = images[lo:hi]
+        _, _, h, w = chunk.shape
         t0 = time.perf_counter()
-        try:
-            (blob, off, reconstruction), (K, idx, bpr) = model.compress_rec(chunk, seed, sampler, block_size=block_size,
-                                                                            rec_on_device=rec_on_device, return_pendings=True, tables=tables,
-                                                                            segment_blocks=segment_blocks)
-        except CodingError as e:                         # compression_performance.py:375-377: log and move on
-            rows += [{"name": names[lo + i], "error": str(e)} for i in range(m)]
-            continue
+        (blob, off, reconstruction), (K, idx, bpr) = model.compress_rec(chunk, seed, sampler, block_size=block_size, rec_on_device=rec_on_device,
+                                                                        return_pendings=True, tables=tables, segment_blocks=segment_blocks)
         columns = _lossy_quality_columns(model, chunk, reconstruction, image_range) if quality else None   # (launched; read below)
-        t_compress = time.perf_counter() - t0
-        t1 = time.perf_counter()
-        host, off_host = (blob.cpu().numpy(), off.cpu().numpy()) if rec_on_device else (blob, off)
-        paths = [os.path.join(out_dir, f"{nm}.{extension}") for nm in names[lo:lo + m]]
-        mv = memoryview(host)
-        for i, path in enumerate(paths):
-            with open(path, "wb") as fh:
-                fh.write(mv[off_host[i]:off_host[i + 1]])
-        back = [open(path, "rb").read() for path in paths]
-        sizes = np.array([len(b) for b in back], dtype=np.int64)
-        off2 = np.concatenate([[0], np.cumsum(sizes)])
-        blob2 = np.frombuffer(b"".join(back), dtype=np.uint8)
-        want = np.array([seed, block_size, h, w, 3], dtype=np.int64)
-        if rec_on_device:
-            blob2 = torch.from_numpy(blob2.copy()).to(blob.device)
-            hdr, K2, idx2 = decode_files_device_ragged(blob2, off2, bpr, idx.shape[2], tables=tables) if segment_blocks is None else \
-                decode_files_device_segmented(blob2, off2, bpr, idx.shape[2], segment_blocks)
-            live = torch.arange(idx.shape[2], device=idx.device)[None, None, :] < K[..., None]
-            same = ((K2 == K).all(dim=1) & ((idx2 == idx) | ~live).all(dim=2).all(dim=1) &
-                    (hdr[:, [0, 1, 3, 4, 5]] == torch.from_numpy(want).to(hdr.device)).all(dim=1)).cpu().numpy()
-            n_idx = K.sum(dim=1).cpu().numpy()
+        t_compress, t1 = time.perf_counter() - t0, time.perf_counter()
+        if segment_blocks is None:
+            decode = lambda b, o: ragged(b, o, bpr, idx.shape[2], tables=tables)  # noqa: E731
         else:
-            hdr, K2, idx2 = decode_files_ragged(blob2, off2, bpr, idx.shape[2], tables=tables) if segment_blocks is None else \
-                decode_files_segmented(blob2, off2, bpr, idx.shape[2], segment_blocks)
-            live = np.arange(idx.shape[2])[None, None, :] < K[..., None]
-            same = (K2 == K).all(axis=1) & ((idx2 == idx) | ~live).all(axis=(1, 2)) & (hdr[:, [0, 1, 3, 4, 5]].astype(np.int64) == want).all(axis=1)
-            n_idx = K.sum(axis=1)
-        t_host = (time.perf_counter() - t1) / m
-        rows += [{"name": names[lo + i], "comp_codelength": int(sizes[i]) * 8, "comp_lossy_bpp": int(sizes[i]) * 8 / (h * w),
-                  "comp_code_bpd": int(sizes[i]) * 8 / (h * w * 3), "code_nats": int(n_idx[i]) * float(np.log(S)),
-                  "n_indices": int(n_idx[i]), "indices_recovered": bool(same[i]), "comp_time": t_compress / m + t_host} for i in range(m)]
+            decode = lambda b, o: segmented(b, o, bpr, idx.shape[2], segment_blocks)  # noqa: E731
+        rows = _check_leg(out_dir, names[lo:hi], "rec" if segment_blocks is None else "recs", blob, off, K, idx, decode,
+                          (seed, block_size, h, w, 3), S, t_compress, t1)
         if quality:
             psnr, ms_ssim, kld = columns.cpu().numpy()           # the one extra read-back
-            for i, row in enumerate(rows[-m:]):
+            for i, row in enumerate(rows):
                 row.update({"psnr": float(psnr[i]), "ms_ssim": float(ms_ssim[i]), "kld": float(kld[i]),
                             "lossy_bpp": float(kld[i]) / (h * w * float(np.log(2.0)))})
-    return rows
+        return rows
+    return [row for rows in _in_batches(n, batch, names, leg) for row in rows]
 
 
 def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_on_device=False, tables=None):
@@ -437,52 +434,18 @@ def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_
     Segmented files (NAME.recs) are told from the reference's by their magic and decoded in groups of their own, under the
     segment_blocks their headers name and the default symbol models."""
     dev = next(model.parameters()).device
-    datas = []
-    for path in paths:
-        with open(path, "rb") as fh:
-            datas.append(fh.read())
-    infos, groups = rec_file_groups(datas)
-    images, rows = [None] * len(paths), [None] * len(paths)
-    for i, w in enumerate(infos):
-        if w is None:
-            rows[i] = {"name": os.path.basename(paths[i]), "status": 4, "error": status_text(4)}     # IREC_REC_E_TRUNCATED_HEADER
-    for (seed, (h, w_, c), R, bpt), members in groups.items():
-        g = infos[members[0]].get("segment_blocks")      # None: the reference's container
-        fits = R == 2 and c == 3 and h % 64 == 0 and w_ % 64 == 0 and h > 0 and w_ > 0 and g != 0 and \
-            list(infos[members[0]]["bpt"]) == model.blocks_per_res((1, c, h, w_), sampler.block_size)
-        step = len(members) if not batch else int(batch)
-        for lo in range(0, len(members), step):
-            part = members[lo:lo + step]
-            t0 = time.perf_counter()
-            if fits:
-                sizes = np.array([len(datas[i]) for i in part], dtype=np.int64)
-                off = np.concatenate([[0], np.cumsum(sizes)])
-                host = np.frombuffer(b"".join(datas[i] for i in part), dtype=np.uint8)
-                max_K = max([1] + [m for i in part for m in infos[i]["max_partitions"] if m <= 65536])
-                if tables is not None and tables.max_K is not None:
-                    max_K = max(max_K, tables.max_K)
-                blob = torch.from_numpy(host.copy()).to(dev) if rec_on_device else host
-                rec, status = model.decompress_rec(blob, off, seed, (len(part), c, h, w_), sampler, max_K=max_K, strict=False,
-                                                   rec_on_device=rec_on_device, tables=tables if g is None else None, segment_blocks=g)
-                texts = [status_text(int(st)) if st else "" for st in status]
-            else:                                                       # IREC_REC_E_STRUCTURE: not this model's block structure
-                rec, status = torch.zeros((len(part), 3, h, w_), device=dev), [17] * len(part)
-                texts = [f"{status_text(17)}: {R} residual blocks of {bpt} blocks for a {h} x {w_} x {c} image do not match the model"] * len(part)
-            dt = (time.perf_counter() - t0) / len(part)
-            for k, i in enumerate(part):
-                images[i] = rec[k] if status[k] == 0 else torch.zeros_like(rec[k])
-                rows[i] = {"name": os.path.basename(paths[i]), "seed": seed, "image_shape": (h, w_, c), "block_size": infos[i]["block_size"],
-                           "status": int(status[k]), "decomp_time": dt}
-                if status[k]:
-                    rows[i]["error"] = texts[k]
-    if strict:
-        for i, row in enumerate(rows):
-            if row["status"]:
-                raise CodingError(f"{row['error']} (image {i})")
-    shapes = {tuple(im.shape) for im in images if im is not None}
-    if len(shapes) == 1 and all(im is not None for im in images):
-        return torch.stack(images, dim=0), rows
-    return images, rows
+
+    def fits(info, key):
+        _, (h, w, c), R, _ = key
+        return R == 2 and c == 3 and h % 64 == 0 and w % 64 == 0 and h > 0 and w > 0 and info.get("segment_blocks") != 0 and \
+            list(info["bpt"]) == model.blocks_per_res((1, c, h, w), sampler.block_size)
+
+    def decode(part, info, blob, off, seed, shape, max_K):
+        g = info.get("segment_blocks")                   # None: the reference's container
+        rec, status = model.decompress_rec(_upload(blob, dev) if rec_on_device else blob, off, seed, shape, sampler, max_K=max_K,
+                                           strict=False, rec_on_device=rec_on_device, tables=tables if g is None else None, segment_blocks=g)
+        return rec, status, [status_text(int(st)) if st else "" for st in status]
+    return _decompress_groups(model, paths, batch, strict, fits, decode, tables)
 
 
 # ---- fitting symbol tables (irec.io.SymbolTables) to a model's own rows -----------------------------------------------------------------
@@ -525,7 +488,7 @@ def fit_symbol_tables(model, images, seed, batch=None, max_K=None):
 def fit_symbol_tables_lossy(model, sampler, images, seed, block_size, batch=None, max_K=None):
     """fit_symbol_tables for Large2LevelVAE and its coder `sampler`: one index table, one count table for each of the two levels.
     block_size: the coder's, as compress_images_lossy takes it (the layout is the sampler's own)."""
-    from .coding.beam_search_coder import PendingCode
+    from .coding.pending import PendingCode
     n = images.shape[0]
     step = n if not batch else int(batch)
     rows = []

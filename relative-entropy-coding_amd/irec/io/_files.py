@@ -43,6 +43,22 @@ def device_offsets(offsets, blob, dev, on_device, who, n=None):
     return torch.from_numpy(host_offsets(offsets, blob.numel(), who, n).copy()).to(dev)   # (a copy: the caller's array may be read-only)
 
 
+def gather_heads(blob, offsets, head_bytes):
+    """The first head_bytes bytes of every file of a blob on the device, gathered there and copied to the host in ONE read-back:
+    (bytes uint8 numpy [N head_bytes], offsets int64 [N + 1] into them) -- what a host function over (blob, offsets) takes.  A file
+    shorter than that, or whose range leaves the blob, reads as zeros; no files or no bytes: an empty blob, nothing read back."""
+    import torch
+    dev = blob.device
+    off = offsets.to(dev) if hasattr(offsets, "is_cuda") else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev)
+    n = off.numel() - 1
+    if n < 1 or blob.numel() < 1:
+        return np.zeros(0, np.uint8), np.zeros(1, np.int64)
+    at = (off[:-1, None] + torch.arange(head_bytes, device=dev)).clamp_(0, blob.numel() - 1)
+    whole = (off[1:] - off[:-1] >= head_bytes) & (off[:-1] >= 0) & (off[1:] <= blob.numel())
+    head = blob.reshape(-1)[at] * whole[:, None].to(torch.uint8)
+    return head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * head_bytes
+
+
 # ---- a device writer: offsets and status in one buffer, one read-back, a second run at the size the first one reports ----------------
 def offsets_and_status(n, dev):
     """(offsets int64 [N + 1], status int32 [N], both): views of one int64 device buffer `both`, which one copy fetches."""

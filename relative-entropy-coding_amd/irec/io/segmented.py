@@ -86,78 +86,26 @@ def segmented_files_max_K(blob, offsets):
 def segmented_files_max_K_device(blob, offsets, blocks_per_res, segment_blocks):
     """segmented_files_max_K for a blob on the device: only the fixed part and the directory of every file (40 + 4 R + 12 S bytes, by
     the call's layout) are gathered and copied to the host."""
-    import torch
-    layout, g, n_seg = _layout(blocks_per_res, segment_blocks, "segmented_files_max_K_device")
-    dev, hb = blob.device, FIXED_BYTES + 4 * layout.R + 12 * n_seg
-    off = offsets.to(dev) if hasattr(offsets, "is_cuda") else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev)
-    n = off.numel() - 1
-    if n < 1 or blob.numel() < 1:
-        return 1
-    at = (off[:-1, None] + torch.arange(hb, device=dev)).clamp_(0, blob.numel() - 1)
-    whole = (off[1:] - off[:-1] >= hb) & (off[:-1] >= 0) & (off[1:] <= blob.numel())              # a shorter file: a zero header, no words
-    head = blob.reshape(-1)[at] * whole[:, None].to(torch.uint8)
-    return segmented_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb)
-
-
-def _layout(blocks_per_res, segment_blocks, who):
-    layout = U._Layout.ragged(blocks_per_res, who)
-    g = int(segment_blocks)
-    if g < 1 or g > _lib.INT32_MAX:
-        raise ValueError(f"{who}: segment_blocks must be at least 1 (got {segment_blocks})")
-    return layout, g, int(sum(-(-int(b) // g) for b in layout.bpr))
-
-
-def _first_cap(n, layout, g, n_seg, max_K):
-    """A first allowance: the fixed parts, and 64 + 40 bits per symbol and terminator of every stream (irec_io.cpp's own)."""
-    blocks = int(layout.bpr.astype(np.int64).sum())
-    return n * (FIXED_BYTES + 4 * layout.R + n_seg * (12 + 2 * 9 + 2 * 5) + 5 * blocks * (1 + max_K))
+    layout = U._Layout.segmented(blocks_per_res, segment_blocks, "segmented_files_max_K_device")
+    return segmented_files_max_K(*_files.gather_heads(blob, offsets, FIXED_BYTES + 4 * layout.R + 12 * layout.n_segments))
 
 
 # ---- host -----------------------------------------------------------------------------------------------------------------------------------
 def encode_files_segmented(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, segment_blocks, n_threads=0):
     """N segmented files at once on host threads (irec_rec_encode_files_segmented), parallel over (image, segment): K [N, T] int32,
     idx [N, T, max_K] int32.  Returns (blob uint8, offsets int64 [N + 1]); ValueError naming the first image that cannot be coded."""
-    lib = _lib.load()
-    layout, g, n_seg = _layout(blocks_per_res, segment_blocks, "encode_files_segmented")
+    layout = U._Layout.segmented(blocks_per_res, segment_blocks, "encode_files_segmented")
     K = np.ascontiguousarray(K, dtype=np.int32)
     idx = np.ascontiguousarray(idx, dtype=np.int32)
-    if K.ndim != 2 or K.shape[1] != layout.T or idx.ndim != 3 or idx.shape[:2] != K.shape:
-        raise ValueError(f"encode_files_segmented: K {K.shape} and idx {idx.shape} are not [N, {layout.T}] and [N, {layout.T}, max_K]")
-    n, max_K = K.shape[0], idx.shape[2]
-    h, w, c = (int(v) for v in image_shape)
-    offsets = np.zeros(n + 1, dtype=np.int64)
-    status = np.zeros(max(n, 1), dtype=np.int32)
-
-    def call(out):
-        total = lib.irec_rec_encode_files_segmented(int(seed), int(block_size), int(max_index), h, w, c, n, layout.R, layout.bpr.ctypes.data, g,
-                                                    max_K, K.ctypes.data, idx.ctypes.data if idx.size else None, out.ctypes.data, out.size,
-                                                    offsets.ctypes.data, status.ctypes.data, int(n_threads))
-        if total < 0:
-            raise ValueError(lib.irec_last_error().decode())
-        _raise_first_status(status[:n])
-        return total
-    return _files.encode_host(call, max(_first_cap(n, layout, g, n_seg, max_K), 1)), offsets
+    U._check_rows(K, idx, layout, "encode_files_segmented")
+    return U._encode_rows_host(seed, image_shape, block_size, K, idx, max_index, layout, n_threads, None, "encode_files_segmented")
 
 
 def _decode_files_segmented_status(blob, offsets, blocks_per_res, segment_blocks, max_K, n_threads=0):
     """irec_rec_decode_files_segmented: (headers [N, 9] uint32, K [N, T], idx [N, T, max_K], status int32 [N]) -- a verdict per file, the
     outputs of a refused one zero."""
-    lib = _lib.load()
-    layout, g, _ = _layout(blocks_per_res, segment_blocks, "decode_files_segmented")
-    blob = np.ascontiguousarray(blob, dtype=np.uint8)
-    offsets = _files.host_offsets(offsets, blob.size, "decode_files_segmented")
-    n = offsets.size - 1
-    hdr = np.zeros((max(n, 1), 9), dtype=np.uint32)
-    K = np.zeros((n, layout.T), dtype=np.int32)
-    idx = np.zeros((n, layout.T, int(max_K)), dtype=np.int32)
-    status = np.zeros(max(n, 1), dtype=np.int32)
-    pad = np.zeros(1, dtype=np.uint8)
-    st = lib.irec_rec_decode_files_segmented(blob.ctypes.data if blob.size else pad.ctypes.data, offsets.ctypes.data, n, layout.R,
-                                             layout.bpr.ctypes.data, g, int(max_K), hdr.ctypes.data, K.ctypes.data if K.size else pad.ctypes.data,
-                                             idx.ctypes.data if idx.size else None, status.ctypes.data, int(n_threads))
-    if st != 0:
-        raise ValueError(lib.irec_last_error().decode())
-    return hdr[:n], K, idx, status[:n]
+    layout = U._Layout.segmented(blocks_per_res, segment_blocks, "decode_files_segmented")
+    return U._decode_rows_host_status(blob, offsets, layout, max_K, None, n_threads, "decode_files_segmented")
 
 
 def decode_files_segmented(blob, offsets, blocks_per_res, max_K, segment_blocks=None, n_threads=0):
@@ -177,58 +125,20 @@ def decode_files_segmented(blob, offsets, blocks_per_res, max_K, segment_blocks=
 
 # ---- device: CUDA tensors in and out, the launches on the current stream ------------------------------------------------------------------
 def _encode_files_device_segmented_launch(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, segment_blocks, out):
-    """One irec_rec_encode_files_device_segmented call on the current stream over rows K [N, T], idx [N, T, max_K], nothing read back:
-    (offsets int64 [N + 1], status int32 [N], both views of `both`, which one copy fetches).  The bytes are in `out` only if
-    offsets[N] <= out.numel()."""
+    """U._encode_rows_device_launch for checked rows in segments (irec_rec_encode_files_device_segmented)."""
     import torch
-    lib = _lib.load()
     who = "encode_files_device_segmented"
-    layout, g, _ = _layout(blocks_per_res, segment_blocks, who)
+    layout = U._Layout.segmented(blocks_per_res, segment_blocks, who)
     if not (K.is_cuda and idx.is_cuda and K.dtype == torch.int32 and idx.dtype == torch.int32):
         raise ValueError(f"{who} takes CUDA int32 tensors")
-    if K.dim() != 2 or K.shape[1] != layout.T or idx.dim() != 3 or tuple(idx.shape[:2]) != tuple(K.shape):
-        raise ValueError(f"{who}: K {tuple(K.shape)} and idx {tuple(idx.shape)} are not [N, {layout.T}] and [N, {layout.T}, max_K]")
-    n, max_K = K.shape[0], idx.shape[2]
-    h, w, c = (int(v) for v in image_shape)
-    K, ks, idx, ist = U._row_strides(K, idx)
-    dev = K.device
-    with torch.cuda.device(dev):
-        ws = torch.empty(max(lib.irec_rec_seg_workspace_bytes(n, layout.R, layout.bpr.ctypes.data, g), 8), dtype=torch.uint8, device=dev)
-        offsets, status, both = _files.offsets_and_status(n, dev)
-        st = lib.irec_rec_encode_files_device_segmented(
-            int(seed), int(block_size), int(max_index), h, w, c, n, layout.R, layout.bpr.ctypes.data, g, max_K, K.data_ptr(), ks,
-            idx.data_ptr() if idx.numel() else None, ist, out.data_ptr() if out.numel() else None, out.numel(), offsets.data_ptr(),
-            status.data_ptr() if n else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
-    _files.check_status(st, "irec_rec_encode_files_device_segmented")
-    return offsets, status, both
+    U._check_rows(K, idx, layout, who)
+    return U._encode_rows_device_launch(seed, image_shape, block_size, K, idx, max_index, layout, out, None, who)
 
 
 def _decode_files_device_segmented_launch(blob, offsets, blocks_per_res, segment_blocks, max_K, on_device=False):
-    """One irec_rec_decode_files_device_segmented call on the current stream: (headers int32 [N, 9] holding the uint32 words, K [N, T],
-    idx [N, T, max_K], status int32 [N]) on the device.  Nothing is read back (U._decode_rows_device_launch's rules for the offsets)."""
-    import torch
-    lib = _lib.load()
+    """U._decode_rows_device_launch for blocks_per_res in segments (irec_rec_decode_files_device_segmented)."""
     who = "decode_files_device_segmented"
-    layout, g, _ = _layout(blocks_per_res, segment_blocks, who)
-    if not (blob.is_cuda and blob.dtype == torch.uint8):
-        raise ValueError(f"{who} takes a CUDA uint8 tensor")
-    blob = blob.contiguous()
-    dev = blob.device
-    max_K = int(max_K)
-    offsets = _files.device_offsets(offsets, blob, dev, on_device, who)
-    n = offsets.numel() - 1
-    with torch.cuda.device(dev):
-        ws = torch.empty(max(lib.irec_rec_seg_workspace_bytes(n, layout.R, layout.bpr.ctypes.data, g), 8), dtype=torch.uint8, device=dev)
-        hdr = torch.zeros((n, 9), dtype=torch.int32, device=dev)
-        K = torch.empty((n, layout.T), dtype=torch.int32, device=dev)
-        idx = torch.empty((n, layout.T, max_K), dtype=torch.int32, device=dev)
-        status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        st = lib.irec_rec_decode_files_device_segmented(
-            blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, layout.R, layout.bpr.ctypes.data, g, max_K,
-            hdr.data_ptr(), K.data_ptr(), idx.data_ptr() if idx.numel() else None, status.data_ptr(), ws.data_ptr(), ws.numel(),
-            torch.cuda.current_stream().cuda_stream)
-    _files.check_status(st, "irec_rec_decode_files_device_segmented")
-    return hdr, K, idx, status[:n]
+    return U._decode_rows_device_launch(blob, offsets, U._Layout.segmented(blocks_per_res, segment_blocks, who), max_K, on_device, None, who)
 
 
 def encode_files_device_segmented(seed, image_shape, block_size, K, idx, max_index, blocks_per_res, segment_blocks, out=None):
@@ -236,10 +146,10 @@ def encode_files_device_segmented(seed, image_shape, block_size, K, idx, max_ind
     contiguous or views of one joined [rows][1 + width] tensor (PendingCode.gather_packed_ragged_device).  Returns (blob uint8, offsets
     int64 [N + 1]) as CUDA tensors, byte for byte what encode_files_segmented gives; the only host synchronisation is ONE read-back of
     offsets and status.  out: a CUDA uint8 buffer to write into (a short one costs a second run at the size the first one reports)."""
-    layout, g, n_seg = _layout(blocks_per_res, segment_blocks, "encode_files_device_segmented")
+    layout = U._Layout.segmented(blocks_per_res, segment_blocks, "encode_files_device_segmented")
     n, max_K = (K.shape[0], idx.shape[2]) if K.dim() == 2 and idx.dim() == 3 else (0, 0)
-    out = U._device_out(out, lambda: _first_cap(n, layout, g, n_seg, max_K), K.device, "encode_files_device_segmented")
-    return _files.encode_device(lambda o: _encode_files_device_segmented_launch(seed, image_shape, block_size, K, idx, max_index, layout, g, o),
+    out = U._device_out(out, lambda: layout.first_cap(n, max_K), K.device, "encode_files_device_segmented")
+    return _files.encode_device(lambda o: _encode_files_device_segmented_launch(seed, image_shape, block_size, K, idx, max_index, layout, segment_blocks, o),
                                 K.shape[0], out, seg_status_text, "irec_rec_encode_files_device_segmented")
 
 

@@ -178,10 +178,11 @@ def _raise_first_status(status):
 class _Layout:
     """The blocks per residual block of a call: R residual blocks of bpt blocks each (uniform: any R the container holds), or one count
     per residual block (ragged: the two-level lossy model codes 13 blocks at level 2 and 302 at level 1).  bpr int32 [R] either way,
-    T = sum(bpr) rows per image."""
+    T = sum(bpr) rows per image.  segment_blocks: the segmented container's cut of every residual block (irec.io.segmented), None for
+    the reference's."""
 
-    def __init__(self, R, bpt=None, bpr=None):
-        self.R, self.bpt = int(R), bpt
+    def __init__(self, R, bpt=None, bpr=None, segment_blocks=None):
+        self.R, self.bpt, self.segment_blocks = int(R), bpt, segment_blocks
         self.bpr = np.full(self.R, bpt, dtype=np.int32) if bpr is None else bpr
         self.T = self.R * bpt if bpr is None else int(bpr.sum())
 
@@ -194,12 +195,59 @@ class _Layout:
             raise ValueError(f"{what}: blocks_per_res must hold at least one entry, every entry >= 1, their sum an int32 (got {list(bpr)})")
         return cls(bpr.size, bpr=bpr.astype(np.int32))
 
+    @classmethod
+    def segmented(cls, blocks_per_res, segment_blocks, what):
+        """The ragged layout of blocks_per_res in segments of segment_blocks coder blocks (a layout of that segment size: itself)."""
+        ragged = cls.ragged(blocks_per_res, what)
+        g = int(segment_blocks)
+        if ragged.segment_blocks is not None and ragged.segment_blocks != g:
+            raise ValueError(f"{what}: a layout in segments of {ragged.segment_blocks} blocks, not of {segment_blocks}")
+        if ragged.segment_blocks is not None:
+            return ragged
+        if g < 1 or g > _lib.INT32_MAX:
+            raise ValueError(f"{what}: segment_blocks must be at least 1 (got {segment_blocks})")
+        return cls(ragged.R, bpr=ragged.bpr, segment_blocks=g)
+
+    @property
+    def n_segments(self):
+        return int(sum(-(-int(b) // self.segment_blocks) for b in self.bpr))
+
     def entry(self, tables):
-        """(the suffix of the library entry a call of this layout reaches, its blocks_per_res argument): the entries without a suffix
-        take one count, `_ragged` an array; any tables go to `_tables`, which takes the array (at most REC_RAGGED_MAX_RES entries)."""
+        """(the suffix of the library entry a call of this layout reaches, its layout arguments): the entries without a suffix take one
+        count, `_ragged` an array; any tables go to `_tables`, which takes the array (at most REC_RAGGED_MAX_RES entries); `_segmented`
+        takes the array and the segment size."""
+        if self.segment_blocks is not None:
+            return "_segmented", (self.bpr.ctypes.data, self.segment_blocks)
         if tables is not None:
-            return "_tables", self.bpr.ctypes.data
-        return ("", self.bpt) if self.bpt is not None else ("_ragged", self.bpr.ctypes.data)
+            return "_tables", (self.bpr.ctypes.data,)
+        return ("", (self.bpt,)) if self.bpt is not None else ("_ragged", (self.bpr.ctypes.data,))
+
+    def first_cap(self, n, max_K):
+        """irec_io.cpp's own first allowance for the files of n images: 64 + 40 bits per symbol and terminator, per stream."""
+        b = self.bpr.astype(np.int64)
+        if self.segment_blocks is not None:
+            return n * (40 + 4 * self.R + self.n_segments * (12 + 2 * 9 + 2 * 5) + 5 * int(b.sum()) * (1 + max_K))
+        return n * (28 + 16 * self.R + int(((64 + 40 * (b + 1)) // 8 + 1 + (64 + 40 * (b * max_K + 1)) // 8 + 1).sum()))
+
+    def workspace_bytes(self, lib, n):
+        """The workspace a device call of this layout over n images takes."""
+        if self.segment_blocks is not None:
+            return lib.irec_rec_seg_workspace_bytes(n, self.R, self.bpr.ctypes.data, self.segment_blocks)
+        return lib.irec_rec_device_workspace_bytes(n, self.R)
+
+    @property
+    def status_text(self):
+        """irec_rec_status -> text for a call of this layout."""
+        if self.segment_blocks is not None:
+            from .segmented import seg_status_text
+            return seg_status_text
+        return _rec_status_text
+
+
+def _check_rows(K, idx, layout, who):
+    """ValueError for rows (numpy or torch) that are not K [N, T], idx [N, T, max_K] of the layout."""
+    if len(K.shape) != 2 or K.shape[1] != layout.T or len(idx.shape) != 3 or tuple(idx.shape[:2]) != tuple(K.shape):
+        raise ValueError(f"{who}: K {tuple(K.shape)} and idx {tuple(idx.shape)} are not [N, {layout.T}] and [N, {layout.T}, max_K]")
 
 
 def _block_rows(K, idx):
@@ -215,26 +263,31 @@ def _block_rows(K, idx):
 
 # ---- host ---------------------------------------------------------------------------------------------------------------------------------
 def _encode_rows_host(seed, image_shape, block_size, K, idx, max_index, layout, n_threads, tables, who):
-    """irec_rec_encode_files[_ragged|_tables] over contiguous rows: (blob uint8, offsets int64 [N + 1])."""
+    """irec_rec_encode_files[_ragged|_tables|_segmented] over contiguous rows: (blob uint8, offsets int64 [N + 1])."""
     lib = _lib.load()
     n, max_K = K.shape[0], idx.shape[2]
     h, w, c = (int(v) for v in image_shape)
     suffix, blocks = layout.entry(tables)
     encode = getattr(lib, "irec_rec_encode_files" + suffix)
     offsets = np.zeros(n + 1, dtype=np.int64)
-    status = np.zeros(max(n, 1), dtype=np.int32)               # (per-image statuses: the entry with tables only)
+    status = np.zeros(max(n, 1), dtype=np.int32)               # (per-image statuses: the entries with tables and of segments only)
     tb = () if tables is None else tables.host_args(layout.R, who)
-    last_error = lib.irec_io_last_error if tables is None else lib.irec_last_error
+    newer = suffix in ("_tables", "_segmented")
+    last_error = lib.irec_last_error if newer else lib.irec_io_last_error
+    if layout.segment_blocks is not None:
+        cap = max(layout.first_cap(n, max_K), 1)
+    else:
+        cap = n * (64 + 16 * layout.R) + 2 * int(K.sum()) + 16 * K.size + 1024
 
     def call(out):
-        total = encode(int(seed), int(block_size), int(max_index), h, w, c, n, layout.R, blocks, max_K, K.ctypes.data,
+        total = encode(int(seed), int(block_size), int(max_index), h, w, c, n, layout.R, *blocks, max_K, K.ctypes.data,
                        idx.ctypes.data if idx.size else None, *tb, out.ctypes.data, out.size, offsets.ctypes.data,
-                       *(() if tables is None else (status.ctypes.data,)), int(n_threads))
+                       *((status.ctypes.data,) if newer else ()), int(n_threads))
         if total < 0:
             raise ValueError(last_error().decode())
-        _raise_first_status(status[:n])
+        _files.raise_first_status(status[:n], layout.status_text)
         return total
-    return _files.encode_host(call, n * (64 + 16 * layout.R) + 2 * int(K.sum()) + 16 * K.size + 1024), offsets
+    return _files.encode_host(call, cap), offsets
 
 
 def _decode_rows_host(blob, offsets, layout, max_K, n_threads):
@@ -247,7 +300,7 @@ def _decode_rows_host(blob, offsets, layout, max_K, n_threads):
     K = np.zeros((n, layout.T), dtype=np.int32)
     idx = np.zeros((n, layout.T, max(max_K, 1)), dtype=np.int32)
     suffix, blocks = layout.entry(None)
-    st = getattr(lib, "irec_rec_decode_files" + suffix)(blob.ctypes.data, offsets.ctypes.data, n, layout.R, blocks, int(max_K), hdr.ctypes.data,
+    st = getattr(lib, "irec_rec_decode_files" + suffix)(blob.ctypes.data, offsets.ctypes.data, n, layout.R, *blocks, int(max_K), hdr.ctypes.data,
                                                         K.ctypes.data, idx.ctypes.data, int(n_threads))
     if st != 0:
         raise ValueError(lib.irec_io_last_error().decode())
@@ -289,8 +342,7 @@ def encode_files_ragged(seed, image_shape, block_size, K, idx, max_index, blocks
     layout = _Layout.ragged(blocks_per_res, "encode_files_ragged")
     K = np.ascontiguousarray(K, dtype=np.int32)
     idx = np.ascontiguousarray(idx, dtype=np.int32)
-    if K.ndim != 2 or K.shape[1] != layout.T or idx.ndim != 3 or idx.shape[:2] != K.shape:
-        raise ValueError(f"encode_files_ragged: K {K.shape} and idx {idx.shape} are not [N, {layout.T}] and [N, {layout.T}, max_K]")
+    _check_rows(K, idx, layout, "encode_files_ragged")
     return _encode_rows_host(seed, image_shape, block_size, K, idx, max_index, layout, n_threads, tables, "encode_files_ragged")
 
 
@@ -300,31 +352,37 @@ def decode_files_ragged(blob, offsets, blocks_per_res, max_K, n_threads=0, table
     layout = _Layout.ragged(blocks_per_res, "decode_files_ragged")
     if tables is None:
         return _decode_rows_host(blob, offsets, layout, max_K, n_threads)
-    hdr, K, idx, status = _decode_files_tables_status(blob, offsets, layout, max_K, tables, n_threads)
+    hdr, K, idx, status = _decode_rows_host_status(blob, offsets, layout, max_K, tables, n_threads, "decode_files_ragged")
     _raise_first_status(status)
     return hdr, K, idx
 
 
-def _decode_files_tables_status(blob, offsets, blocks_per_res, max_K, tables, n_threads=0):
-    """irec_rec_decode_files_tables: (headers [N, 9] uint32, K [N, T], idx [N, T, max_K], status int32 [N]) -- a verdict per file, the
-    outputs of a refused one zero."""
+def _decode_rows_host_status(blob, offsets, layout, max_K, tables, n_threads, who):
+    """irec_rec_decode_files_tables, or _segmented for a segmented layout: (headers [N, 9] uint32, K [N, T], idx [N, T, max_K], status
+    int32 [N]) -- a verdict per file (its text: layout.status_text), the outputs of a refused one zero."""
     lib = _lib.load()
-    layout = _Layout.ragged(blocks_per_res, "decode_files_ragged")
     blob = np.ascontiguousarray(blob, dtype=np.uint8)
-    offsets = _files.host_offsets(offsets, blob.size, "decode_files_ragged")
+    offsets = _files.host_offsets(offsets, blob.size, who)
     n = offsets.size - 1
-    hdr = np.zeros((n, 9), dtype=np.uint32)
+    hdr = np.zeros((max(n, 1), 9), dtype=np.uint32)
     K = np.zeros((n, layout.T), dtype=np.int32)
     idx = np.zeros((n, layout.T, int(max_K)), dtype=np.int32)
     status = np.zeros(max(n, 1), dtype=np.int32)
     pad = np.zeros(1, dtype=np.uint8)
-    st = lib.irec_rec_decode_files_tables(blob.ctypes.data if blob.size else pad.ctypes.data, offsets.ctypes.data, n, layout.R,
-                                          layout.bpr.ctypes.data, int(max_K), *tables.host_args(layout.R, "decode_files_ragged"),
-                                          hdr.ctypes.data, K.ctypes.data, idx.ctypes.data if idx.size else None, status.ctypes.data,
-                                          int(n_threads))
+    suffix, blocks = layout.entry(tables)
+    tb = () if tables is None else tables.host_args(layout.R, who)
+    st = getattr(lib, "irec_rec_decode_files" + suffix)(
+        blob.ctypes.data if blob.size else pad.ctypes.data, offsets.ctypes.data, n, layout.R, *blocks, int(max_K), *tb, hdr.ctypes.data,
+        K.ctypes.data if K.size else pad.ctypes.data, idx.ctypes.data if idx.size else None, status.ctypes.data, int(n_threads))
     if st != 0:
         raise ValueError(lib.irec_last_error().decode())
-    return hdr, K, idx, status[:n]
+    return hdr[:n], K, idx, status[:n]
+
+
+def _decode_files_tables_status(blob, offsets, blocks_per_res, max_K, tables, n_threads=0):
+    """_decode_rows_host_status for blocks_per_res under tables (irec_rec_decode_files_tables)."""
+    return _decode_rows_host_status(blob, offsets, _Layout.ragged(blocks_per_res, "decode_files_ragged"), max_K, tables, n_threads,
+                                    "decode_files_ragged")
 
 
 # ---- device: CUDA tensors in and out, the launches on the current stream -----------------------------------------------------------------
@@ -351,7 +409,7 @@ def _block_strides(K, idx):
 
 
 def _encode_rows_device_launch(seed, image_shape, block_size, K, idx, max_index, layout, out, tables, who):
-    """One irec_rec_encode_files_device[_ragged|_tables] call on the current stream over rows K [N, T], idx [N, T, max_K], nothing read
+    """One irec_rec_encode_files_device[_ragged|_tables|_segmented] call on the current stream over rows K [N, T], idx [N, T, max_K], nothing read
     back: (offsets int64 [N + 1], status int32 [N], both views of `both`, which one copy fetches).  The bytes are in `out` only if
     offsets[N] <= out.numel()."""
     import torch
@@ -362,11 +420,11 @@ def _encode_rows_device_launch(seed, image_shape, block_size, K, idx, max_index,
     dev = K.device
     suffix, blocks = layout.entry(tables)
     with torch.cuda.device(dev):
-        ws = torch.empty(max(lib.irec_rec_device_workspace_bytes(n, layout.R), 8), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(layout.workspace_bytes(lib, n), 8), dtype=torch.uint8, device=dev)
         offsets, status, both = _files.offsets_and_status(n, dev)
         tb = () if tables is None else tables.to(dev).device_args(layout.R, who)
         st = getattr(lib, "irec_rec_encode_files_device" + suffix)(
-            int(seed), int(block_size), int(max_index), h, w, c, n, layout.R, blocks, max_K, K.data_ptr(), ks,
+            int(seed), int(block_size), int(max_index), h, w, c, n, layout.R, *blocks, max_K, K.data_ptr(), ks,
             idx.data_ptr() if idx.numel() else None, ist, *tb, out.data_ptr() if out.numel() else None, out.numel(), offsets.data_ptr(),
             status.data_ptr() if n else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
     _files.check_status(st, "irec_rec_encode_files_device" + suffix)
@@ -374,7 +432,7 @@ def _encode_rows_device_launch(seed, image_shape, block_size, K, idx, max_index,
 
 
 def _decode_rows_device_launch(blob, offsets, layout, max_K, on_device, tables, who):
-    """One irec_rec_decode_files_device[_ragged|_tables] call on the current stream: (headers int32 [N, 9] holding the uint32 words,
+    """One irec_rec_decode_files_device[_ragged|_tables|_segmented] call on the current stream: (headers int32 [N, 9] holding the uint32 words,
     K [N, T], idx [N, T, max_K], status int32 [N]) on the device.  Nothing is read back: host `offsets` are checked against the blob
     before any kernel sees them, and with on_device those that are on the device stay there (_files.device_offsets)."""
     import torch
@@ -388,14 +446,14 @@ def _decode_rows_device_launch(blob, offsets, layout, max_K, on_device, tables, 
     n = offsets.numel() - 1
     suffix, blocks = layout.entry(tables)
     with torch.cuda.device(dev):
-        ws = torch.empty(max(lib.irec_rec_device_workspace_bytes(n, layout.R), 8), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(layout.workspace_bytes(lib, n), 8), dtype=torch.uint8, device=dev)
         hdr = torch.zeros((n, 9), dtype=torch.int32, device=dev)
         K = torch.empty((n, layout.T), dtype=torch.int32, device=dev)
         idx = torch.empty((n, layout.T, max_K), dtype=torch.int32, device=dev)
         status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
         tb = () if tables is None else tables.to(dev).device_args(layout.R, who)
         st = getattr(lib, "irec_rec_decode_files_device" + suffix)(
-            blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, layout.R, blocks, max_K, *tb, hdr.data_ptr(),
+            blob.data_ptr() if blob.numel() else ws.data_ptr(), offsets.data_ptr(), n, layout.R, *blocks, max_K, *tb, hdr.data_ptr(),
             K.data_ptr(), idx.data_ptr() if idx.numel() else None, status.data_ptr(), ws.data_ptr(), ws.numel(),
             torch.cuda.current_stream().cuda_stream)
     _files.check_status(st, "irec_rec_decode_files_device" + suffix)
@@ -414,8 +472,7 @@ def _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, ma
     layout = _Layout.ragged(blocks_per_res, "encode_files_device_ragged")
     if not (K.is_cuda and idx.is_cuda and K.dtype == torch.int32 and idx.dtype == torch.int32):
         raise ValueError("encode_files_device_ragged takes CUDA int32 tensors")
-    if K.dim() != 2 or K.shape[1] != layout.T or idx.dim() != 3 or tuple(idx.shape[:2]) != tuple(K.shape):
-        raise ValueError(f"encode_files_device_ragged: K {tuple(K.shape)} and idx {tuple(idx.shape)} are not [N, {layout.T}] and [N, {layout.T}, max_K]")
+    _check_rows(K, idx, layout, "encode_files_device_ragged")
     return _encode_rows_device_launch(seed, image_shape, block_size, K, idx, max_index, layout, out, tables, "encode_files_device_ragged")
 
 
@@ -445,12 +502,6 @@ def _device_out(out, first_cap, dev, who):
     return out
 
 
-def _first_cap(n, layout, max_K):
-    """irec_io.cpp's own first allowance: 64 + 40 bits per symbol and terminator, per stream."""
-    b = layout.bpr.astype(np.int64)
-    return n * (28 + 16 * layout.R + int(((64 + 40 * (b + 1)) // 8 + 1 + (64 + 40 * (b * max_K + 1)) // 8 + 1).sum()))
-
-
 def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=None, tables=None):
     """encode_files on the device (irec_rec_encode_files_device): K [N, R, bpt], idx [N, R, bpt, max_K] int32 CUDA tensors, contiguous
     or views of one joined [rows][1 + width] tensor (PendingCode.gather_packed_device).  Returns (blob uint8, offsets int64 [N + 1]) as
@@ -464,7 +515,7 @@ def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=No
     n, r, bpt = K.shape
     if tables is not None:                             # (R <= IREC_REC_RAGGED_MAX_RES: the entry point with tables takes the ragged layout)
         return encode_files_device_ragged(seed, image_shape, block_size, *_block_rows(K, idx), max_index, [bpt] * r, out, tables=tables)
-    out = _device_out(out, lambda: _first_cap(n, _Layout(r, bpt), idx.shape[3]), K.device, "encode_files_device")
+    out = _device_out(out, lambda: _Layout(r, bpt).first_cap(n, idx.shape[3]), K.device, "encode_files_device")
     return _files.encode_device(lambda o: _encode_files_device_launch(seed, image_shape, block_size, K, idx, max_index, o), n, out,
                                 _rec_status_text, "irec_rec_encode_files_device")
 
@@ -490,7 +541,7 @@ def encode_files_device_ragged(seed, image_shape, block_size, K, idx, max_index,
     and status.  out: a CUDA uint8 buffer to write into (a short one costs a second run at the size the first one reports)."""
     layout = _Layout.ragged(blocks_per_res, "encode_files_device_ragged")
     n, max_K = (K.shape[0], idx.shape[2]) if K.dim() == 2 and idx.dim() == 3 else (0, 0)
-    out = _device_out(out, lambda: _first_cap(n, layout, max_K), K.device, "encode_files_device_ragged")
+    out = _device_out(out, lambda: layout.first_cap(n, max_K), K.device, "encode_files_device_ragged")
     return _files.encode_device(lambda o: _encode_files_device_ragged_launch(seed, image_shape, block_size, K, idx, max_index, layout, o, tables),
                                 K.shape[0], out, _rec_status_text, "irec_rec_encode_files_device_ragged")
 
@@ -538,6 +589,11 @@ def rec_files_max_K(blob, offsets, tables=None):
     if tables is not None and tables.max_K is not None:
         need = max(need, tables.max_K)                 # (a file coded under count tables says 0xFFFFFFFF: the bound is the tables')
     return need
+
+
+def rec_files_max_K_device(blob, offsets, n_res_blocks, tables=None):
+    """rec_files_max_K for a blob on the device: only the 28 + 16 R header bytes of every file are gathered and copied to the host."""
+    return rec_files_max_K(*_files.gather_heads(blob, offsets, _STATIC.size + 16 * int(n_res_blocks)), tables)
 
 
 def write_compressed_code(file_path, seed, image_shape, block_size, block_indices, max_index,

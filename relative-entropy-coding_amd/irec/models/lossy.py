@@ -13,11 +13,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import _lib
 from ..coding.pending import PendingCode, recode
-from ..coding.utils import CodingError
 from ..io import read_compressed_code, write_compressed_code
-from .resnet_vae import STATUS_HEADER, STATUS_ROWS, STATUS_TABLE, ModelError, segmented_rows, _Normal, _nchw, _nhwc, deterministic_transforms, status_text
+from ._rec_rows import STATUS_ROWS, finish, header_want, join_status, packed_rows, read_rows
+from .resnet_vae import ModelError, _Normal, _nchw, _nhwc, deterministic_transforms
 
 
 def _down(cin, cout, n):
@@ -53,7 +52,6 @@ class Large2LevelVAE(nn.Module):
         self._prior_log_scale_head = nn.Conv2d(f2, f2, 3, padding=1)
         self._level_1_posterior_loc_combiner = nn.Conv2d(2 * f1, f1, 1)
         self._level_1_posterior_log_scale_combiner = nn.Conv2d(2 * f1, f1, 1)
-        self._rows_cache = {}
 
     def prior_base(self, batch_size, height, width):
         """large_2_level_vae.py:312-313."""
@@ -184,18 +182,6 @@ class Large2LevelVAE(nn.Module):
             blob, offsets = encode(seed, (height, width, 3), block_size, K, idx, self._max_index(sampler), bpr, tables=tables)
         return ((blob, offsets, reconstruction), (K, idx, bpr)) if return_pendings else (blob, offsets, reconstruction)
 
-    def _packed_rows(self, n, bpr, device):
-        """Per level r the int32 device map (image i, block j) -> row i T + first[r] + j of packed K [N, T] arrays."""
-        key = (n, tuple(bpr), str(device))
-        if key not in self._rows_cache:
-            if len(self._rows_cache) > 16:
-                self._rows_cache.clear()
-            T, first = sum(bpr), np.concatenate([[0], np.cumsum(bpr)])
-            i = torch.arange(n, dtype=torch.int32).reshape(n, 1)
-            self._rows_cache[key] = [(i * T + int(first[r]) + torch.arange(b, dtype=torch.int32).reshape(1, b)).reshape(-1).contiguous().to(device)
-                                     for r, b in enumerate(bpr)]
-        return self._rows_cache[key]
-
     def _decompress_device(self, K, idx, seed, image_shape, sampler, status):
         """The generative pass driven by rows on the device: K [N, T], idx [N, T, max_K] int32 (contiguous, or the views of one joined
         tensor), each level's coder reading its rows in place and accumulating its verdict on them into `status` (int32 [N], device).
@@ -205,7 +191,7 @@ class Large2LevelVAE(nn.Module):
         if K.dim() != 2 or tuple(K.shape) != (n, sum(bpr)) or idx.dim() != 3 or tuple(idx.shape[:2]) != tuple(K.shape):
             raise ModelError(f"K {tuple(K.shape)} / idx {tuple(idx.shape)} are not [N = {n}, T = {sum(bpr)}] and [N, T, max_K]: images of shape "
                              f"{tuple(image_shape)} are coded in {bpr} blocks")
-        rows = self._packed_rows(n, bpr, K.device)
+        rows = packed_rows(n, bpr, K.device)
         with deterministic_transforms():
             l2_prior_loc, l2_prior_scale = self._level_2_prior(n, height, width)
             self.level_2_prior = _Normal(_nhwc(l2_prior_loc), _nhwc(l2_prior_scale))
@@ -214,13 +200,6 @@ class Large2LevelVAE(nn.Module):
             self.level_1_prior = _Normal(_nhwc(l1_prior_loc), _nhwc(l1_prior_scale))
             y = sampler.decode(self.level_1_prior, None, seed=seed, batched=True, packed=(K, idx, rows[1]), status=status)
             return self.synthesis_transform(_nchw(y))
-
-    @staticmethod
-    def _raise_status(status):
-        """CodingError for the first image with a nonzero joined status (BidirectionalResNetVAE.decompress_rec has the encoding)."""
-        bad = np.flatnonzero(status)
-        if bad.size:
-            raise CodingError(f"{status_text(int(status[bad[0]]))} (image {int(bad[0])})")
 
     @staticmethod
     def _to_device(a, device):
@@ -237,52 +216,7 @@ class Large2LevelVAE(nn.Module):
         status = torch.zeros(int(image_shape[0]), dtype=torch.int32, device=device)
         reconstruction = self._decompress_device(K, idx, seed, image_shape, sampler, status)
         host = status.cpu().numpy()
-        host = np.where(host != 0, host + STATUS_ROWS, 0).astype(np.int32)
-        if strict:
-            self._raise_status(host)
-            return reconstruction
-        return reconstruction, host
-
-    @staticmethod
-    def _decode_files_host(blob, offsets, bpr, max_K, tables=None):
-        """irec.io.decode_files_ragged with a verdict per file: (headers, K, idx, status int32 [N]).  The host reader stops at the first
-        file it refuses; only then is every file read alone, a refused one leaving zero rows and the irec_rec_status of the reader's
-        words for it (the first of a class that shares its text)."""
-        from ..io.utils import _REC_STATUS_TEXT, _decode_files_tables_status, decode_files_ragged
-        n = len(offsets) - 1
-        if tables is not None:                          # (the reader with tables gives a verdict per file itself)
-            return _decode_files_tables_status(blob, offsets, bpr, max_K, tables)
-        try:
-            hdr, K, idx = decode_files_ragged(blob, offsets, bpr, max_K)
-            return hdr, K, idx, np.zeros(n, dtype=np.int32)
-        except ValueError:
-            pass
-        hdr, K, idx = np.zeros((n, 9), np.uint32), np.zeros((n, sum(bpr)), np.int32), np.zeros((n, sum(bpr), max_K), np.int32)
-        status = np.zeros(n, dtype=np.int32)
-        for i in range(n):
-            one = blob[int(offsets[i]):int(offsets[i + 1])]
-            try:
-                hdr[i], K[i], idx[i] = (a[0] for a in decode_files_ragged(one if one.size else np.zeros(1, np.uint8), np.array([0, one.size]), bpr,
-                                                                         max_K, n_threads=1))
-            except ValueError as e:
-                text = str(e).rsplit(" (image", 1)[0]
-                status[i] = next((code for code, t in sorted(_REC_STATUS_TEXT.items()) if t == text and code >= 4), 16)
-        return hdr, K, idx, status
-
-    @staticmethod
-    def _files_max_K_device(blob, offsets, R=2, tables=None):
-        """Index slots per block that decode the files of a blob on the device (irec.io.rec_files_max_K): only the 28 + 16 R header bytes
-        of every file are gathered and copied to the host."""
-        from ..io.utils import rec_files_max_K
-        dev, hb = blob.device, 28 + 16 * R
-        off = offsets.to(dev) if hasattr(offsets, "is_cuda") else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev)
-        n = off.numel() - 1
-        if n < 1 or blob.numel() < 1:
-            return rec_files_max_K(np.zeros(0, np.uint8), np.zeros(1, np.int64), tables)
-        at = (off[:-1, None] + torch.arange(hb, device=dev)).clamp_(0, blob.numel() - 1)
-        whole = (off[1:] - off[:-1] >= hb) & (off[:-1] >= 0) & (off[1:] <= blob.numel())          # a shorter file: a zero header, no words
-        head = blob.reshape(-1)[at] * whole[:, None].to(torch.uint8)
-        return rec_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb, tables)
+        return finish(reconstruction, np.where(host != 0, host + STATUS_ROWS, 0).astype(np.int32), strict)
 
     @torch.no_grad()
     def decompress_rec(self, blob, offsets, seed, image_shape, sampler, max_K=None, strict=True, rec_on_device=False, tables=None,
@@ -302,44 +236,16 @@ class Large2LevelVAE(nn.Module):
         the largest max_part word of their directories).  The segmented reader's own causes (irec_rec_status 20 .. 22: magic or
         version, directory, segment size) are STATUS_SEGMENTED + 0 .. 2 in the joined status; a plain file read as a segmented one has
         the first of them, and a segmented file read without segment_blocks has status 5."""
-        from ..io.utils import _decode_files_device_ragged_launch, rec_files_max_K
         n, _, height, width = image_shape
         bpr = self.blocks_per_res(image_shape, sampler.block_size)
         device = self._prior_base.device
-        if segment_blocks is not None:
-            if tables is not None:
-                raise ValueError("decompress_rec: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
-            hdr, K, idx, rec_status = segmented_rows(blob, offsets, bpr, segment_blocks, max_K, rec_on_device, device)
-            words = hdr.to(torch.int64).bitwise_and_(0xFFFFFFFF)
-        elif rec_on_device:
-            if max_K is None:
-                max_K = self._files_max_K_device(blob, offsets, tables=tables)
-            hdr, K, idx, rec_status = _decode_files_device_ragged_launch(blob, offsets, bpr, int(max_K), on_device=True, tables=tables)
-            words = hdr.to(torch.int64).bitwise_and_(0xFFFFFFFF)
-        else:
-            blob_h = np.ascontiguousarray(blob.cpu().numpy() if hasattr(blob, "cpu") else blob, dtype=np.uint8)
-            off_h = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
-            if max_K is None:
-                max_K = rec_files_max_K(blob_h, off_h, tables)
-            hdr, K, idx, rec_status = self._decode_files_host(blob_h, off_h, bpr, int(max_K), tables)
-            both = np.concatenate([K[..., None], idx], axis=2)                                    # one upload for the rows
-            both = torch.from_numpy(both).to(device)
-            K, idx = both[..., 0], both[..., 1:]
-            words = torch.from_numpy(hdr.astype(np.int64)).to(device)
-            rec_status = torch.from_numpy(rec_status).to(device)
-        if tables is not None:
-            rec_status = torch.where(rec_status == _lib.IREC_REC_E_TABLE, torch.full_like(rec_status, STATUS_TABLE), rec_status)
+        if segment_blocks is not None and tables is not None:
+            raise ValueError("decompress_rec: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
+        words, K, idx, rec_status = read_rows(blob, offsets, bpr, max_K, rec_on_device=rec_on_device, tables=tables, segment_blocks=segment_blocks,
+                                              device=device)
         if len(rec_status) != n:
             raise ModelError(f"{len(rec_status)} files for images of shape {tuple(image_shape)}")
-        want = torch.tensor([int(seed) & 0xFFFFFFFF, int(height), int(width), 3, 2], dtype=torch.int64).to(device)
-        differs = (torch.cat([words[:, 0:1], words[:, 3:6], words[:, 8:9]], dim=1) != want).any(dim=1)   # seed, height, width, channels, R
         rows_status = torch.zeros(n, dtype=torch.int32, device=device)
         reconstruction = self._decompress_device(K, idx, seed, image_shape, sampler, rows_status)
-        joined = torch.where(rec_status != 0, rec_status,
-                             torch.where(differs, torch.full_like(rec_status, STATUS_HEADER),
-                                         torch.where(rows_status != 0, rows_status + STATUS_ROWS, rows_status)))
-        host = joined.cpu().numpy()
-        if strict:
-            self._raise_status(host)
-            return reconstruction
-        return reconstruction, host
+        joined = join_status(rec_status, words, header_want(seed, (n, 3, height, width), 2, device), rows_status)
+        return finish(reconstruction, joined.cpu().numpy(), strict)

@@ -20,64 +20,12 @@ from .. import _lib
 from ..coding import BeamSearchCoder, CodingError, GaussianCoder, ImportanceSampler
 from ..coding.beam_search_coder import MorePartitionsNeeded, PendingCode, SplitNotResident
 from ..coding.pending import recode
+from ._rec_rows import STATUS_HEADER, STATUS_SEGMENTED, STATUS_TABLE  # noqa: F401  (the joined status's names are read from this module)
+from ._rec_rows import STATUS_RESIDUAL, STATUS_ROWS, finish, header_want, join_status, packed_rows, raise_status, read_rows, status_text
 
 
 class ModelError(Exception):
     """rec/models/resnet_vae.py (ModelError)."""
-
-
-# the joined per-image status of decompress_rec / decompress_packed beside irec_rec_status (1 .. 18)
-STATUS_HEADER = 19      # the file's seed, height, width, channels or R differ from the call's
-STATUS_TABLE = 20       # IREC_REC_E_TABLE (19 on the wire, which STATUS_HEADER has here): a symbol table that cannot be coded under
-STATUS_SEGMENTED = 21   # + (irec_rec_status - 20): IREC_REC_E_SEG_MAGIC, _SEG_DIRECTORY, _SEG_BLOCKS (20 .. 22 on the wire) as 21 .. 23
-STATUS_ROWS = 32        # + irec_rows_status (1 K_RANGE, 2 INDEX_RANGE, 3 RATIO_TABLE)
-STATUS_RESIDUAL = 48    # + irec_res_status (decompress_lossless: the .res file of an image whose .rec file decoded)
-
-
-def segmented_rows(blob, offsets, blocks_per_res, segment_blocks, max_K, rec_on_device, device):
-    """The rows of N segmented files (NAME.recs) on `device`, for the models' decompress_rec: (headers [N, 9] int32 holding the uint32
-    words, K [N, T], idx [N, T, max_K], status int32 [N]).  rec_on_device: blob is a CUDA tensor and nothing but the directories (for
-    max_K None) is copied to the host -- irec.io's launch form of the device reader; otherwise the files are read on host threads and
-    the rows uploaded once.  The status is irec_rec_status with the segmented reader's own causes moved to STATUS_SEGMENTED + 0 .. 2."""
-    from ..io import segmented as SG
-    if rec_on_device:
-        if max_K is None:
-            max_K = SG.segmented_files_max_K_device(blob, offsets, blocks_per_res, segment_blocks)
-        hdr, K, idx, status = SG._decode_files_device_segmented_launch(blob, offsets, blocks_per_res, segment_blocks, int(max_K), on_device=True)
-    else:
-        blob_h = np.ascontiguousarray(blob.cpu().numpy() if hasattr(blob, "cpu") else blob, dtype=np.uint8)
-        off_h = np.ascontiguousarray(offsets.cpu().numpy() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
-        if max_K is None:
-            max_K = SG.segmented_files_max_K(blob_h, off_h)
-        hdr, K, idx, status = SG._decode_files_segmented_status(blob_h, off_h, blocks_per_res, segment_blocks, int(max_K))
-        both = torch.from_numpy(np.concatenate([K[..., None], idx], axis=2)).to(device)           # one upload for the rows
-        K, idx = both[..., 0], both[..., 1:]
-        hdr, status = torch.from_numpy(hdr.view(np.int32)).to(device), torch.from_numpy(status).to(device)
-    moved = status + (STATUS_SEGMENTED - _lib.IREC_REC_E_SEG_MAGIC)
-    return hdr, K, idx, torch.where(status >= _lib.IREC_REC_E_SEG_MAGIC, moved, status)
-
-
-def status_text(status, table_length=None, requested=None):
-    """The coder's text for a joined status.  A count beyond the fitted ratio table gets the reference's message when the table's
-    length and the count that was asked for are known."""
-    from ..coding.coder import RATIO_TABLE_TEXT
-    from ..io.residual import res_status_text
-    from ..io.utils import _REC_STATUS_TEXT
-    status = int(status)
-    if status > STATUS_RESIDUAL:
-        return res_status_text(status - STATUS_RESIDUAL)
-    if status == STATUS_ROWS + _lib.IREC_ROWS_E_RATIO_TABLE:
-        if table_length is not None and requested is not None:
-            return RATIO_TABLE_TEXT.format(table_length, requested)
-        return RATIO_TABLE_TEXT.split(".")[0] + "."
-    if STATUS_SEGMENTED <= status <= STATUS_SEGMENTED + 2:
-        from ..io.segmented import seg_status_text
-        return seg_status_text(status - STATUS_SEGMENTED + _lib.IREC_REC_E_SEG_MAGIC)
-    own = {STATUS_HEADER: "decompress_rec: the file's header (seed, image shape, residual blocks) differs from the arguments",
-           STATUS_TABLE: _REC_STATUS_TEXT[_lib.IREC_REC_E_TABLE],
-           STATUS_ROWS + _lib.IREC_ROWS_E_K_RANGE: "partition count out of range [min_K, max_K]",
-           STATUS_ROWS + _lib.IREC_ROWS_E_INDEX_RANGE: "index out of range [0, n_samples)"}
-    return own.get(status) or _REC_STATUS_TEXT.get(status, f"irec_rec: status {status}")
 
 
 class deterministic_transforms:
@@ -388,7 +336,6 @@ class BidirectionalResNetVAE(nn.Module):
                                        kl_per_partition=kl_per_partition, name=f"resnet_block_{res_block_idx}")
             for res_block_idx in range(num_res_blocks)])
         self._generative_base = nn.Parameter(torch.zeros(deterministic_filters))
-        self._packed_rows_cache, self._header_want_cache = {}, {}   # device constants of the packed decompress path, per batch shape
         # resnet_vae.py:581: the log of the discretized-logistic likelihood's one scale (the .res coder's model, compress_lossless).
         # Created after every other parameter and without a random draw: no existing initialisation moves.
         self.likelihood_log_scale = nn.Parameter(torch.zeros(()))
@@ -523,29 +470,6 @@ class BidirectionalResNetVAE(nn.Module):
             return self._finish(tensor)
 
     # ---- the read side on the device: rows that never leave it, one read-back per batch -----------------------------------------
-    def _packed_rows(self, n, R, bpt, device):
-        """Per residual block r the int32 device map (image i, block j) -> row (i R + r) bpt + j of packed K [N, R, bpt] arrays."""
-        cache = self._packed_rows_cache
-        key = (n, R, bpt, str(device))
-        if key not in cache:
-            if len(cache) > 16:
-                cache.clear()
-            i = torch.arange(n, dtype=torch.int32).reshape(n, 1)
-            j = torch.arange(bpt, dtype=torch.int32).reshape(1, bpt)
-            cache[key] = [((i * R + r) * bpt + j).reshape(-1).contiguous().to(device) for r in range(R)]
-        return cache[key]
-
-    def _header_want(self, seed, image_shape, device):
-        """The header words (seed, height, width, channels, R) a file of this call must carry, int64 on the device."""
-        cache = self._header_want_cache
-        key = (int(seed), tuple(int(v) for v in image_shape[1:]), self.num_res_blocks, str(device))
-        if key not in cache:
-            if len(cache) > 16:
-                cache.clear()
-            _, c, h, w = image_shape
-            cache[key] = torch.tensor([int(seed) & 0xFFFFFFFF, int(h), int(w), int(c), self.num_res_blocks], dtype=torch.int64).to(device)
-        return cache[key]
-
     def blocks_per_tensor(self, image_shape):
         """Coder blocks per residual block and image (Coder.split, coder.py:69-83) for images of this shape."""
         _, _, h, w = image_shape
@@ -564,7 +488,7 @@ class BidirectionalResNetVAE(nn.Module):
             raise ModelError(f"K {tuple(K.shape)} / idx {tuple(idx.shape)} are not [N = {batch_size}, R = {self.num_res_blocks}, bpt] and [N, R, bpt, max_K]")
         if bpt != self.blocks_per_tensor(image_shape):
             raise ModelError(f"{bpt} blocks per residual block, but images of shape {tuple(image_shape)} are coded in {self.blocks_per_tensor(image_shape)}")
-        rows = self._packed_rows(n, R, bpt, K.device)
+        rows = packed_rows(n, [bpt] * R, K.device)
         with deterministic_transforms():
             tensor = self.generative_base(batch_size=batch_size, width=width, height=height)
             for r, resnet_block in enumerate(self.residual_blocks):
@@ -590,10 +514,10 @@ class BidirectionalResNetVAE(nn.Module):
 
     def _raise_status(self, status, K=None):
         """CodingError for the first image with a nonzero joined status (decompress_rec has the encoding), "(image i)" appended."""
-        bad = np.flatnonzero(status)
-        if bad.size:
-            i = int(bad[0])
-            raise CodingError(f"{self.status_text(status[i], None if K is None else K[i])} (image {i})")
+        raise_status(status, lambda i, st: self.status_text(st, None if K is None else K[i]))
+
+    def _finish_status(self, result, host, K, strict):
+        return finish(result, host, strict, lambda status: self._raise_status(status, K))
 
     @torch.no_grad()
     def decompress_packed(self, K, idx, seed, image_shape, strict=True):
@@ -604,58 +528,31 @@ class BidirectionalResNetVAE(nn.Module):
         status = torch.zeros(int(image_shape[0]), dtype=torch.int32, device=K.device)
         reconstruction = self._decompress_device(K, idx, seed, image_shape, status)
         host = status.cpu().numpy()
-        host = np.where(host != 0, host + STATUS_ROWS, 0).astype(np.int32)
-        if strict:
-            self._raise_status(host, K)
-            return reconstruction
-        return reconstruction, host
+        return self._finish_status(reconstruction, np.where(host != 0, host + STATUS_ROWS, 0).astype(np.int32), K, strict)
 
     def _decompress_rec_device(self, blob, offsets, seed, image_shape, max_K, tables=None, segment_blocks=None):
         """Everything of decompress_rec that runs on the device: the three launches of the .rec reader, the header check, the pass,
-        the joined status.  Returns (reconstruction, status int32 [N] on the device, K).  No host synchronisation."""
-        from ..io.utils import _decode_files_device_launch
+        the joined status.  Returns (reconstruction, status int32 [N] on the device, K).  No host synchronisation when max_K is given."""
+        from ..io.utils import _Layout
         n, R, bpt = int(image_shape[0]), self.num_res_blocks, self.blocks_per_tensor(image_shape)
-        if segment_blocks is not None:
-            hdr, K, idx, rec_status = segmented_rows(blob, offsets, [bpt] * R, segment_blocks, max_K, True, blob.device)
-            K, idx = K.view(n, R, bpt), idx.view(n, R, bpt, max_K)
-        else:
-            hdr, K, idx, rec_status = _decode_files_device_launch(blob, offsets, R, bpt, max_K, on_device=True, tables=tables)
-        if tables is not None:
-            rec_status = torch.where(rec_status == _lib.IREC_REC_E_TABLE, torch.full_like(rec_status, STATUS_TABLE), rec_status)
-        words = hdr.to(torch.int64).bitwise_and_(0xFFFFFFFF)
-        words = torch.cat([words[:, 0:1], words[:, 3:6], words[:, 8:9]], dim=1)      # seed, height, width, channels, R
-        differs = (words != self._header_want(seed, image_shape, K.device)).any(dim=1)
+        layout = _Layout(R, bpt) if tables is None and segment_blocks is None else [bpt] * R     # (one count: the reader of any R)
+        words, K, idx, rec_status = read_rows(blob, offsets, layout, max_K, rec_on_device=True, tables=tables, segment_blocks=segment_blocks)
+        K, idx = K.view(K.shape[0], R, bpt), idx.view(K.shape[0], R, bpt, idx.shape[2])
         rows_status = torch.zeros(n, dtype=torch.int32, device=K.device)
         reconstruction = self._decompress_device(K, idx, seed, image_shape, rows_status)
-        joined = torch.where(rec_status != 0, rec_status,
-                             torch.where(differs, torch.full_like(rec_status, STATUS_HEADER),
-                                         torch.where(rows_status != 0, rows_status + STATUS_ROWS, rows_status)))
-        return reconstruction, joined, K
+        return reconstruction, join_status(rec_status, words, header_want(seed, image_shape, R, K.device), rows_status), K
 
     def files_max_K(self, blob, offsets, tables=None):
         """Index slots per block that decode the files of a blob on the device: the largest max_partitions word of their headers
         (irec.io.rec_files_max_K; with count tables, those tables' largest K).  Only the 28 + 16 R header bytes of every file are
         gathered and copied to the host."""
-        from ..io.utils import rec_files_max_K
-        dev, hb = blob.device, 28 + 16 * self.num_res_blocks
-        off = offsets.to(dev) if hasattr(offsets, "is_cuda") else torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev)
-        n = off.numel() - 1
-        if n < 1 or blob.numel() < 1:
-            return rec_files_max_K(np.zeros(0, np.uint8), np.zeros(1, np.int64), tables)
-        at = (off[:-1, None] + torch.arange(hb, device=dev)).clamp_(0, blob.numel() - 1)
-        whole = (off[1:] - off[:-1] >= hb) & (off[:-1] >= 0) & (off[1:] <= blob.numel())          # a shorter file: a zero header, no words
-        head = blob.reshape(-1)[at] * whole[:, None].to(torch.uint8)
-        return rec_files_max_K(head.cpu().numpy().reshape(-1), np.arange(n + 1, dtype=np.int64) * hb, tables)
+        from ..io.utils import rec_files_max_K_device
+        return rec_files_max_K_device(blob, offsets, self.num_res_blocks, tables)
 
     @torch.no_grad()
     def _decompress_rec_status(self, blob, offsets, seed, image_shape, max_K=None, tables=None, segment_blocks=None):
         """decompress_rec up to its read-back: (reconstruction, status int32 numpy [N], K on the device)."""
-        if max_K is None and segment_blocks is not None:
-            from ..io.segmented import segmented_files_max_K_device
-            max_K = segmented_files_max_K_device(blob, offsets, [self.blocks_per_tensor(image_shape)] * self.num_res_blocks, segment_blocks)
-        elif max_K is None:
-            max_K = self.files_max_K(blob, offsets, tables)
-        reconstruction, joined, K = self._decompress_rec_device(blob, offsets, seed, image_shape, int(max_K), tables, segment_blocks)
+        reconstruction, joined, K = self._decompress_rec_device(blob, offsets, seed, image_shape, max_K, tables, segment_blocks)
         return reconstruction, joined.cpu().numpy(), K
 
     @torch.no_grad()
@@ -673,10 +570,7 @@ class BidirectionalResNetVAE(nn.Module):
         has the bytes on the host already (harness.decompress_images) spares by passing max_K.
         A file written under count tables (compress_rec(tables=)) has status 5 here: decompress_rec_tables reads it."""
         reconstruction, host, K = self._decompress_rec_status(blob, offsets, seed, image_shape, max_K)
-        if strict:
-            self._raise_status(host, K)
-            return reconstruction
-        return reconstruction, host
+        return self._finish_status(reconstruction, host, K, strict)
 
     @torch.no_grad()
     def decompress_rec_tables(self, blob, offsets, seed, image_shape, tables, max_K=None, strict=True):
@@ -685,10 +579,7 @@ class BidirectionalResNetVAE(nn.Module):
         call's table, or has status 5 (IREC_REC_E_COUNT_FILES) if the call brought none; a file without flags decodes under the
         default models, so one call reads both sorts.  max_K None: the largest of the headers' words and the count tables' K."""
         reconstruction, host, K = self._decompress_rec_status(blob, offsets, seed, image_shape, max_K, tables)
-        if strict:
-            self._raise_status(host, K)
-            return reconstruction
-        return reconstruction, host
+        return self._finish_status(reconstruction, host, K, strict)
 
     @torch.no_grad()
     def decompress_rec_segmented(self, blob, offsets, seed, image_shape, segment_blocks=None, max_K=None, strict=True):
@@ -703,10 +594,7 @@ class BidirectionalResNetVAE(nn.Module):
             if not segment_blocks:
                 raise CodingError("decompress_rec_segmented: the first file is not a segmented file (no magic, or segment_blocks 0)")
         reconstruction, host, K = self._decompress_rec_status(blob, offsets, seed, image_shape, max_K, None, segment_blocks)
-        if strict:
-            self._raise_status(host, K)
-            return reconstruction
-        return reconstruction, host
+        return self._finish_status(reconstruction, host, K, strict)
 
     # ---- the lossless pair: .rec (the latents' indices) + .res (the pixels under the likelihood given the reconstruction) ----------
     def likelihood_scale(self):
@@ -749,7 +637,7 @@ class BidirectionalResNetVAE(nn.Module):
     def _decompress_lossless_device(self, rec_blob, rec_offsets, res_blob, res_offsets, seed, image_shape, max_K, stream_len):
         """Everything of decompress_lossless that runs on the device, on one stream: _decompress_rec_device, the three launches of the
         .res reader on its reconstruction, the joined status, refused images zeroed.  Returns (pixels uint8, status int32 [N], K) on
-        the device.  No host synchronisation."""
+        the device.  No host synchronisation when max_K is given."""
         from ..io.residual import _decode_residuals_device_launch
         reconstruction, joined, K = self._decompress_rec_device(rec_blob, rec_offsets, seed, image_shape, max_K)
         pixels, res_status = _decode_residuals_device_launch(res_blob, res_offsets, reconstruction, self.likelihood_scale(), stream_len,
@@ -763,14 +651,11 @@ class BidirectionalResNetVAE(nn.Module):
     def _decompress_lossless_status(self, rec_blob, rec_offsets, res_blob, res_offsets, seed, image_shape, max_K=None, stream_len=None):
         """decompress_lossless up to its read-back: (pixels, status int32 numpy [N], K on the device)."""
         from ..io.residual import MAX_STREAM_LEN, _stream_len_device
-        if max_K is None:
-            max_K = self.files_max_K(rec_blob, rec_offsets)
         if stream_len is None:
             off = res_offsets.cpu().numpy() if hasattr(res_offsets, "cpu") else np.asarray(res_offsets)
             stream_len = _stream_len_device(res_blob, off[:2])
             stream_len = stream_len if stream_len and 1 <= stream_len <= MAX_STREAM_LEN else None   # (a damaged word: the default, and a status)
-        pixels, joined, K = self._decompress_lossless_device(rec_blob, rec_offsets, res_blob, res_offsets, seed, image_shape, int(max_K),
-                                                             stream_len)
+        pixels, joined, K = self._decompress_lossless_device(rec_blob, rec_offsets, res_blob, res_offsets, seed, image_shape, max_K, stream_len)
         return pixels, joined.cpu().numpy(), K
 
     @torch.no_grad()
@@ -785,10 +670,7 @@ class BidirectionalResNetVAE(nn.Module):
         max_K None costs decompress_rec's small read-back of the .rec headers, stream_len None one of 12 bytes of the first .res
         header; a caller that knows them passes them."""
         pixels, host, K = self._decompress_lossless_status(rec_blob, rec_offsets, res_blob, res_offsets, seed, image_shape, max_K, stream_len)
-        if strict:
-            self._raise_status(host, K)
-            return pixels
-        return pixels, host
+        return self._finish_status(pixels, host, K, strict)
 
 
 class GraphedDecompress:
@@ -858,11 +740,7 @@ class GraphedDecompress:
         host = self.status.cpu().numpy()
         if (host == _lib.IREC_REC_E_MAX_K).any():
             return self._eager(blob, offsets, strict)
-        reconstruction = self.reconstruction.clone()
-        if strict:
-            self.model._raise_status(host, self.K)
-            return reconstruction
-        return reconstruction, host
+        return self.model._finish_status(self.reconstruction.clone(), host, self.K, strict)
 
 
 class GraphedCompress:

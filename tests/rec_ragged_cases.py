@@ -80,7 +80,7 @@ def first_allowance(n, bpr, mk):
 
 def joined(K, idx):
     """One [rows][1 + width] tensor, K in column 0 (what PendingCode.gather_packed_ragged builds on the device)."""
-    return np.ascontiguousarray(np.concatenate([K.reshape(-1, 1), idx.reshape(K.size, -1)], axis=1).astype(np.int32))
+    return np.ascontiguousarray(np.concatenate([K.reshape(-1, 1), idx.reshape(K.size, idx.shape[-1])], axis=1).astype(np.int32))
 
 
 def core_encode(K, idx, max_index, bpr, cap=None, strided=False, seed=SEED, shape=SHAPE, block_size=BLOCK_SIZE, expect=0):

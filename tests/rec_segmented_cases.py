@@ -19,8 +19,16 @@ SEED, SHAPE, BLOCK_SIZE = RC.SEED, RC.SHAPE, RC.BLOCK_SIZE
 E_SEG_MAGIC, E_SEG_DIRECTORY, E_SEG_BLOCKS = 20, 21, 22  # irec_rec_status of include/irec.h
 
 
+EDGES = (((1, 4), 0, 36, 0), ((3, 1, 5), 3, 36, 0))       # (structure, N, max_index, max_K) beside the grid: no images; no index slots
+
+
+def grid():
+    """[(blocks per residual block, N, max_index, max_K)]: every structure with its max_K at every N and max_index, then EDGES."""
+    return [(bpr, n, S, STRUCTURES[bpr]) for bpr in STRUCTURES for n in N_IMAGES for S in MAX_INDEX] + list(EDGES)
+
+
 def case_names():
-    return [f"{'_'.join(map(str, bpr))}-N{n}-S{S}" for bpr in STRUCTURES for n in N_IMAGES for S in MAX_INDEX]
+    return [f"{'_'.join(map(str, bpr))}-N{n}-S{S}" + ("" if mk == STRUCTURES[bpr] else f"-K{mk}") for bpr, n, S, mk in grid()]
 
 
 def irec_coder(model, message):
@@ -61,6 +69,8 @@ def rows_of(rng, bpr, mk, n, S, g):
     T = sum(bpr)
     K = rng.integers(0, mk + 1, (n, T)).astype(np.int32)
     idx = rng.integers(0, S, (n, T, mk)).astype(np.int32)
+    if n == 0:
+        return K, idx
     r, row, nb = [s for s in segments_of(bpr, g) if s[0] == len(bpr) - 1][0]
     free = np.ones((n, T), dtype=bool)
     if n * T > nb + 1:
@@ -76,8 +86,7 @@ def rows_of(rng, bpr, mk, n, S, g):
 @functools.lru_cache(maxsize=None)
 def case(which, g):
     """Case `which` of case_names() at segment size g with its expected files, read-only."""
-    bpr, n, S = [(bpr, n, S) for bpr in STRUCTURES for n in N_IMAGES for S in MAX_INDEX][which]
-    mk = STRUCTURES[bpr]
+    bpr, n, S, mk = grid()[which]
     K, idx = rows_of(np.random.default_rng(20260000 + 97 * which + g), bpr, mk, n, S, g)
     files = [file_of(K[i], idx[i], bpr, g, S) for i in range(n)]
     c = {"name": case_names()[which], "bpr": bpr, "g": g, "max_index": S, "K": K, "idx": idx, "files": files,
