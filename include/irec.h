@@ -723,6 +723,53 @@ irec_status irec_res_decode_files(const uint8_t *bytes, const int64_t *offsets, 
 irec_status irec_res_model_counts(int32_t m, float scale, uint32_t *cumulative /*[257]*/);
 irec_status irec_res_symbol_counts(const uint8_t *pixels, const float *loc, float scale, int64_t n, uint32_t *count /*[n]*/);
 
+/* One scale per channel: .res version 2.  The four "_scales" entry points take the arguments of the four above with
+ * scales [channels] (float32; a device pointer in the device forms) in place of scale, and keep their guarantees and their
+ * workspace (irec_res_device_workspace_bytes).  Symbol p of an image belongs to channel p / (height * width); a stream that crosses a
+ * channel boundary goes on under the next channel's scale; the model of a pixel given (m, s_c) is the same.  The file differs from
+ * version 1 in the version word (2) and in holding channels scale words where version 1 holds one (INTEGRATION.md has the offsets).
+ * Any channel's scale outside [2^-24, 2^24] or not finite: IREC_RES_E_SCALE for every image.  Any scale word that differs from the
+ * call's: IREC_RES_E_SCALE_WORD.  A version-1 file given to a "_scales" reader, or a version-2 file given to a reader above:
+ * IREC_RES_E_MAGIC. */
+irec_status irec_res_encode_files_device_scales(const uint8_t *pixels, const float *loc, const float *scales /*[channels]*/, int32_t n_images,
+                                                uint32_t height, uint32_t width, uint32_t channels, uint32_t stream_len, uint8_t *out,
+                                                int64_t cap, int64_t *offsets /*[n_images + 1]*/, int32_t *status /*[n_images]*/,
+                                                void *workspace, size_t workspace_bytes, void *hip_stream);
+irec_status irec_res_decode_files_device_scales(const uint8_t *bytes, const int64_t *offsets, const float *loc, const float *scales /*[channels]*/,
+                                                int32_t n_images, uint32_t height, uint32_t width, uint32_t channels, uint32_t stream_len,
+                                                uint8_t *pixels_out, int32_t *status, void *workspace, size_t workspace_bytes,
+                                                void *hip_stream);
+irec_status irec_res_encode_files_scales(const uint8_t *pixels, const float *loc, const float *scales /*[channels]*/, int32_t n_images,
+                                         uint32_t height, uint32_t width, uint32_t channels, uint32_t stream_len, uint8_t *out, int64_t cap,
+                                         int64_t *offsets, int32_t *status, int32_t n_threads);
+irec_status irec_res_decode_files_scales(const uint8_t *bytes, const int64_t *offsets, const float *loc, const float *scales /*[channels]*/,
+                                         int32_t n_images, uint32_t height, uint32_t width, uint32_t channels, uint32_t stream_len,
+                                         uint8_t *pixels_out, int32_t *status, int32_t n_threads);
+
+/* What a batch costs under candidate scales (csrc/irec_res_fit.hip over csrc/irec_res_fit_core.h): the quantity a fitter of the .res
+ * scale searches over.  pixels, loc [n][channels][height][width] as above; scales [channels][n_candidates] float32,
+ * 1 <= n_candidates <= IREC_RES_FIT_MAX_CANDIDATES; cost [IREC_RES_COST_ENTRIES] from irec_res_cost_table:
+ * cost[n] = rint((16 - log2 n) * 2^16) for n in 1 .. 65536, cost[0] = 0 (data: built once on the host, passed to both forms).
+ *   bits [n][channels][n_candidates] int64, written (not added): the sum over the pixels of image i, channel ch of
+ *        cost[C(x + 1) - C(x)] under scales[ch][k] -- the model's exact code length in units of 2^-16 bit; INT64_MAX for a candidate
+ *        outside [2^-24, 2^24] or not finite (no error)
+ *   skipped [n][channels] int64: the pixels left out of every sum because their loc is not finite
+ * Integer adds only: the result depends on no order, the device form equals the host form bit for bit, and an image's rows are the
+ * same alone or inside any batch.  The device form: device pointers (cost and scales too), asynchronous on hip_stream, no allocation,
+ * synchronisation, copy or atomic inside (two launches); it writes exactly bits, skipped and the workspace (8-byte aligned, at least
+ * irec_res_scale_bits_workspace_bytes, which is 0 for a shape the entries refuse).  Null pointers, a shape the .res entries refuse,
+ * n_candidates outside 1 .. 64: IREC_E_INVALID; a workspace smaller than sized: IREC_E_WORKSPACE; no launch either way. */
+#define IREC_RES_FIT_MAX_CANDIDATES 64
+#define IREC_RES_COST_ENTRIES 65537
+irec_status irec_res_cost_table(uint32_t *cost /*[IREC_RES_COST_ENTRIES]*/);
+size_t irec_res_scale_bits_workspace_bytes(int32_t n_images, uint32_t height, uint32_t width, uint32_t channels, int32_t n_candidates);
+irec_status irec_res_scale_bits_device(const uint8_t *pixels, const float *loc, const float *scales, const uint32_t *cost, int32_t n_images,
+                                       uint32_t height, uint32_t width, uint32_t channels, int32_t n_candidates, int64_t *bits,
+                                       int64_t *skipped, void *workspace, size_t workspace_bytes, void *hip_stream);
+irec_status irec_res_scale_bits(const uint8_t *pixels, const float *loc, const float *scales, const uint32_t *cost, int32_t n_images,
+                                uint32_t height, uint32_t width, uint32_t channels, int32_t n_candidates, int64_t *bits, int64_t *skipped,
+                                int32_t n_threads);
+
 /* Distortion of a batch (csrc/irec_quality.hip over csrc/irec_quality_core.h): what PSNR and MS-SSIM are made from, for a
  * (reconstruction) and b (original), float32 [n][c][h][w] each.  A pixel is v * mul + add, clamped to [0, max_val] where the image's
  * clip flag is set; MS-SSIM is tf.image.ssim_multiscale of TF 2.1 with filter_size 11 and filter_sigma 1.5 (INTEGRATION.md has the

@@ -9,6 +9,8 @@
 //            scan: offsets, status, stream positions, headers) -> res_write_kernel (streams; nothing at all if the files do not fit cap)
 //   decode:  res_decode_head_kernel (header checks, stream positions) -> res_decode_streams_kernel (pixels, checksum shares)
 //            -> res_decode_status_kernel (one status per image, first cause; the pixels of an image with an error zeroed)
+// The "_scales" entry points (one scale per channel, version-2 files) run the same launches through kernels of their own, compiled with
+// irec_res::ChannelScales where those above are compiled with irec_res::CallScale.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -93,6 +95,48 @@ __global__ __launch_bounds__(RES_NT) void res_decode_status_kernel(irec_res::Dec
     if (t == 0) c.status[i] = st;
     if (st) for (int64_t e = t; e < c.n_sym; e += RES_NT) c.pixels[i * c.n_sym + e] = 0;
   }
+}
+
+// ---- the same launches under one scale per channel (version 2; irec_res::ChannelScales, scales [channels] on the device): kernels of
+//      their own, so that the ones above stay the code they were ----------------------------------------------------------------------
+__global__ __launch_bounds__(RES_NT) void res_size_scales_kernel(irec_res::EncodeCall c, irec_res::ChannelScales sc) {
+  const int64_t lane = (int64_t)blockIdx.x * RES_NT + threadIdx.x;
+  if (lane < (int64_t)c.N * c.ns) irec_res::encode_size_lane(c, sc, lane);
+}
+
+__global__ __launch_bounds__(RES_NT) void res_layout_scales_kernel(irec_res::EncodeCall c, irec_res::ChannelScales sc) {
+  __shared__ int64_t part[RES_NT];
+  const int t = threadIdx.x;
+  const int64_t per = ((int64_t)c.N + RES_NT - 1) / RES_NT, lo = t * per, hi = lo + per < c.N ? lo + per : c.N;
+  int64_t sum = 0;
+  for (int64_t i = lo; i < hi; ++i) sum += irec_res::encode_image_bytes(c, sc, i);
+  part[t] = sum;
+  __syncthreads();
+  for (int d = 1; d < RES_NT; d *= 2) {
+    const int64_t add = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  const int64_t total = part[RES_NT - 1];
+  int64_t at = part[t] - sum;
+  for (int64_t i = lo; i < hi; ++i) { irec_res::encode_image_layout(c, sc, i, at, total <= c.cap); at += irec_res::encode_image_bytes(c, sc, i); }
+  if (t == RES_NT - 1) c.offsets[c.N] = total;
+}
+
+__global__ __launch_bounds__(RES_NT) void res_write_scales_kernel(irec_res::EncodeCall c, irec_res::ChannelScales sc) {
+  const int64_t lane = (int64_t)blockIdx.x * RES_NT + threadIdx.x;
+  if (lane < (int64_t)c.N * c.ns) irec_res::encode_write_lane(c, sc, lane);
+}
+
+__global__ __launch_bounds__(RES_NT) void res_decode_head_scales_kernel(irec_res::DecodeCall c, irec_res::ChannelScales sc) {
+  const int64_t lane = (int64_t)blockIdx.x * RES_NT + threadIdx.x;
+  if (lane < c.N) irec_res::decode_head_lane(c, sc, lane);
+}
+
+__global__ __launch_bounds__(RES_NT) void res_decode_streams_scales_kernel(irec_res::DecodeCall c, irec_res::ChannelScales sc) {
+  const int64_t lane = (int64_t)blockIdx.x * RES_NT + threadIdx.x;
+  if (lane < (int64_t)c.N * c.ns) irec_res::decode_stream_lane(c, sc, lane);
 }
 
 int res_grid(int64_t lanes) { const int64_t g = (lanes + RES_NT - 1) / RES_NT; return (int)(g < 1 ? 1 : g); }
@@ -205,6 +249,84 @@ irec_status irec_res_decode_files_device(const uint8_t *bytes, const int64_t *of
   RES_HIP(hipGetLastError());
   return IREC_OK;
 }
+
+// ---- one scale per channel: version-2 files (scales [channels]: a device pointer here, a host pointer in the host forms below) -------
+irec_status irec_res_encode_files_device_scales(const uint8_t *pixels, const float *loc, const float *scales, int32_t n_images,
+                                                uint32_t height, uint32_t width, uint32_t channels, uint32_t stream_len, uint8_t *out,
+                                                int64_t cap, int64_t *offsets, int32_t *status, void *workspace, size_t workspace_bytes,
+                                                void *hip_stream) {
+  using namespace irec;
+  irec_res::EncodeCall c;
+  if (!scales || !make_encode_call(c, pixels, loc, 0.0f, n_images, height, width, channels, stream_len, out, cap, offsets, status))
+    return set_last_error(IREC_E_INVALID, "irec_res_encode_files_device_scales", "bad arguments");
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < irec_res_device_workspace_bytes(n_images, c.ns))
+    return set_last_error(IREC_E_WORKSPACE, "irec_res_encode_files_device_scales", "workspace too small (irec_res_device_workspace_bytes) or not 8-byte aligned");
+  irec_res::encode_bind_workspace(c, workspace);
+  const irec_res::ChannelScales sc{scales, (int64_t)height * width};
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int64_t lanes = (int64_t)n_images * c.ns;
+  if (lanes > 0) {
+    hipLaunchKernelGGL(res_size_scales_kernel, dim3(res_grid(lanes)), dim3(RES_NT), 0, st, c, sc);
+    RES_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(res_layout_scales_kernel, dim3(1), dim3(RES_NT), 0, st, c, sc);
+  RES_HIP(hipGetLastError());
+  if (lanes > 0) {
+    hipLaunchKernelGGL(res_write_scales_kernel, dim3(res_grid(lanes)), dim3(RES_NT), 0, st, c, sc);
+    RES_HIP(hipGetLastError());
+  }
+  return IREC_OK;
+}
+
+irec_status irec_res_decode_files_device_scales(const uint8_t *bytes, const int64_t *offsets, const float *loc, const float *scales,
+                                                int32_t n_images, uint32_t height, uint32_t width, uint32_t channels, uint32_t stream_len,
+                                                uint8_t *pixels_out, int32_t *status, void *workspace, size_t workspace_bytes,
+                                                void *hip_stream) {
+  using namespace irec;
+  irec_res::DecodeCall c;
+  if (!scales || !make_decode_call(c, bytes, offsets, loc, 0.0f, n_images, height, width, channels, stream_len, pixels_out, status))
+    return set_last_error(IREC_E_INVALID, "irec_res_decode_files_device_scales", "bad arguments");
+  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < irec_res_device_workspace_bytes(n_images, c.ns))
+    return set_last_error(IREC_E_WORKSPACE, "irec_res_decode_files_device_scales", "workspace too small (irec_res_device_workspace_bytes) or not 8-byte aligned");
+  if (n_images == 0) return IREC_OK;
+  irec_res::decode_bind_workspace(c, workspace);
+  const irec_res::ChannelScales sc{scales, (int64_t)height * width};
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(res_decode_head_scales_kernel, dim3(res_grid(n_images)), dim3(RES_NT), 0, st, c, sc);
+  RES_HIP(hipGetLastError());
+  hipLaunchKernelGGL(res_decode_streams_scales_kernel, dim3(res_grid((int64_t)n_images * c.ns)), dim3(RES_NT), 0, st, c, sc);
+  RES_HIP(hipGetLastError());
+  hipLaunchKernelGGL(res_decode_status_kernel, dim3(n_images < 65536 ? n_images : 65536), dim3(RES_NT), 0, st, c);   // (no scale in it)
+  RES_HIP(hipGetLastError());
+  return IREC_OK;
+}
+
+irec_status irec_res_encode_files_scales(const uint8_t *pixels, const float *loc, const float *scales, int32_t n_images, uint32_t height,
+                                         uint32_t width, uint32_t channels, uint32_t stream_len, uint8_t *out, int64_t cap, int64_t *offsets,
+                                         int32_t *status, int32_t n_threads) try {
+  using namespace irec;
+  irec_res::EncodeCall c;
+  if (!scales || !make_encode_call(c, pixels, loc, 0.0f, n_images, height, width, channels, stream_len, out, cap, offsets, status))
+    return set_last_error(IREC_E_INVALID, "irec_res_encode_files_scales", "bad arguments");
+  std::vector<int64_t> ws((size_t)(irec_res::workspace_bytes(n_images, c.ns) / 8 + 1));
+  irec_res::encode_bind_workspace(c, ws.data());
+  irec_res::encode_call_host(c, irec_res::ChannelScales{scales, (int64_t)height * width}, ThreadedLanes{n_threads});
+  return IREC_OK;
+} catch (const std::exception &e) { return irec::set_last_error(IREC_E_INVALID, "irec_res_encode_files_scales", e.what()); }
+
+irec_status irec_res_decode_files_scales(const uint8_t *bytes, const int64_t *offsets, const float *loc, const float *scales, int32_t n_images,
+                                         uint32_t height, uint32_t width, uint32_t channels, uint32_t stream_len, uint8_t *pixels_out,
+                                         int32_t *status, int32_t n_threads) try {
+  using namespace irec;
+  irec_res::DecodeCall c;
+  if (!scales || !make_decode_call(c, bytes, offsets, loc, 0.0f, n_images, height, width, channels, stream_len, pixels_out, status))
+    return set_last_error(IREC_E_INVALID, "irec_res_decode_files_scales", "bad arguments");
+  if (n_images == 0) return IREC_OK;
+  std::vector<int64_t> ws((size_t)(irec_res::workspace_bytes(n_images, c.ns) / 8 + 1));
+  irec_res::decode_bind_workspace(c, ws.data());
+  irec_res::decode_call_host(c, irec_res::ChannelScales{scales, (int64_t)height * width}, ThreadedLanes{n_threads});
+  return IREC_OK;
+} catch (const std::exception &e) { return irec::set_last_error(IREC_E_INVALID, "irec_res_decode_files_scales", e.what()); }
 
 // ---- the same lane functions over host memory: the referee of the kernels above, and the path of host arrays ------------------------------
 irec_status irec_res_encode_files(const uint8_t *pixels, const float *loc, float scale, int32_t n_images, uint32_t height, uint32_t width,

@@ -16,6 +16,11 @@
 // Container, little-endian, fields at any alignment:
 //     0 magic 'IRES' u32 | 4 version u16 | 6 channels u16 | 8 stream_len u32 | 12 height u32 | 16 width u32 | 20 float32 bits of s u32 |
 //     24 checksum u32 | 28 n_streams x u16 byte length | the streams back to back
+// Version 2 (one scale per channel; the policy ChannelScales below) differs in the version word and in the scale words alone:
+//     0 .. 19 as above with version 2 | 20 + 4 c float32 bits of s_c u32, c < channels | 20 + 4 channels checksum u32 |
+//     24 + 4 channels n_streams x u16 byte length | the streams back to back
+// Symbol p of an image belongs to channel p / (height width); a stream that crosses a channel boundary goes on under the next
+// channel's inv = 1 / (4096 s_c) from the boundary's symbol on.  The model of a pixel given (m, s_c) is the one above.
 // Image i's symbols are its C H W bytes in tensor order; stream j covers [j L, min((j + 1) L, C H W)); lane i n_streams + j.
 // checksum = sum mod 2^32 over symbols of mix(((p << 8) | x) + 0x9E3779B9) with p the symbol's position and mix the 32-bit finalizer
 // below, a bijection: one wrong pixel always changes it, and being linear in neither p nor x it does not cancel over the +1 / -1
@@ -38,7 +43,7 @@ using irec_rec::put_u16;
 using irec_rec::get_u32;
 using irec_rec::get_u16;
 
-constexpr uint32_t MAGIC = 0x53455249u, VERSION = 1;   // "IRES"
+constexpr uint32_t MAGIC = 0x53455249u, VERSION = 1, VERSION_SCALES = 2;   // "IRES"
 constexpr int TOTAL_BITS = 16;
 constexpr uint32_t TOTAL = 1u << TOTAL_BITS, N_SYMBOLS = 256;
 constexpr int64_t HEADER_BYTES = 28, MAX_STREAM_LEN = 4096;
@@ -118,15 +123,55 @@ struct BitReader {
   IREC_REC_HD uint64_t bit(int64_t i) const { return i < n_bits ? (uint64_t)((p[i >> 3] >> (7 - (i & 7))) & 1) : 0; }
 };
 
+// ---- the scales of a call ---------------------------------------------------------------------------------------------------------
+// CallScale: the call's one scale (EncodeCall::scale, DecodeCall::scale) and version 1 -- what every entry point without "_scales" in
+// its name is compiled with, and nothing else: its stream walks under one constant inv.  ChannelScales: scales[channels], version 2.
+// A policy gives the header's size, writes and compares the scale words, and makes the cursor that a stream asks for the inv of each
+// of its symbols' positions, which are consecutive: the cursor of ChannelScales divides once per channel that the stream enters.
+struct FixedInv {
+  static constexpr bool fixed = true;
+  double inv;
+  IREC_REC_HD double at(int64_t) const { return inv; }
+};
+struct ChannelInv {
+  static constexpr bool fixed = false;
+  const float *scales; int64_t plane, next; double inv;
+  IREC_REC_HD double at(int64_t p) {
+    if (p >= next) { const int64_t ch = p / plane; inv = model_inv(scales[ch]); next = (ch + 1) * plane; }
+    return inv;
+  }
+};
+struct CallScale {
+  static constexpr bool per_channel = false;
+  static constexpr uint32_t version = VERSION;
+  IREC_REC_HD int64_t header_bytes(uint32_t) const { return HEADER_BYTES; }
+  IREC_REC_HD bool ok(float scale, uint32_t) const { return scale_ok(scale); }
+  IREC_REC_HD FixedInv cursor(float scale) const { return FixedInv{model_inv(scale)}; }
+};
+struct ChannelScales {
+  static constexpr bool per_channel = true;
+  static constexpr uint32_t version = VERSION_SCALES;
+  const float *scales; int64_t plane;                                             // [channels]; height * width
+  IREC_REC_HD int64_t header_bytes(uint32_t channels) const { return HEADER_BYTES + 4 * ((int64_t)channels - 1); }
+  IREC_REC_HD bool ok(float, uint32_t channels) const {
+    bool all = true;
+    for (uint32_t ch = 0; ch < channels; ++ch) all = all && scale_ok(scales[ch]);
+    return all;
+  }
+  IREC_REC_HD ChannelInv cursor(float) const { return ChannelInv{scales, plane, 0, 0.0}; }
+};
+
 // ---- one stream ---------------------------------------------------------------------------------------------------------------------
-// n symbols x[k] under m[k] = loc_to_m(loc[k]).  0, or IREC_RES_E_LOC for a loc that is not finite.  *share: the checksum terms.
-template <class Sink>
-IREC_REC_HD inline int32_t encode_stream(const uint8_t *x, const float *loc, double inv, int64_t p0, int64_t n, Sink &sink, uint32_t *share) {
+// n symbols x[k] under m[k] = loc_to_m(loc[k]) and the cursor's inv at p0 + k.  0, or IREC_RES_E_LOC for a loc that is not finite.
+// *share: the checksum terms.
+template <class Sink, class Inv>
+IREC_REC_HD inline int32_t encode_stream(const uint8_t *x, const float *loc, Inv inv_at, int64_t p0, int64_t n, Sink &sink, uint32_t *share) {
   uint64_t low = 0, high = WHOLE;
   int64_t s = 0;
   uint32_t sum = 0;
   for (int64_t k = 0; k < n; ++k) {
     if (!is_finite(loc[k])) return IREC_RES_E_LOC;
+    const double inv = inv_at.at(p0 + k);
     const int32_t m = loc_to_m(loc[k]);
     const uint32_t sym = x[k];
     sum += checksum_term(p0 + k, sym);
@@ -149,13 +194,16 @@ IREC_REC_HD inline int32_t encode_stream(const uint8_t *x, const float *loc, dou
 
 // The inverse: n symbols into out[0, n), nothing else written.  0 or IREC_RES_E_CORRUPT (target < 0, width <= 0, target >= width, or
 // more than n_bits + 64 renormalisation shifts).  Every loop is bounded on entry: n symbols, 8 bisection steps, the shift budget.
-IREC_REC_HD inline int32_t decode_stream(const BitReader &in, const float *loc, double inv, int64_t p0, int64_t n, uint8_t *out, uint32_t *share) {
+template <class Inv>
+IREC_REC_HD inline int32_t decode_stream(const BitReader &in, const float *loc, Inv inv_at, int64_t p0, int64_t n, uint8_t *out, uint32_t *share) {
   uint64_t low = 0, high = WHOLE, z = 0;
   int64_t i = 0, shifts_left = in.n_bits + 64;
   uint32_t sum = 0;
   *share = 0;
   while (i < 32) { z += in.bit(i) << (31 - i); ++i; }
+  double inv = inv_at.at(p0);
   for (int64_t k = 0; k < n; ++k) {
+    if constexpr (!Inv::fixed) inv = inv_at.at(p0 + k);
     if (z < low || high <= low || z >= high) return IREC_RES_E_CORRUPT;
     const uint64_t width = high - low, target = z - low;
     const uint64_t v = (((target + 1) << TOTAL_BITS) - 1) / width;                // < 2^16, as target < width
@@ -206,28 +254,31 @@ IREC_REC_HD inline void encode_bind_workspace(EncodeCall &c, void *ws) {
 }
 IREC_REC_HD inline int64_t stream_bytes(int64_t n_bits) { return (n_bits + 7) / 8; }
 
-template <class Sink>
-IREC_REC_HD inline int32_t encode_lane_stream(const EncodeCall &c, int64_t lane, Sink &sink, uint32_t *share) {
+template <class Sink, class Scales>
+IREC_REC_HD inline int32_t encode_lane_stream(const EncodeCall &c, const Scales &sc, int64_t lane, Sink &sink, uint32_t *share) {
   const int64_t i = lane / c.ns, j = lane % c.ns, k0 = j * (int64_t)c.stream_len;
   const int64_t k1 = k0 + c.stream_len < c.n_sym ? k0 + c.stream_len : c.n_sym;
-  if (!scale_ok(c.scale)) return IREC_RES_E_SCALE;
-  return encode_stream(c.pixels + i * c.n_sym + k0, c.loc + i * c.n_sym + k0, model_inv(c.scale), k0, k1 - k0, sink, share);
+  if (!sc.ok(c.scale, c.channels)) return IREC_RES_E_SCALE;
+  return encode_stream(c.pixels + i * c.n_sym + k0, c.loc + i * c.n_sym + k0, sc.cursor(c.scale), k0, k1 - k0, sink, share);
 }
 
 // launch 1, lane < N ns
-IREC_REC_HD inline void encode_size_lane(const EncodeCall &c, int64_t lane) {
+template <class Scales>
+IREC_REC_HD inline void encode_size_lane(const EncodeCall &c, const Scales &sc, int64_t lane) {
   CountingSink sink;
   uint32_t share = 0;
-  const int32_t st = encode_lane_stream(c, lane, sink, &share);
+  const int32_t st = encode_lane_stream(c, sc, lane, sink, &share);
   c.stream_status[lane] = st;
   c.n_bits[lane] = st ? 0 : (int32_t)sink.n;
   c.share[lane] = st ? 0u : share;
 }
+IREC_REC_HD inline void encode_size_lane(const EncodeCall &c, int64_t lane) { encode_size_lane(c, CallScale{}, lane); }
 
 // launch 2, per image: its status (the first cause in stream order) and its file's bytes (0 with an error status) ...
-IREC_REC_HD inline int64_t encode_image_bytes(const EncodeCall &c, int64_t i) {
+template <class Scales>
+IREC_REC_HD inline int64_t encode_image_bytes(const EncodeCall &c, const Scales &sc, int64_t i) {
   int32_t st = IREC_RES_OK;
-  int64_t bytes = HEADER_BYTES + 2 * (int64_t)c.ns;
+  int64_t bytes = sc.header_bytes(c.channels) + 2 * (int64_t)c.ns;
   for (int64_t j = 0; j < c.ns; ++j) {
     if (st == IREC_RES_OK) st = c.stream_status[i * c.ns + j];
     bytes += stream_bytes(c.n_bits[i * c.ns + j]);
@@ -235,36 +286,48 @@ IREC_REC_HD inline int64_t encode_image_bytes(const EncodeCall &c, int64_t i) {
   c.status[i] = st;
   return st ? 0 : bytes;
 }
+IREC_REC_HD inline int64_t encode_image_bytes(const EncodeCall &c, int64_t i) { return encode_image_bytes(c, CallScale{}, i); }
 // ... and, once the call's total is known, the positions of its streams and (if the files fit cap) its header
-IREC_REC_HD inline void encode_image_layout(const EncodeCall &c, int64_t i, int64_t at, bool fits) {
+template <class Scales>
+IREC_REC_HD inline void encode_image_layout(const EncodeCall &c, const Scales &sc, int64_t i, int64_t at, bool fits) {
   c.offsets[i] = at;
   if (c.status[i]) return;
-  int64_t pos = HEADER_BYTES + 2 * (int64_t)c.ns;
+  const int64_t head = sc.header_bytes(c.channels);
+  int64_t pos = head + 2 * (int64_t)c.ns;
   uint32_t sum = 0;
   uint8_t *f = c.out + at;
   for (int64_t j = 0; j < c.ns; ++j) {
     const int64_t nb = stream_bytes(c.n_bits[i * c.ns + j]);
     c.pos[i * c.ns + j] = pos;
     sum += c.share[i * c.ns + j];
-    if (fits) put_u16(f + HEADER_BYTES + 2 * j, (uint32_t)nb);
+    if (fits) put_u16(f + head + 2 * j, (uint32_t)nb);
     pos += nb;
   }
   if (!fits) return;
-  put_u32(f, MAGIC); put_u16(f + 4, VERSION); put_u16(f + 6, c.channels); put_u32(f + 8, c.stream_len); put_u32(f + 12, c.height);
-  put_u32(f + 16, c.width); put_u32(f + 20, __builtin_bit_cast(uint32_t, c.scale)); put_u32(f + 24, sum);
+  put_u32(f, MAGIC); put_u16(f + 4, Scales::version); put_u16(f + 6, c.channels); put_u32(f + 8, c.stream_len); put_u32(f + 12, c.height);
+  put_u32(f + 16, c.width);
+  if constexpr (Scales::per_channel) {
+    for (uint32_t ch = 0; ch < c.channels; ++ch) put_u32(f + 20 + 4 * (int64_t)ch, __builtin_bit_cast(uint32_t, sc.scales[ch]));
+  } else {
+    put_u32(f + 20, __builtin_bit_cast(uint32_t, c.scale));
+  }
+  put_u32(f + head - 4, sum);
 }
+IREC_REC_HD inline void encode_image_layout(const EncodeCall &c, int64_t i, int64_t at, bool fits) { encode_image_layout(c, CallScale{}, i, at, fits); }
 
 // launch 3, lane < N ns: the stream of the lane.  Nothing at all is written when the files do not fit cap.
-IREC_REC_HD inline void encode_write_lane(const EncodeCall &c, int64_t lane) {
+template <class Scales>
+IREC_REC_HD inline void encode_write_lane(const EncodeCall &c, const Scales &sc, int64_t lane) {
   const int64_t i = lane / c.ns;
   if (c.offsets[c.N] > c.cap || c.status[i]) return;
   const int64_t at = c.offsets[i] + c.pos[lane], nb = c.n_bits[lane];
   if (at < c.offsets[i] || at + stream_bytes(nb) > c.offsets[i + 1]) return;      // (cannot happen: the layout pass summed these very sizes)
   WritingSink sink(c.out + at, nb);
   uint32_t share;
-  encode_lane_stream(c, lane, sink, &share);
+  encode_lane_stream(c, sc, lane, sink, &share);
   sink.finish();
 }
+IREC_REC_HD inline void encode_write_lane(const EncodeCall &c, int64_t lane) { encode_write_lane(c, CallScale{}, lane); }
 
 // ================================================================================================================================
 //  Decoding a call: headers and stream positions, the streams, one status per image
@@ -283,22 +346,34 @@ IREC_REC_HD inline void decode_bind_workspace(DecodeCall &c, void *ws) {
 }
 
 // launch 1, lane i < N: every check that needs no stream decoded, and the position of every stream.  Reads [file, file + n_bytes) only.
-IREC_REC_HD inline void decode_head_lane(const DecodeCall &c, int64_t i) {
-  const int64_t lo = c.offsets[i], n_bytes = c.offsets[i + 1] - lo;
+// (version 2 looks at the magic and version words as soon as the file holds them: a version-1 file shorter than a version-2 header is
+//  still "not this version")
+IREC_REC_HD inline bool scale_words_differ(const DecodeCall &c, const ChannelScales &sc, const uint8_t *f) {
+  bool differ = false;
+  for (uint32_t ch = 0; ch < c.channels; ++ch)
+    differ = differ || get_u32(f + 20 + 4 * (int64_t)ch) != __builtin_bit_cast(uint32_t, sc.scales[ch]) || !scale_ok(sc.scales[ch]);
+  return differ;
+}
+IREC_REC_HD inline bool scale_words_differ(const DecodeCall &, const CallScale &, const uint8_t *) { return false; }
+template <class Scales>
+IREC_REC_HD inline void decode_head_lane(const DecodeCall &c, const Scales &sc, int64_t i) {
+  const int64_t lo = c.offsets[i], n_bytes = c.offsets[i + 1] - lo, head = sc.header_bytes(c.channels);
   const uint8_t *f = c.bytes + lo;
   int32_t st = IREC_RES_OK;
   c.head_sum[i] = 0;
-  if (lo < 0 || n_bytes < HEADER_BYTES) st = IREC_RES_E_TRUNCATED_HEADER;
-  else if (get_u32(f) != MAGIC || get_u16(f + 4) != VERSION) st = IREC_RES_E_MAGIC;
+  if (lo < 0 || n_bytes < (Scales::per_channel ? 6 : head)) st = IREC_RES_E_TRUNCATED_HEADER;
+  else if (get_u32(f) != MAGIC || get_u16(f + 4) != Scales::version) st = IREC_RES_E_MAGIC;
+  else if (Scales::per_channel && n_bytes < head) st = IREC_RES_E_TRUNCATED_HEADER;
   else if (get_u16(f + 6) != c.channels || get_u32(f + 8) != c.stream_len || get_u32(f + 12) != c.height || get_u32(f + 16) != c.width)
     st = IREC_RES_E_SHAPE;
-  else if (get_u32(f + 20) != __builtin_bit_cast(uint32_t, c.scale) || !scale_ok(c.scale)) st = IREC_RES_E_SCALE_WORD;
-  else if (n_bytes < HEADER_BYTES + 2 * (int64_t)c.ns) st = IREC_RES_E_TRUNCATED_HEADER;
+  else if (Scales::per_channel ? scale_words_differ(c, sc, f) : get_u32(f + 20) != __builtin_bit_cast(uint32_t, c.scale) || !scale_ok(c.scale))
+    st = IREC_RES_E_SCALE_WORD;
+  else if (n_bytes < head + 2 * (int64_t)c.ns) st = IREC_RES_E_TRUNCATED_HEADER;
   if (st == IREC_RES_OK) {
-    c.head_sum[i] = get_u32(f + 24);
-    int64_t pos = HEADER_BYTES + 2 * (int64_t)c.ns;
+    c.head_sum[i] = get_u32(f + head - 4);
+    int64_t pos = head + 2 * (int64_t)c.ns;
     for (int64_t j = 0; j < c.ns; ++j) {
-      const int64_t nb = get_u16(f + HEADER_BYTES + 2 * j);
+      const int64_t nb = get_u16(f + head + 2 * j);
       c.pos[i * c.ns + j] = pos; c.len[i * c.ns + j] = (int32_t)nb;
       pos += nb;
     }
@@ -306,9 +381,11 @@ IREC_REC_HD inline void decode_head_lane(const DecodeCall &c, int64_t i) {
   }
   c.head_status[i] = st;
 }
+IREC_REC_HD inline void decode_head_lane(const DecodeCall &c, int64_t i) { decode_head_lane(c, CallScale{}, i); }
 
 // launch 2, lane < N ns: its stream into its own pixels
-IREC_REC_HD inline void decode_stream_lane(const DecodeCall &c, int64_t lane) {
+template <class Scales>
+IREC_REC_HD inline void decode_stream_lane(const DecodeCall &c, const Scales &sc, int64_t lane) {
   const int64_t i = lane / c.ns, j = lane % c.ns, k0 = j * (int64_t)c.stream_len;
   const int64_t k1 = k0 + c.stream_len < c.n_sym ? k0 + c.stream_len : c.n_sym;
   c.stream_status[lane] = IREC_RES_OK; c.share[lane] = 0;
@@ -317,9 +394,10 @@ IREC_REC_HD inline void decode_stream_lane(const DecodeCall &c, int64_t lane) {
   if (pos < 0 || nb < 0 || pos + nb > n_bytes) { c.stream_status[lane] = IREC_RES_E_TRUNCATED_STREAMS; return; }   // (the head lane checked)
   const BitReader in{c.bytes + lo + pos, nb * 8};
   uint32_t share = 0;
-  c.stream_status[lane] = decode_stream(in, c.loc + i * c.n_sym + k0, model_inv(c.scale), k0, k1 - k0, c.pixels + i * c.n_sym + k0, &share);
+  c.stream_status[lane] = decode_stream(in, c.loc + i * c.n_sym + k0, sc.cursor(c.scale), k0, k1 - k0, c.pixels + i * c.n_sym + k0, &share);
   c.share[lane] = share;
 }
+IREC_REC_HD inline void decode_stream_lane(const DecodeCall &c, int64_t lane) { decode_stream_lane(c, CallScale{}, lane); }
 
 // ---- a whole call over host memory: what the kernels of irec_res.hip do, the lanes of a launch dealt out by par(n, body) with
 //      body(lo, hi) running lanes [lo, hi) in a plain loop (the workspace bound by the caller).  The host entry points pass a pool of
@@ -327,16 +405,18 @@ IREC_REC_HD inline void decode_stream_lane(const DecodeCall &c, int64_t lane) {
 struct SerialLanes {
   template <class F> void operator()(int64_t n, F &&body) const { body((int64_t)0, n); }
 };
-template <class Par>
-inline void encode_call_host(const EncodeCall &c, Par &&par) {
+template <class Scales, class Par>
+inline void encode_call_host(const EncodeCall &c, const Scales &sc, Par &&par) {
   const int64_t lanes = (int64_t)c.N * c.ns;
-  par(lanes, [&c](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) encode_size_lane(c, l); });
+  par(lanes, [&c, &sc](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) encode_size_lane(c, sc, l); });
   int64_t total = 0, at = 0;
-  for (int64_t i = 0; i < c.N; ++i) total += encode_image_bytes(c, i);
-  for (int64_t i = 0; i < c.N; ++i) { encode_image_layout(c, i, at, total <= c.cap); at += encode_image_bytes(c, i); }
+  for (int64_t i = 0; i < c.N; ++i) total += encode_image_bytes(c, sc, i);
+  for (int64_t i = 0; i < c.N; ++i) { encode_image_layout(c, sc, i, at, total <= c.cap); at += encode_image_bytes(c, sc, i); }
   c.offsets[c.N] = total;
-  par(lanes, [&c](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) encode_write_lane(c, l); });
+  par(lanes, [&c, &sc](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) encode_write_lane(c, sc, l); });
 }
+template <class Par>
+inline void encode_call_host(const EncodeCall &c, Par &&par) { encode_call_host(c, CallScale{}, par); }
 inline void decode_image_status(const DecodeCall &c, int64_t i) {
   int32_t st = c.head_status[i];
   uint32_t sum = 0;
@@ -345,12 +425,14 @@ inline void decode_image_status(const DecodeCall &c, int64_t i) {
   c.status[i] = st;
   if (st) for (int64_t e = 0; e < c.n_sym; ++e) c.pixels[i * c.n_sym + e] = 0;
 }
-template <class Par>
-inline void decode_call_host(const DecodeCall &c, Par &&par) {
-  for (int64_t i = 0; i < c.N; ++i) decode_head_lane(c, i);
-  par((int64_t)c.N * c.ns, [&c](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) decode_stream_lane(c, l); });
+template <class Scales, class Par>
+inline void decode_call_host(const DecodeCall &c, const Scales &sc, Par &&par) {
+  for (int64_t i = 0; i < c.N; ++i) decode_head_lane(c, sc, i);
+  par((int64_t)c.N * c.ns, [&c, &sc](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) decode_stream_lane(c, sc, l); });
   for (int64_t i = 0; i < c.N; ++i) decode_image_status(c, i);
 }
+template <class Par>
+inline void decode_call_host(const DecodeCall &c, Par &&par) { decode_call_host(c, CallScale{}, par); }
 
 } // namespace irec_res
 #endif // IREC_RES_CORE_H_

@@ -221,6 +221,16 @@ SIGNATURES = {
                                                     ctypes.c_size_t, _vp]),
     "irec_res_encode_files": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _i32] + [ctypes.c_uint32] * 4 + [_vp, _i64, _vp, _vp, _i32]),
     "irec_res_decode_files": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _i32] + [ctypes.c_uint32] * 4 + [_vp, _vp, _i32]),
+    "irec_res_encode_files_device_scales": (ctypes.c_int, [_vp, _vp, _vp, _i32] + [ctypes.c_uint32] * 4 + [_vp, _i64, _vp, _vp, _vp,
+                                                           ctypes.c_size_t, _vp]),
+    "irec_res_decode_files_device_scales": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32] + [ctypes.c_uint32] * 4 + [_vp, _vp, _vp,
+                                                           ctypes.c_size_t, _vp]),
+    "irec_res_encode_files_scales": (ctypes.c_int, [_vp, _vp, _vp, _i32] + [ctypes.c_uint32] * 4 + [_vp, _i64, _vp, _vp, _i32]),
+    "irec_res_decode_files_scales": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32] + [ctypes.c_uint32] * 4 + [_vp, _vp, _i32]),
+    "irec_res_cost_table": (ctypes.c_int, [_vp]),
+    "irec_res_scale_bits_workspace_bytes": (ctypes.c_size_t, [_i32] + [ctypes.c_uint32] * 3 + [_i32]),
+    "irec_res_scale_bits_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32] + [ctypes.c_uint32] * 3 + [_i32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "irec_res_scale_bits": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32] + [ctypes.c_uint32] * 3 + [_i32, _vp, _vp, _i32]),
     "irec_res_model_counts": (ctypes.c_int, [_i32, ctypes.c_float, _vp]),
     "irec_res_symbol_counts": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _i64, _vp]),
     "irec_quality_workspace_bytes": (ctypes.c_size_t, [_i32] * 5),

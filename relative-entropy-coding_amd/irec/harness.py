@@ -166,7 +166,7 @@ def _lossless_leg(model, chunk, names, seed, block_size, out_dir, S, stream_len)
     pixels, status = model.decompress_lossless(_upload(back, chunk.device), off2, _upload(res_back, chunk.device), res_off2, seed, tuple(chunk.shape),
                                                max_K=max(int(K.max()), 1), strict=False, stream_len=stream_len)
     same = ((pixels == chunk).reshape(n, -1).all(dim=1)).cpu().numpy() & (status == 0)
-    ideal = residual_model_bits(chunk, rec, model.likelihood_scale())
+    ideal = residual_model_bits(chunk, rec, model.residual_scale())
     n_idx = K.sum(dim=(1, 2)).cpu().numpy()
     t_host = (time.perf_counter() - t1) / n
     rows = []
@@ -483,6 +483,16 @@ def fit_symbol_tables(model, images, seed, batch=None, max_K=None):
     if max_K is None:
         max_K = 2 * max(idx.shape[2] for _, idx, _ in rows)
     return _fit_batches(rows, S, int(max_K) + 1)
+
+
+def fit_likelihood_scale(model, images, seed, per_channel=False, batch=None, block_size=None):
+    """Fit BidirectionalResNetVAE `model`'s likelihood scale to uint8 `images` [n, 3, H, W] (on its device) and set it on the model
+    (model.fit_likelihood_scale: the batches' pixels are costed where they lie under candidate scales, one small read-back per round
+    of the search): one scale, and version-1 .res files as before, or with per_channel=True one per colour channel and version-2
+    files.  compress_images(lossless=True) and decompress_images_lossless work with the model as it then is.  Returns the fitted
+    log-scale(s) and their coded bits, (float, float) or (float64 [3], float64 [3])."""
+    log_scales, units, _ = model.fit_likelihood_scale(images, seed, per_channel=per_channel, batch=batch, block_size=block_size)
+    return log_scales, np.asarray(units, dtype=np.float64) / 65536.0 if per_channel else float(units) / 65536.0
 
 
 def fit_symbol_tables_lossy(model, sampler, images, seed, block_size, batch=None, max_K=None):

@@ -8,3 +8,4 @@ from .segmented import decode_files_device_segmented, segment_blocks_of, segment
 from .tables import SymbolTables, RowHistograms, hist_rows, tables_from_histograms  # noqa: F401
 from .residual import encode_residuals, decode_residuals, encode_residuals_device, decode_residuals_device  # noqa: F401
 from .residual import residual_model_bits, res_status_text  # noqa: F401
+from .residual import cost_table, scale_bits, scale_bits_device, residual_model_bits_device, fit_scales  # noqa: F401

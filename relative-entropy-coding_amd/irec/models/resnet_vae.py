@@ -340,6 +340,10 @@ class BidirectionalResNetVAE(nn.Module):
         # Created after every other parameter and without a random draw: no existing initialisation moves.
         self.likelihood_log_scale = nn.Parameter(torch.zeros(()))
         self._likelihood_scale_cache = None
+        # One log-scale per colour channel, or None (the scalar parameter above holds): a buffer that is absent from state_dict()
+        # while it is None, so a model without per-channel scales keeps its keys.  set_likelihood_scales / fit_likelihood_scale set it.
+        self.register_buffer("likelihood_log_scales", None)
+        self._likelihood_scales_cache = None
 
     def generative_base(self, batch_size, height, width):
         """resnet_vae.py:619-623."""
@@ -607,16 +611,39 @@ class BidirectionalResNetVAE(nn.Module):
             self._likelihood_scale_cache = (key, scale_from_log(p.detach().cpu().item()))
         return self._likelihood_scale_cache[1]
 
+    def set_likelihood_scales(self, log_scales):
+        """One likelihood log-scale per colour channel ([3] values: .res version 2 from here on), or None: back to the scalar
+        likelihood_log_scale and version 1.  A model with per-channel scales has the extra state_dict() key likelihood_log_scales."""
+        if log_scales is None:
+            self.likelihood_log_scales = None
+        else:
+            t = torch.as_tensor(log_scales, dtype=torch.float32).detach().reshape(-1)
+            if t.numel() != 3 or not bool(torch.isfinite(t).all()):
+                raise ModelError("set_likelihood_scales takes three finite log-scales, or None")
+            self.likelihood_log_scales = t.clone().to(self.likelihood_log_scale.device)
+        self._likelihood_scales_cache = None
+
+    def likelihood_scales(self):
+        """None, or exp(likelihood_log_scales) as the float32 [3] tensor (on the model's device) that the version-2 .res coder reads:
+        exp in float64, rounded once to float32, as likelihood_scale() does.  Read back when the buffer has changed, not per call."""
+        p = self.likelihood_log_scales
+        if p is None:
+            return None
+        key = (p._version, p.data_ptr())
+        if self._likelihood_scales_cache is None or self._likelihood_scales_cache[0] != key:
+            from ..io.residual import scale_from_log
+            scales = torch.tensor([scale_from_log(v) for v in p.detach().cpu().tolist()], dtype=torch.float32, device=p.device)
+            self._likelihood_scales_cache = (key, scales)
+        return self._likelihood_scales_cache[1]
+
+    def residual_scale(self):
+        """What the .res calls take as `scale`: the per-channel tensor when it is set (version 2), else the one float (version 1)."""
+        scales = self.likelihood_scales()
+        return self.likelihood_scale() if scales is None else scales
+
     @torch.no_grad()
-    def compress_lossless(self, images_u8, seed, stream_len=None, update_sampler=False, block_size=None, return_pendings=False):
-        """images_u8 [N, 3, H, W] uint8 CUDA -> (rec_blob, rec_offsets, res_blob, res_offsets, reconstruction), CUDA tensors.  The model
-        sees x / 256 - 0.5; the .rec files are exactly compress_rec's on that input; image i's .res file is
-        res_blob[res_offsets[i]:res_offsets[i + 1]]: its pixels arithmetic-coded on the device under the discretized logistic of
-        loc = the reconstruction that decompress_rec makes of those files (returned as `reconstruction`) and
-        scale = exp(likelihood_log_scale) (irec.io.encode_residuals_device; stream_len: symbols per stream, default
-        irec.io.residual.DEFAULT_STREAM_LEN).  decompress_lossless gives the images back exactly.
-        return_pendings: also compress_rec's device K / idx views, (the five, (K, idx))."""
-        from ..io.residual import encode_residuals_device
+    def _lossless_rec(self, images_u8, seed, update_sampler=False, block_size=None):
+        """compress_lossless's two passes: ((rec blob, offsets), (K, idx), the DECODER's reconstruction of those files)."""
         if not (images_u8.is_cuda and images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.shape[1] == 3):
             raise ModelError("compress_lossless takes a CUDA uint8 tensor [N, 3, H, W]")
         x = images_u8.to(torch.float32).mul_(1.0 / 256.0).sub_(0.5)                 # exact: the values are k / 256 - 1 / 2
@@ -627,8 +654,45 @@ class BidirectionalResNetVAE(nn.Module):
         # same batch, the same bits.
         K, idx = pendings
         reconstruction = self._decompress_device(K, idx, seed, tuple(images_u8.shape), torch.zeros(K.shape[0], dtype=torch.int32, device=K.device))
+        return (blob, offsets), pendings, reconstruction
+
+    @torch.no_grad()
+    def fit_likelihood_scale(self, images_u8, seed, per_channel=False, batch=None, block_size=None):
+        """Fit the likelihood scale to `images_u8` [n, 3, H, W] (uint8, on the model's device) where the data is: every batch goes
+        through compress_lossless's own two passes to the decoder's reconstruction, irec.io.residual.fit_scales searches the exact
+        coded cost of the pixels over the log-scale (the current scalar among the candidates), and the result is set: the scalar
+        likelihood_log_scale (per-channel scales cleared), or with per_channel=True the three likelihood_log_scales.  One small
+        read-back per round of the search.  Returns fit_scales' (log_scales, bits, evaluated)."""
+        from ..io.residual import fit_scales
+        n = images_u8.shape[0]
+        step = n if not batch else int(batch)
+        pairs = []
+        for lo in range(0, n, step):
+            chunk = images_u8[lo:lo + step]
+            pairs.append((chunk, self._lossless_rec(chunk, seed, block_size=block_size)[2]))
+        start = float(self.likelihood_log_scale.detach().cpu().item())
+        log_scales, bits, evaluated = fit_scales(pairs, per_channel=per_channel, start=start)
+        if per_channel:
+            self.set_likelihood_scales(log_scales)
+        else:
+            self.set_likelihood_scales(None)
+            self.likelihood_log_scale.fill_(float(log_scales))
+        return log_scales, bits, evaluated
+
+    @torch.no_grad()
+    def compress_lossless(self, images_u8, seed, stream_len=None, update_sampler=False, block_size=None, return_pendings=False):
+        """images_u8 [N, 3, H, W] uint8 CUDA -> (rec_blob, rec_offsets, res_blob, res_offsets, reconstruction), CUDA tensors.  The model
+        sees x / 256 - 0.5; the .rec files are exactly compress_rec's on that input; image i's .res file is
+        res_blob[res_offsets[i]:res_offsets[i + 1]]: its pixels arithmetic-coded on the device under the discretized logistic of
+        loc = the reconstruction that decompress_rec makes of those files (returned as `reconstruction`) and
+        scale = exp(likelihood_log_scale) (irec.io.encode_residuals_device; stream_len: symbols per stream, default
+        irec.io.residual.DEFAULT_STREAM_LEN), or, exactly when likelihood_log_scales is set, one scale per channel and version-2
+        files.  decompress_lossless gives the images back exactly.
+        return_pendings: also compress_rec's device K / idx views, (the five, (K, idx))."""
+        from ..io.residual import encode_residuals_device
+        (blob, offsets), pendings, reconstruction = self._lossless_rec(images_u8, seed, update_sampler, block_size)
         try:
-            res_blob, res_offsets = encode_residuals_device(images_u8, reconstruction, self.likelihood_scale(), stream_len=stream_len)
+            res_blob, res_offsets = encode_residuals_device(images_u8, reconstruction, self.residual_scale(), stream_len=stream_len)
         except ValueError as e:
             raise CodingError(str(e))
         out = (blob, offsets, res_blob, res_offsets, reconstruction)
@@ -640,7 +704,7 @@ class BidirectionalResNetVAE(nn.Module):
         the device.  No host synchronisation when max_K is given."""
         from ..io.residual import _decode_residuals_device_launch
         reconstruction, joined, K = self._decompress_rec_device(rec_blob, rec_offsets, seed, image_shape, max_K)
-        pixels, res_status = _decode_residuals_device_launch(res_blob, res_offsets, reconstruction, self.likelihood_scale(), stream_len,
+        pixels, res_status = _decode_residuals_device_launch(res_blob, res_offsets, reconstruction, self.residual_scale(), stream_len,
                                                              on_device=True)
         joined = torch.where(joined != 0, joined, torch.where(res_status != 0, res_status + STATUS_RESIDUAL, res_status))
         # an image that an earlier stage refused was residual-decoded on a reconstruction that means nothing: zero, not garbage

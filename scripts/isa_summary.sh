@@ -1,6 +1,7 @@
 #!/bin/bash
 # Per-kernel register / scratch / LDS / instruction-mix summary of the HIP sources, from hipcc's own assembly output.
 # Usage: scripts/isa_summary.sh [out.txt]   (no GPU needed; cross-compiles for gfx950)
+#        UNITS="irec_res irec_res_fit" scripts/isa_summary.sh out.txt   only these units (before / after a change of one header)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${1:-/dev/stdout}
@@ -12,7 +13,7 @@ echo "# kernel | VGPRs | AGPRs | SGPRs | scratch B/lane | static LDS B | scratch
 echo "# (round 5, last column: the loop of 80 ds_read_b32 and 0 scratch operations is the software-pipelined steady state that every full step of a 20-beam build"
 echo "#  runs -- 20 beams x 4 dim slots per sample; the loops listed before it are the beam-by-beam fall-back of partly filled stripes and the first step's"
 echo "#  wide path: the headline build's 588 B/lane of scratch are outside the steady state)"
-for f in irec_team irec_team_margin irec_chunk_gang irec_prep irec_ten irec_lone irec_kernels irec_decode irec_rec irec_rec_tables irec_rec_seg; do
+for f in ${UNITS:-irec_team irec_team_margin irec_chunk_gang irec_prep irec_ten irec_lone irec_kernels irec_decode irec_rec irec_rec_tables irec_rec_seg irec_res irec_res_fit}; do
   extra=""; case $f in irec_team*|irec_chunk_gang|irec_prep|irec_ten|irec_kernels) extra="-mllvm -sink-insts-to-avoid-spills=true";; esac   # (SINK_OBJS of csrc/Makefile)
   hipcc $FLAGS $extra "$ROOT/relative-entropy-coding_amd/csrc/$f.hip" -o "$TMP/$f.s" 2>/dev/null
   python3 - "$TMP/$f.s" <<'PY'
