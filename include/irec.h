@@ -36,6 +36,21 @@ extern "C" {
 #define IREC_MAX_BEAMS 256       /* hard limit of this build (reference: any python int, beam_search_coder.py:28); B <= 60 takes the */
                                  /* register-resident encoders, anything above the generic kernel                                    */
 #define IREC_MAX_PARTITIONS 65536 /* hard limit on K = ceil(KL / kl_per_partition) */
+/* Seeds.  A CODING SEED is the `seed` of GaussianCoder.encode / decode: any int64 up to IREC_SEED_MAX = INT64_MAX -
+ * (IREC_MAX_PARTITIONS + 2), so that no step seed the library forms from it -- seed + t of step t < IREC_MAX_PARTITIONS, seed + j + 1
+ * and seed + j + 2 of the Gumbel draw of step j -- overflows int64.  Every entry point that takes a coding seed (irec_beam_encode[_ex],
+ * irec_beam_decode[_ws | _tensors], irec_normal_table_build, irec_gumbel_table_build, irec_test_proposal_table) answers IREC_E_INVALID
+ * above it, with the seed and the bound in irec_last_error(); nothing is launched and nothing is written.  The host sampler
+ * (irec_importance_encode / _decode, irec_tf_stateless_gumbel) takes the seed of ONE step, which its caller forms from a coding seed,
+ * and adds at most 2 to it: it answers IREC_E_INVALID above INT64_MAX - 2.  Negative seeds are valid.  The beam-search coders reduce seed + t modulo 2^31 - 1
+ * (TensorFlow's truncation of both seeds, python/framework/random_seed.py; residue 0 becomes the pair (0, 2^31 - 1)), so seeds congruent
+ * modulo 2^31 - 1 code identically -- as they do in the reference; the shuffle and the importance coder's normal stream take their op
+ * seed from CPython's random.Random(seed), which sees every bit of the seed.  The stamps of IREC_FLAG_REUSE_TABLES hold all 64 bits: two
+ * seeds share a table only if they are equal.
+ * A HEADER SEED is the uint32 field of a .rec / .recs file (irec_rec_encode_file*): a file can only name a coding seed in [0, 2^32), and
+ * decompress codes under the seed it reads, so a caller that writes files must code under a seed of that range (irec.io.header_seed
+ * refuses any other before a byte is written). */
+#define IREC_SEED_MAX (INT64_MAX - (IREC_MAX_PARTITIONS + 2))
 
 typedef enum {
   IREC_OK = 0,

@@ -35,6 +35,22 @@ irec_status fail(irec_status code, const char *fmt, ...) {
   return code;
 }
 
+// A coding seed above IREC_SEED_MAX (include/irec.h): some seed + t the call forms would overflow int64.  Checked before anything else of
+// the call, so nothing is launched and nothing written.
+irec_status check_seed(const char *who, int64_t seed) {
+  if (seed > IREC_SEED_MAX)
+    return fail(IREC_E_INVALID, "%s: seed %lld exceeds IREC_SEED_MAX = %lld (INT64_MAX - IREC_MAX_PARTITIONS - 2: seed + step must fit int64)", who,
+                (long long)seed, (long long)IREC_SEED_MAX);
+  return IREC_OK;
+}
+// The sampler entry points take the seed of ONE step (the coding seed + t, formed by their caller) and add at most 2 to it themselves.
+irec_status check_step_seed(const char *who, int64_t seed) {
+  if (seed > INT64_MAX - 2)
+    return fail(IREC_E_INVALID, "%s: step seed %lld exceeds INT64_MAX - 2 = %lld (the Gumbel draw takes seed + 1 and seed + 2)", who,
+                (long long)seed, (long long)(INT64_MAX - 2));
+  return IREC_OK;
+}
+
 #define HIP_TRY(expr)                                                                           \
   do {                                                                                          \
     hipError_t e_ = (expr);                                                                     \
@@ -367,6 +383,7 @@ irec_status irec_tf_stateless_normal(int64_t seed0, int64_t seed1, int64_t count
 static inline float gumbel_element(TfStatelessNormalStream &gst, uint64_t s) { return -std::log(-std::log(gst.element(s))); }
 
 irec_status irec_tf_stateless_gumbel(int64_t seed, int64_t count, float *out) {
+  if (irec_status s = check_step_seed("irec_tf_stateless_gumbel", seed)) return s;
   if (count < 0 || (count > 0 && !out)) return fail(IREC_E_INVALID, "irec_tf_stateless_gumbel: bad arguments");
   TfStatelessNormalStream gst(seed, seed + 1);
   for (int64_t e = 0; e < count; ++e) out[e] = gumbel_element(gst, (uint64_t)e);
@@ -376,6 +393,7 @@ irec_status irec_tf_stateless_gumbel(int64_t seed, int64_t count, float *out) {
 irec_status irec_importance_encode(const float *t_loc, const float *t_scale, const float *p_loc, const float *p_scale,
                                    int64_t n, double coding_bits, double alpha, int64_t seed, int64_t *out_index,
                                    float *out_sample) try {
+  if (irec_status s = check_step_seed("irec_importance_encode", seed)) return s;
   if (!t_loc || !t_scale || !p_loc || !p_scale || !out_index || !out_sample || n < 1)
     return fail(IREC_E_INVALID, "irec_importance_encode: bad arguments");
   if (!(alpha >= 1.0)) return fail(IREC_E_INVALID, "Alpha must be in the range [1, inf), but %g was given!", alpha); // :33-34
@@ -417,6 +435,7 @@ irec_status irec_importance_encode(const float *t_loc, const float *t_scale, con
 
 irec_status irec_importance_decode(const float *p_loc, const float *p_scale, int64_t n, int64_t index, int64_t seed,
                                    float *out_sample) {
+  if (irec_status s = check_step_seed("irec_importance_decode", seed)) return s;
   if (!p_loc || !p_scale || !out_sample || n < 1 || index < 0)
     return fail(IREC_E_INVALID, "irec_importance_decode: bad arguments");
   TfNormalStream st(seed);
@@ -1198,6 +1217,7 @@ irec_status irec_beam_encode_ex(irec_context *ctx, const irec_params *p, int64_t
                                 const int32_t *perm, const float *q_loc, const float *q_scale, const float *p_loc,
                                 const float *p_scale, int64_t seed, int32_t max_K, int32_t *out_K, int32_t *out_indices,
                                 float *out_sample, float *out_margin, void *workspace, size_t workspace_bytes, void *hip_stream) {
+  if (irec_status s = check_seed("irec_beam_encode", seed)) return s;
   if (!ctx) return fail(IREC_E_INVALID, "irec_beam_encode: null context");
   if (irec_status s = check_params(p)) return s;
   if (((p->flags & IREC_FLAG_MARGINS) != 0) != (out_margin != nullptr))
@@ -1365,6 +1385,7 @@ static irec_status beam_decode_impl(irec_context *ctx, const irec_params *p, int
                                     const int32_t *perm, const float *p_loc, const float *p_scale, int64_t seed,
                                     int32_t max_K, const int32_t *K, const int32_t *indices, float *out_sample,
                                     void *workspace, size_t workspace_bytes, void *hip_stream, const DecTensors *tens = nullptr) {
+  if (irec_status s = check_seed("irec_beam_decode", seed)) return s;
   if (!ctx) return fail(IREC_E_INVALID, "irec_beam_decode: null context");
   if (irec_status s = check_params(p)) return s;
   if (n_blocks < 0) return fail(IREC_E_INVALID, "irec_beam_decode: n_blocks < 0");
@@ -1521,6 +1542,7 @@ irec_status irec_test_select_quick(irec_context *ctx, const float *scores, int32
 
 irec_status irec_test_proposal_table(irec_context *ctx, int64_t seed, int32_t n_samples, int32_t dim, int32_t n_steps,
                                      uint16_t *out_tab, void *hip_stream) {
+  if (irec_status s = check_seed("irec_test_proposal_table", seed)) return s;
   if (!ctx || !out_tab || n_samples < 1 || dim < 1 || dim > irec::FAST_MAX_DIM || n_steps < 1)
     return fail(IREC_E_INVALID, "irec_test_proposal_table: bad arguments");
   IREC_ON_DEVICE(ctx->device);
@@ -1555,6 +1577,7 @@ size_t irec_normal_table_floats(int32_t n_samples, int32_t dim, int32_t steps) {
 }
 
 irec_status irec_normal_table_build(int64_t seed, int32_t n_samples, int32_t dim, int32_t steps, float *out, int32_t n_threads) try {
+  if (irec_status s = check_seed("irec_normal_table_build", seed)) return s;
   const size_t n = irec_normal_table_floats(n_samples, dim, steps);
   if (!n) return IREC_E_INVALID;
   if (!out) return fail(IREC_E_INVALID, "irec_normal_table_build: null output");
@@ -1600,6 +1623,7 @@ size_t irec_gumbel_table_floats(int32_t n_samples, int32_t steps) {
 }
 
 irec_status irec_gumbel_table_build(int64_t seed, int32_t n_samples, int32_t steps, float *out, int32_t n_threads) try {
+  if (irec_status s = check_seed("irec_gumbel_table_build", seed)) return s;
   if (!irec_gumbel_table_floats(n_samples, steps)) return IREC_E_INVALID;
   if (!out) return fail(IREC_E_INVALID, "irec_gumbel_table_build: null output");
   const size_t S_pad = round_up_sz((size_t)n_samples, IREC_NORMAL_TABLE_PAD);

@@ -41,6 +41,9 @@ REC_TABLE_LDS_SYMBOLS = 4096     # IREC_REC_TABLE_LDS_SYMBOLS
 IREC_REC_E_SEG_MAGIC, IREC_REC_E_SEG_DIRECTORY, IREC_REC_E_SEG_BLOCKS = 20, 21, 22   # irec_rec_status: the segmented reader's own causes
 REC_SEG_MAGIC = b"IRSG"          # the first four bytes of a segmented file (NAME.recs)
 INT32_MAX = 2 ** 31 - 1
+INT64_MAX = 2 ** 63 - 1
+SEED_MAX = INT64_MAX - (MAX_PARTITIONS + 2)   # IREC_SEED_MAX: the largest coding seed (seed + step must fit int64; the library checks it)
+HEADER_SEED_MAX = 2 ** 32 - 1                 # the seed field of a .rec / .recs header is a uint32
 
 
 class IrecParams(ctypes.Structure):
@@ -99,8 +102,43 @@ class IrecPlanDetail(ctypes.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+def seed_int(seed):
+    """`seed` as a Python int of any size: an integer type (numpy's included), or anything else that int() takes without changing its
+    value (a 0-d array, an integral float); ValueError for the rest."""
+    if hasattr(seed, "__index__"):
+        return seed.__index__()
+    try:
+        value = None if isinstance(seed, (str, bytes)) else int(seed)
+    except (TypeError, ValueError, OverflowError):
+        value = None
+    if value is None or value != seed:
+        raise ValueError(f"seed must be an integer, got {seed!r}")
+    return value
+
+
+def seed64(seed, coding=False):
+    """`seed` as the Python int a C entry point takes for an int64 seed, or ValueError: ctypes wraps an int that does not fit the C type
+    silently (c_int64(2 ** 63).value == -2 ** 63).  The bound IREC_SEED_MAX of a coding seed is the library's own check; coding=True
+    makes it here, for the callers that form seed + step themselves (the host path of the sequential coder)."""
+    seed = seed_int(seed)
+    if not -INT64_MAX - 1 <= seed <= (SEED_MAX if coding else INT64_MAX):
+        raise ValueError(f"seed {seed} is out of range: a coding seed is an int64 of at most IREC_SEED_MAX = {SEED_MAX} "
+                         "(INT64_MAX - MAX_PARTITIONS - 2: seed + step must fit int64)")
+    return seed
+
+
+class Seed64:
+    """The argument type of every int64 `seed` of include/irec.h: seed64 for whoever calls the library without it (ctypes reports the
+    ValueError as a ctypes.ArgumentError)."""
+
+    @classmethod
+    def from_param(cls, seed):
+        return ctypes.c_int64(seed64(seed))
+
+
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
+_seed = Seed64
 _i32 = ctypes.c_int32
 _PP = ctypes.POINTER(IrecParams)
 
@@ -148,15 +186,15 @@ SIGNATURES = {
     "irec_n_samples": (_i32, [ctypes.c_double, ctypes.c_double]),
     "irec_codelength": (ctypes.c_double, [_i64, _i32]),
     "irec_build_lut": (ctypes.c_int, [_vp]),
-    "irec_tf_shuffle_perm": (ctypes.c_int, [_i64, _i64, _vp]),
-    "irec_philox_uniform_int": (ctypes.c_int, [_i64, _i64, _vp]),
-    "irec_importance_encode": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _i64,
+    "irec_tf_shuffle_perm": (ctypes.c_int, [_seed, _i64, _vp]),
+    "irec_philox_uniform_int": (ctypes.c_int, [_seed, _i64, _vp]),
+    "irec_importance_encode": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _seed,
                                               ctypes.POINTER(_i64), _vp]),
-    "irec_tf_stateless_normal": (ctypes.c_int, [_i64, _i64, _i64, _vp]),
-    "irec_tf_stateless_gumbel": (ctypes.c_int, [_i64, _i64, _vp]),
-    "irec_importance_decode": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
+    "irec_tf_stateless_normal": (ctypes.c_int, [_seed, _seed, _i64, _vp]),
+    "irec_tf_stateless_gumbel": (ctypes.c_int, [_seed, _i64, _vp]),
+    "irec_importance_decode": (ctypes.c_int, [_vp, _vp, _i64, _i64, _seed, _vp]),
     "irec_importance_n_samples": (_i64, [ctypes.c_double]),
-    "irec_tf_random_normal": (ctypes.c_int, [_i64, _i64, _vp]),
+    "irec_tf_random_normal": (ctypes.c_int, [_seed, _i64, _vp]),
     "irec_create": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(_vp)]),
     "irec_create_ex": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "irec_create_with": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(IrecTables), ctypes.POINTER(_vp)]),
@@ -168,26 +206,26 @@ SIGNATURES = {
     "irec_test_plan_ws": (ctypes.c_int, [_i32, _i32, _PP, _i64, _i32, _i32, _i64, _vp, _vp]),
     "irec_encode_plan": (ctypes.c_int, [_vp, _PP, _i64, _i32, _i32, ctypes.POINTER(IrecPlanInfo)]),
     "irec_block_kl": (ctypes.c_int, [_vp, _PP, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "irec_beam_encode": (ctypes.c_int, [_vp, _PP, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
+    "irec_beam_encode": (ctypes.c_int, [_vp, _PP, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _seed, _i32,
                                         _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    "irec_beam_encode_ex": (ctypes.c_int, [_vp, _PP, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
+    "irec_beam_encode_ex": (ctypes.c_int, [_vp, _PP, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _seed, _i32,
                                            _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    "irec_beam_decode": (ctypes.c_int, [_vp, _PP, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "irec_beam_decode": (ctypes.c_int, [_vp, _PP, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _seed, _i32, _vp, _vp, _vp, _vp]),
     "irec_decode_workspace_bytes": (ctypes.c_size_t, [_vp, _PP, _i32]),
-    "irec_beam_decode_ws": (ctypes.c_int, [_vp, _PP, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
+    "irec_beam_decode_ws": (ctypes.c_int, [_vp, _PP, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _seed, _i32, _vp, _vp, _vp, _vp,
                                            ctypes.c_size_t, _vp]),
     "irec_decode_tensors_supported": (_i32, [_PP, _i32, _i32]),
-    "irec_beam_decode_tensors": (ctypes.c_int, [_vp, _PP, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
+    "irec_beam_decode_tensors": (ctypes.c_int, [_vp, _PP, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _seed, _i32, _vp, _vp, _vp, _vp,
                                                 ctypes.c_size_t, _vp]),
     "irec_normal_table_floats": (ctypes.c_size_t, [_i32, _i32, _i32]),
-    "irec_normal_table_build": (ctypes.c_int, [_i64, _i32, _i32, _i32, _vp, _i32]),
+    "irec_normal_table_build": (ctypes.c_int, [_seed, _i32, _i32, _i32, _vp, _i32]),
     "irec_gc_importance_encode": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables),
                                                  ctypes.c_float, _i32, _vp, _vp, _vp, _vp]),
     "irec_gc_encode_workspace_bytes": (ctypes.c_size_t, [_vp, _i64, _i32]),
     "irec_gc_importance_encode_ws": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables),
                                                     ctypes.c_float, _i32, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "irec_gumbel_table_floats": (ctypes.c_size_t, [_i32, _i32]),
-    "irec_gumbel_table_build": (ctypes.c_int, [_i64, _i32, _i32, _vp, _i32]),
+    "irec_gumbel_table_build": (ctypes.c_int, [_seed, _i32, _i32, _vp, _i32]),
     "irec_gc_importance_encode_gumbel": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(IrecNormalTables),
                                                         ctypes.c_float, _i32, _vp, _vp, _vp, _vp, ctypes.c_size_t,
                                                         ctypes.POINTER(IrecGumbelTable), _vp]),
@@ -238,7 +276,7 @@ SIGNATURES = {
     "irec_quality_host": (ctypes.c_int, [_vp, _vp] + [_i32] * 5 + [ctypes.POINTER(IrecQualityParams), _vp, _vp, _i32]),
     "irec_decode_rows_status": (ctypes.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "irec_test_rows_status_host": (ctypes.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
-    "irec_device_uniform_int": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    "irec_device_uniform_int": (ctypes.c_int, [_vp, _seed, _i64, _vp, _vp]),
     "irec_shim_stats": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "irec_shim_cat_elu": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "irec_shim_residual_elu": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
@@ -246,7 +284,7 @@ SIGNATURES = {
     "irec_test_reduce_scatter": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp]),
     "irec_test_select": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "irec_test_select_quick": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
-    "irec_test_proposal_table": (ctypes.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "irec_test_proposal_table": (ctypes.c_int, [_vp, _seed, _i32, _i32, _i32, _vp, _vp]),
     "irec_device_tables": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                           ctypes.POINTER(_vp)]),
 }

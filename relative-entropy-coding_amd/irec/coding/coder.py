@@ -502,6 +502,7 @@ class GaussianCoder(Coder):
     def _encode_block_host(self, target_dist, coding_dist, seed):
         """coder.py:497-559 in the notation of DESIGN.md §3 (cv, tv, a): K - 1 auxiliary variables, then the block's sample, every
         draw through `self.sampler.coded_sample`."""
+        seed = _lib.seed64(seed, coding=True)              # (the step seeds seed + t are formed here, not in the library)
         mq, sq, mp, sp = (self._host(t) for t in (target_dist.loc, target_dist.scale, coding_dist.loc, coding_dist.scale))
         device = torch.as_tensor(target_dist.loc).device
         picked, self.last_path = [], "host"
@@ -524,6 +525,7 @@ class GaussianCoder(Coder):
 
     def _decode_block_host(self, coding_dist, indices, seed):
         """coder.py:561-584: the p recursion alone, indices read in encoder order (the caller's list is not touched)."""
+        seed = _lib.seed64(seed, coding=True)
         mp, sp = self._host(coding_dist.loc), self._host(coding_dist.scale)
         device = torch.as_tensor(coding_dist.loc).device
         n, self.last_path = len(indices), "host"

@@ -79,7 +79,7 @@ class ImportanceSampler(Sampler):
         out = np.empty_like(pl)
         idx = ctypes.c_int64(-1)
         _lib.check(_lib.load().irec_importance_encode(_ptr(tl), _ptr(ts), _ptr(pl), _ptr(ps), pl.size,
-                                                      float(self.coding_bits), float(self.alpha), int(seed),
+                                                      float(self.coding_bits), float(self.alpha), _lib.seed64(seed),
                                                       ctypes.byref(idx), _ptr(out)),
                    "irec_importance_encode")
         return int(idx.value), torch.from_numpy(out).reshape(loc.shape).to(loc.device)
@@ -89,7 +89,7 @@ class ImportanceSampler(Sampler):
         loc = torch.as_tensor(coder.loc)
         pl, ps = _host_f32(coder.loc), _host_f32(coder.scale)
         out = np.empty_like(pl)
-        _lib.check(_lib.load().irec_importance_decode(_ptr(pl), _ptr(ps), pl.size, int(sample_index), int(seed), _ptr(out)),
+        _lib.check(_lib.load().irec_importance_decode(_ptr(pl), _ptr(ps), pl.size, int(sample_index), _lib.seed64(seed), _ptr(out)),
                    "irec_importance_decode")
         return torch.from_numpy(out).reshape(loc.shape).to(loc.device)
 

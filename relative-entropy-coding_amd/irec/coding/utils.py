@@ -15,5 +15,5 @@ def stateless_gumbel_sample(shape, seed):
     from .. import _lib
     n = int(np.prod(shape))
     g = np.empty(n, dtype=np.float32)
-    _lib.check(_lib.load().irec_tf_stateless_gumbel(int(seed), n, g.ctypes.data_as(ctypes.c_void_p)), "irec_tf_stateless_gumbel")
+    _lib.check(_lib.load().irec_tf_stateless_gumbel(_lib.seed64(seed), n, g.ctypes.data_as(ctypes.c_void_p)), "irec_tf_stateless_gumbel")
     return g.reshape(shape)

@@ -23,7 +23,7 @@ def _ptr(t):
 def tf_shuffle_perm(seed, n):
     """tf.random.set_seed(seed); tf.random.shuffle(tf.range(n))  (reference: coder.py:62-64).  Host numpy int64."""
     perm = np.empty(n, dtype=np.int64)
-    _lib.check(_lib.load().irec_tf_shuffle_perm(int(seed), int(n), perm.ctypes.data_as(ctypes.c_void_p)),
+    _lib.check(_lib.load().irec_tf_shuffle_perm(_lib.seed64(seed), int(n), perm.ctypes.data_as(ctypes.c_void_p)),
                "irec_tf_shuffle_perm")
     return perm
 
@@ -36,7 +36,7 @@ def build_lut():
 
 def philox_uniform_int(seed, n):
     out = np.empty(n, dtype=np.int32)
-    _lib.check(_lib.load().irec_philox_uniform_int(int(seed), int(n), out.ctypes.data_as(ctypes.c_void_p)),
+    _lib.check(_lib.load().irec_philox_uniform_int(_lib.seed64(seed), int(n), out.ctypes.data_as(ctypes.c_void_p)),
                "irec_philox_uniform_int")
     return out
 
@@ -55,7 +55,7 @@ def build_normal_table(seed, n_samples, dim, steps, n_threads=0):
     s_pad = -(-int(n_samples) // _lib.IREC_NORMAL_TABLE_PAD) * _lib.IREC_NORMAL_TABLE_PAD
     out = np.empty((int(steps), int(dim), s_pad), dtype=np.float32)
     assert out.size == n
-    _lib.check(lib.irec_normal_table_build(int(seed), int(n_samples), int(dim), int(steps), out.ctypes.data_as(ctypes.c_void_p),
+    _lib.check(lib.irec_normal_table_build(_lib.seed64(seed), int(n_samples), int(dim), int(steps), out.ctypes.data_as(ctypes.c_void_p),
                                            int(n_threads)), "irec_normal_table_build")
     return out
 
@@ -71,7 +71,7 @@ def build_gumbel_table(seed, n_samples, steps, n_threads=0):
     s_pad = -(-int(n_samples) // _lib.IREC_NORMAL_TABLE_PAD) * _lib.IREC_NORMAL_TABLE_PAD
     out = np.empty((int(steps), s_pad), dtype=np.float32)
     assert out.size == n
-    _lib.check(lib.irec_gumbel_table_build(int(seed), int(n_samples), int(steps), out.ctypes.data_as(ctypes.c_void_p), int(n_threads)),
+    _lib.check(lib.irec_gumbel_table_build(_lib.seed64(seed), int(n_samples), int(steps), out.ctypes.data_as(ctypes.c_void_p), int(n_threads)),
                "irec_gumbel_table_build")
     return out
 
@@ -392,7 +392,7 @@ class Engine:
             session["key"] = None
         _lib.check(self.lib.irec_beam_encode_ex(self.ctx, ctypes.byref(params), lay.n_blocks, _ptr(lay.block_base),
                                                 _ptr(lay.block_pos), _ptr(lay.block_dim), lay.max_dim, _ptr(lay.perm),
-                                                _ptr(q_loc), _ptr(q_scale), _ptr(p_loc), _ptr(p_scale), int(seed),
+                                                _ptr(q_loc), _ptr(q_scale), _ptr(p_loc), _ptr(p_scale), _lib.seed64(seed),
                                                 int(max_K), _ptr(out_K), _ptr(out_idx), _ptr(sample), _ptr(margin), _ptr(ws),
                                                 ws.numel(), self._stream()), "irec_beam_encode_ex")
         return out_K, out_idx, sample, margin
@@ -445,7 +445,7 @@ class Engine:
             session["key"] = None      # (until the call below has been issued: an error leaves nothing to trust)
         _lib.check(self.lib.irec_beam_encode(self.ctx, ctypes.byref(params), lay.n_blocks, _ptr(lay.block_base),
                                              _ptr(lay.block_pos), _ptr(lay.block_dim), lay.max_dim, _ptr(lay.perm),
-                                             _ptr(q_loc), _ptr(q_scale), _ptr(p_loc), _ptr(p_scale), int(seed),
+                                             _ptr(q_loc), _ptr(q_scale), _ptr(p_loc), _ptr(p_scale), _lib.seed64(seed),
                                              int(max_K), _ptr(out_K), _ptr(out_idx), _ptr(sample), _ptr(ws),
                                              ws.numel(), self._stream()), "irec_beam_encode")
         if session is not None:
@@ -506,7 +506,7 @@ class Engine:
             ws = self._decode_ws(tparams, max_K)
             _lib.check(self.lib.irec_beam_decode_tensors(self.ctx, ctypes.byref(tparams), lay.n_tensors, lay.n, bs_eff,
                                                          _ptr(lay.natural_dev() if block_row is None else block_row), _ptr(lay.perm), _ptr(p_loc), _ptr(p_scale),
-                                                         int(seed), max_K, _ptr(K), _ptr(indices), _ptr(sample), _ptr(ws),
+                                                         _lib.seed64(seed), max_K, _ptr(K), _ptr(indices), _ptr(sample), _ptr(ws),
                                                          ws.numel() if ws is not None else 0, self._stream()),
                        "irec_beam_decode_tensors")
             return sample
@@ -519,14 +519,14 @@ class Engine:
                 raise ValueError(f"unknown decode mode {mode!r}")
             _lib.check(self.lib.irec_beam_decode(self.ctx, ctypes.byref(params), lay.n_blocks, _ptr(lay.block_base),
                                                  _ptr(lay.block_pos), _ptr(lay.block_dim), _ptr(lay.perm), _ptr(p_loc),
-                                                 _ptr(p_scale), int(seed), max_K, _ptr(K), _ptr(indices),
+                                                 _ptr(p_scale), _lib.seed64(seed), max_K, _ptr(K), _ptr(indices),
                                                  _ptr(sample), self._stream()), "irec_beam_decode")
             return sample
         params = self.with_table_dims(params, lay)
         ws = self._decode_ws(params, max_K)
         _lib.check(self.lib.irec_beam_decode_ws(self.ctx, ctypes.byref(params), lay.n_blocks, _ptr(lay.block_base),
                                                 _ptr(lay.block_pos), _ptr(lay.block_dim), lay.max_dim, _ptr(lay.perm),
-                                                _ptr(p_loc), _ptr(p_scale), int(seed), max_K, _ptr(K), _ptr(indices),
+                                                _ptr(p_loc), _ptr(p_scale), _lib.seed64(seed), max_K, _ptr(K), _ptr(indices),
                                                 _ptr(sample), _ptr(ws), ws.numel() if ws is not None else 0,
                                                 self._stream()), "irec_beam_decode_ws")
         return sample
@@ -669,14 +669,14 @@ class Engine:
     # ---- test hooks ------------------------------------------------------------------------------------------------
     def device_uniform_int(self, seed, n):
         out = torch.empty(n, dtype=torch.int32, device=self.device)
-        _lib.check(self.lib.irec_device_uniform_int(self.ctx, int(seed), int(n), _ptr(out), self._stream()),
+        _lib.check(self.lib.irec_device_uniform_int(self.ctx, _lib.seed64(seed), int(n), _ptr(out), self._stream()),
                    "irec_device_uniform_int")
         return out
 
     def test_proposal_table(self, seed, n_samples, dim, n_steps):
         dp = (dim + 3) // 4 * 4
         out = torch.zeros((n_steps, n_samples, dp), dtype=torch.int16, device=self.device)
-        _lib.check(self.lib.irec_test_proposal_table(self.ctx, int(seed), int(n_samples), int(dim), int(n_steps), _ptr(out),
+        _lib.check(self.lib.irec_test_proposal_table(self.ctx, _lib.seed64(seed), int(n_samples), int(dim), int(n_steps), _ptr(out),
                                                      self._stream()), "irec_test_proposal_table")
         return out
 

@@ -21,7 +21,7 @@ import torch
 
 from . import sharding
 from .coding import CodingError
-from .io import decode_files, decode_files_device, encode_files, read_compressed_code, rec_header_words, write_compressed_code
+from .io import decode_files, decode_files_device, encode_files, header_seed, read_compressed_code, rec_header_words, write_compressed_code
 from .models.resnet_vae import STATUS_RESIDUAL, status_text
 
 
@@ -194,6 +194,7 @@ def compress_images(model, images, names, seed, block_size, out_dir, batch=None,
     decompress_images_tables reads them.  The per-image form and the lossless pair keep the default models (ValueError)."""
     if tables is not None and (lossless or not (rec_on_device or (packed and hasattr(model, "compress_packed")))):
         raise ValueError("compress_images: tables go with the packed host leg or rec_on_device, not with lossless or packed=False")
+    seed = header_seed(seed, "compress_images")            # (before out_dir is made or a batch coded: no leg could write this seed)
     os.makedirs(out_dir, exist_ok=True)
     n = images.shape[0]
     batch = n if not batch else int(batch)
@@ -397,6 +398,7 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
     from .io import decode_files_device_ragged, decode_files_device_segmented, decode_files_ragged, decode_files_segmented
     if segment_blocks is not None and tables is not None:
         raise ValueError("compress_images_lossy: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
+    seed = header_seed(seed, "compress_images_lossy")      # (before out_dir is made or a batch coded)
     os.makedirs(out_dir, exist_ok=True)
     n = images.shape[0]
     batch = n if not batch else int(batch)

@@ -27,6 +27,21 @@ from .entropy_coding import ArithmeticCoder
 _STATIC = struct.Struct("IIIIIHHHH")
 
 
+def header_seed(seed, who):
+    """The seed as the uint32 header field of a .rec / .recs file holds it, or ValueError: a file can only name a coding seed in
+    [0, 2^32), and decompress codes under the seed it reads -- the coders take any int64, and ctypes would wrap one silently into the
+    field (2^32 + 5 -> 5, -1 -> 4294967295: a file that decodes to another image without an error).  THE check of every writer, host
+    and device, and of the drivers above them, which call it before they code anything."""
+    try:
+        value = _lib.seed_int(seed)
+    except ValueError as e:
+        raise ValueError(f"{who}: {e} (the seed of a .rec header: an integer in [0, 2^32))")
+    if not 0 <= value <= _lib.HEADER_SEED_MAX:
+        raise ValueError(f"{who}: seed {value} does not fit the uint32 seed field of a .rec header: a seed that goes into a file "
+                         f"must lie in [0, 2^32) = [0, {_lib.HEADER_SEED_MAX}]")
+    return value
+
+
 def _uniform_model(n_values: int, weight: int) -> np.ndarray:
     """Terminator count 1, every value symbol `1 + weight` (utils.py:31-35 with weight 1000, :41-47 with weight 100)."""
     model = np.full(n_values + 1, 1 + weight, dtype=np.int64)
@@ -81,7 +96,7 @@ class RecHeader:
         r = len(self.blocks_per_res_block)
         tail = [*self.blocks_per_res_block, *self.count_stream_bytes, *self.index_stream_bytes,
                 *[m & 0xFFFFFFFF for m in self.max_partitions]]
-        return _STATIC.pack(self.seed, self.block_size, self.max_index, *self.image_shape, int(self.uses_count_file),
+        return _STATIC.pack(header_seed(self.seed, "RecHeader.pack"), self.block_size, self.max_index, *self.image_shape, int(self.uses_count_file),
                             int(self.uses_index_file), r) + struct.pack(f"{4 * r}I", *tail)
 
     @classmethod
@@ -95,6 +110,7 @@ class RecHeader:
 def _native_encode(seed, image_shape, block_size, block_indices, max_index):
     """The whole container in one C++ call (irec_rec_encode_file): default symbol models only."""
     lib = _lib.load()
+    seed = header_seed(seed, "write_compressed_code")
     bpr = np.array([len(rb) for rb in block_indices], dtype=np.int32)
     K = np.array([len(ix) for rb in block_indices for ix in rb], dtype=np.int32)
     flat = np.fromiter(itertools.chain.from_iterable(itertools.chain.from_iterable(block_indices)), dtype=np.int32,
@@ -102,7 +118,7 @@ def _native_encode(seed, image_shape, block_size, block_indices, max_index):
     h, w, c = (int(v) for v in image_shape)
 
     def call(out):
-        n = lib.irec_rec_encode_file(int(seed), int(block_size), int(max_index), h, w, c, len(bpr), bpr.ctypes.data,
+        n = lib.irec_rec_encode_file(seed, int(block_size), int(max_index), h, w, c, len(bpr), bpr.ctypes.data,
                                      K.ctypes.data, flat.ctypes.data if flat.size else None, out.ctypes.data, out.size)
         if n < 0:
             raise ValueError(lib.irec_io_last_error().decode())
@@ -265,6 +281,7 @@ def _block_rows(K, idx):
 def _encode_rows_host(seed, image_shape, block_size, K, idx, max_index, layout, n_threads, tables, who):
     """irec_rec_encode_files[_ragged|_tables|_segmented] over contiguous rows: (blob uint8, offsets int64 [N + 1])."""
     lib = _lib.load()
+    seed = header_seed(seed, who)
     n, max_K = K.shape[0], idx.shape[2]
     h, w, c = (int(v) for v in image_shape)
     suffix, blocks = layout.entry(tables)
@@ -280,7 +297,7 @@ def _encode_rows_host(seed, image_shape, block_size, K, idx, max_index, layout, 
         cap = n * (64 + 16 * layout.R) + 2 * int(K.sum()) + 16 * K.size + 1024
 
     def call(out):
-        total = encode(int(seed), int(block_size), int(max_index), h, w, c, n, layout.R, *blocks, max_K, K.ctypes.data,
+        total = encode(seed, int(block_size), int(max_index), h, w, c, n, layout.R, *blocks, max_K, K.ctypes.data,
                        idx.ctypes.data if idx.size else None, *tb, out.ctypes.data, out.size, offsets.ctypes.data,
                        *((status.ctypes.data,) if newer else ()), int(n_threads))
         if total < 0:
@@ -414,6 +431,7 @@ def _encode_rows_device_launch(seed, image_shape, block_size, K, idx, max_index,
     offsets[N] <= out.numel()."""
     import torch
     lib = _lib.load()
+    seed = header_seed(seed, who)                      # (before anything is launched: _row_strides may copy)
     n, max_K = K.shape[0], idx.shape[2]
     h, w, c = (int(v) for v in image_shape)
     K, ks, idx, ist = _row_strides(K, idx)
@@ -424,7 +442,7 @@ def _encode_rows_device_launch(seed, image_shape, block_size, K, idx, max_index,
         offsets, status, both = _files.offsets_and_status(n, dev)
         tb = () if tables is None else tables.to(dev).device_args(layout.R, who)
         st = getattr(lib, "irec_rec_encode_files_device" + suffix)(
-            int(seed), int(block_size), int(max_index), h, w, c, n, layout.R, *blocks, max_K, K.data_ptr(), ks,
+            seed, int(block_size), int(max_index), h, w, c, n, layout.R, *blocks, max_K, K.data_ptr(), ks,
             idx.data_ptr() if idx.numel() else None, ist, *tb, out.data_ptr() if out.numel() else None, out.numel(), offsets.data_ptr(),
             status.data_ptr() if n else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
     _files.check_status(st, "irec_rec_encode_files_device" + suffix)
@@ -508,6 +526,7 @@ def encode_files_device(seed, image_shape, block_size, K, idx, max_index, out=No
     CUDA tensors, byte for byte what encode_files gives; the only host synchronisation is ONE read-back of offsets and status.
     out: a CUDA uint8 buffer to write into (a short one costs a second run at the size the first one reports)."""
     import torch
+    seed = header_seed(seed, "encode_files_device")    # (here as well: _block_rows below may copy on the device)
     if not (K.is_cuda and idx.is_cuda and K.dtype == torch.int32 and idx.dtype == torch.int32):
         raise ValueError("encode_files_device takes CUDA int32 tensors")
     if K.dim() != 3 or idx.dim() != 4 or tuple(idx.shape[:3]) != tuple(K.shape):
@@ -603,6 +622,7 @@ def write_compressed_code(file_path, seed, image_shape, block_size, block_indice
     path below is the reference-shaped one (byte-identical, tests/test_rec_io.py) and serves the count-file variants."""
     if len(image_shape) != 3:
         raise ValueError(f"Image shape must be rank 3, but was {image_shape}!")
+    seed = header_seed(seed, "write_compressed_code")      # (before the file is opened: a refused seed leaves nothing behind)
     if num_aux_var_counts_file is None and index_counts_file is None and len(block_indices) > 0 and \
             all(len(rb) > 0 for rb in block_indices):
         with open(file_path, "wb") as fh:
@@ -615,6 +635,7 @@ def write_compressed_code(file_path, seed, image_shape, block_size, block_indice
 def _write_compressed_code_py(file_path, seed, image_shape, block_size, block_indices, max_index,
                               num_aux_var_counts_file=None, index_counts_file=None):
     """The reference-shaped writer: one ArithmeticCoder call per stream (rec/io/utils.py:7-106)."""
+    seed = header_seed(seed, "write_compressed_code")
     partition_counts = [[len(ix) for ix in res_block] for res_block in block_indices]
     flat_indices = [np.concatenate([np.asarray(ix, dtype=np.int64).reshape(-1) for ix in res_block])
                     for res_block in block_indices]

@@ -64,9 +64,12 @@ def packed_rows(n, blocks_per_res, device):
 
 
 def header_want(seed, image_shape, n_res_blocks, device):
-    """The header words (seed, height, width, channels, R) a file of this call must carry, int64 on the device."""
+    """The header words (seed, height, width, channels, R) a file of this call must carry, int64 on the device.  A seed that no header
+    holds (outside [0, 2^32)) is wanted as -1, which no file carries: every file then has STATUS_HEADER, instead of the files whose
+    seed equals the call's low 32 bits being decoded under another seed."""
     _, c, h, w = (int(v) for v in image_shape)
-    words = [int(seed) & 0xFFFFFFFF, h, w, c, int(n_res_blocks)]
+    seed = int(seed)
+    words = [seed if 0 <= seed <= 0xFFFFFFFF else -1, h, w, c, int(n_res_blocks)]
     return _cached(_WANT_CACHE, (*words, str(device)), lambda: torch.tensor(words, dtype=torch.int64).to(device))
 
 

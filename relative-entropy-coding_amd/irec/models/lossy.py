@@ -14,7 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..coding.pending import PendingCode, recode
-from ..io import read_compressed_code, write_compressed_code
+from ..io import header_seed, read_compressed_code, write_compressed_code
 from ._rec_rows import STATUS_ROWS, finish, header_want, join_status, packed_rows, read_rows
 from .resnet_vae import ModelError, _Normal, _nchw, _nhwc, deterministic_transforms
 
@@ -93,6 +93,7 @@ class Large2LevelVAE(nn.Module):
 
     def compress(self, file_path, image, seed, sampler, block_size, max_index):
         """large_2_level_vae.py:406-419.  image: [H, W, 3] tensor (the reference's layout)."""
+        seed = header_seed(seed, "compress")               # (before anything is coded: the file could not name another seed)
         sampling_fn = lambda target, coder: sampler.encode(target, coder, seed=seed)  # noqa: E731  (:408)
         x = image.permute(2, 0, 1)[None].contiguous()
         with deterministic_transforms():
@@ -167,6 +168,7 @@ class Large2LevelVAE(nn.Module):
         encode_files_device_segmented with rec_on_device), which decompress_rec reads under the same segment_blocks.  Default symbol
         models only: together with tables it is a ValueError."""
         from ..io import encode_files_device_ragged, encode_files_device_segmented, encode_files_ragged, encode_files_segmented
+        seed = header_seed(seed, "compress_rec")           # (before anything is coded: the files could not name another seed)
         if segment_blocks is not None and tables is not None:
             raise ValueError("compress_rec: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
         _, _, height, width = images.shape

@@ -404,8 +404,9 @@ class BidirectionalResNetVAE(nn.Module):
         segment_blocks: None for the reference's file; g >= 1 for the segmented container (NAME.recs, INTEGRATION.md §8: every residual
         block's rows in segments of g coder blocks, one lane per stream of a segment -- irec.io.encode_files_device_segmented), which
         decompress_rec_segmented reads.  Default symbol models only: together with tables it is a ValueError."""
-        from ..io import encode_files_device, encode_files_device_segmented
+        from ..io import encode_files_device, encode_files_device_segmented, header_seed
         from ..io.utils import _block_rows
+        seed = header_seed(seed, "compress_rec")           # (before anything is coded: the files could not name another seed)
         if segment_blocks is not None and tables is not None:
             raise ValueError("compress_rec: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
         _, _, height, width = image.shape

@@ -183,6 +183,39 @@ def enumerate_plans(n_cu=256, dims=DIMS, blocks=BLOCKS, accept=None):
     return best
 
 
+# ---- the encoder families (tests/test_memory_contract_gpu.py section B, tests/test_seed_domain_gpu.py) ----------------------------
+def template_args(name):
+    return name[name.index("<") + 1:-1].split(",") if "<" in name else []
+
+
+# family -> (canonical name, its template arguments) -> whether the build belongs to it: one entry per way an encoder keeps its state
+FAMILIES = {
+    "split fast": lambda n, a: n.startswith("encode_fast_kernel<") and a[3] != "0",
+    "team, shared rows": lambda n, a: n.startswith("encode_team_kernel<") and a[5] == "true",
+    "chunk gang": lambda n, a: n.startswith("encode_chunk_kernel<") and a[3] == "true",
+    "team": lambda n, a: n.startswith("encode_team_kernel<") and a[5] == "false" and a[6] == "false",
+    "ten": lambda n, a: n.startswith("encode_ten_kernel<"),
+    "lone": lambda n, a: n == "encode_lone_kernel",
+    "one-table fast": lambda n, a: n.startswith("encode_fast_kernel<") and a[2] == "true" and a[3] == "0",
+    "chunk": lambda n, a: n.startswith("encode_chunk_kernel<") and a[3] == "false",
+    "generic": lambda n, a: n == "encode_generic_kernel",
+}
+
+
+def family_id(family):
+    return family.replace(" ", "_").replace(",", "")
+
+
+def family_members(plans, family):
+    """The names of `plans` (enumerate_plans) that belong to a family, cheapest planned call first."""
+    return sorted((n for n in plans if FAMILIES[family](n, template_args(n))), key=lambda n: (plans[n]["cost"], n))
+
+
+def family_names(plans):
+    """[(family, the name of its cheapest planned call, or None where the planner names no kernel of the family)]."""
+    return [(family, (family_members(plans, family) or [None])[0]) for family in FAMILIES]
+
+
 # ---- the corner calls of a name (tests/test_kernel_corners.py) -------------------------------------------------------------------
 SEED = 42                                  # the coding seed of every corner call
 BUDGET = 4e8                               # proposal evaluations per call, at most: scripts/soak_parity.py's per-block cap

@@ -213,33 +213,12 @@ def test_one_item_per_compiled_encoder():
 
 
 # ---- B ----
-def _template_args(name):
-    return name[name.index("<") + 1:-1].split(",") if "<" in name else []
-
-
-_FAMILIES = {
-    "split fast": lambda n, a: n.startswith("encode_fast_kernel<") and a[3] != "0",
-    "team, shared rows": lambda n, a: n.startswith("encode_team_kernel<") and a[5] == "true",
-    "chunk gang": lambda n, a: n.startswith("encode_chunk_kernel<") and a[3] == "true",
-    "team": lambda n, a: n.startswith("encode_team_kernel<") and a[5] == "false" and a[6] == "false",
-    "ten": lambda n, a: n.startswith("encode_ten_kernel<"),
-    "lone": lambda n, a: n == "encode_lone_kernel",
-    "one-table fast": lambda n, a: n.startswith("encode_fast_kernel<") and a[2] == "true" and a[3] == "0",
-    "chunk": lambda n, a: n.startswith("encode_chunk_kernel<") and a[3] == "false",
-    "generic": lambda n, a: n == "encode_generic_kernel",
-}
-
-
 def _family_names():
     try:
         plans = _plans()
     except Exception:
         return []
-    out = []
-    for family, pred in _FAMILIES.items():
-        hits = [n for n in plans if pred(n, _template_args(n))]
-        out.append(pytest.param(min(hits, key=lambda n: (plans[n]["cost"], n)) if hits else None, id=family.replace(" ", "_").replace(",", "")))
-    return out
+    return [pytest.param(name, id=kn.family_id(family)) for family, name in kn.family_names(plans)]
 
 
 @pytest.mark.parametrize("name", _family_names())

@@ -156,6 +156,40 @@ def test_hip_equals_reference_python_on_48_random_blocks(engine):
         assert np.allclose(got, RAND[f"b{k}_sample"], rtol=0, atol=1e-5 * max(1.0, float(np.abs(got).max()))), k
 
 
+SEED_CORNERS = np.load(os.path.join(GOLDEN_DIR, "refpy_seed_corners.npz"))
+
+
+@pytest.mark.both_suites
+@pytest.mark.usefixtures("suite")
+def test_oracle_equals_reference_python_at_the_seed_corners(oracle):
+    """tests/golden/make_golden_refpy_seeds.py: the reference's encode_block / decode_block on the 64-dim block of tests/seed_cases.py at
+    the seeds M - 3 (its zero step, seed + 3 = 0 mod M, inside the block's ten steps), 2^31, -1 and 2^40 + 5.  This pins the reference's
+    PYTHON seed arithmetic -- `seed + iteration` on an int of any size, given to tf.random.set_seed and to the op seed -- which the
+    oracle restates in int64; it does not pin the Philox primitives or TensorFlow's truncation of the seed pair mod 2^31 - 1: the
+    stubs the reference ran over take those from the oracle itself (tests/test_tf_vectors.py and tests/test_tf_doc_kats.py pin them)."""
+    import seed_cases as SC
+    M = 2 ** 31 - 1
+    seeds = [int(s) for s in SEED_CORNERS["seeds"]]
+    assert seeds == [M - 3, 2 ** 31, -1, 2 ** 40 + 5] and set(seeds) <= set(SC.SEEDS)
+    omega, eps1, B = (float(v) for v in SEED_CORNERS["settings"])
+    S, B = int(SEED_CORNERS["n_samples"]), int(B)
+    assert S == oracle.n_samples(omega, eps1) == 20
+    mq, sq, mp, sp = SEED_CORNERS["inputs"]
+    assert all(np.array_equal(a, b[0]) for a, b in zip((mq, sq, mp, sp), SC.inputs(64, 1)))     # the block the seed tests code
+    seen = []
+    for k, seed in enumerate(seeds):
+        want = SEED_CORNERS[f"s{k}_indices"].tolist()
+        assert len(want) >= SC.MIN_K
+        for mode in (oracle.CANONICAL, oracle.LITERAL):
+            idx, sample = oracle.encode_block(mq, sq, mp, sp, seed, omega, S, B, mode=mode)
+            assert idx == want, (seed, mode)
+            assert np.allclose(sample, SEED_CORNERS[f"s{k}_sample"], rtol=0, atol=1e-5 * max(1.0, float(np.abs(sample).max()))), (seed, mode)
+        dec = oracle.decode_block(mp, sp, want, seed, S)
+        assert np.allclose(dec, SEED_CORNERS[f"s{k}_decoded"], rtol=0, atol=1e-5 * max(1.0, float(np.abs(dec).max()))), seed
+        seen.append(want)
+    assert len({tuple(w) for w in seen}) == len(seeds)              # (four streams, not one)
+
+
 @pytest.mark.skipif(not os.path.isdir("/root/reference/rec/coding"), reason="live run needs the reference checkout (build container only)")
 def test_reference_python_live_on_fresh_blocks(oracle):
     """The reference's encode_block / decode_block executed NOW (numpy TF stub) on random blocks of the four settings."""
