@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "irec_call.h"
 #include "irec_device.h"
 #include "irec_internal.h"
 #include "irec_kernels.h"
@@ -393,13 +394,7 @@ hipError_t launch_fit_rows(const FitRowsArgs &A, int grid, hipStream_t st) {
 //  C ABI
 // ================================================================================================================================
 // (irec_host.cpp: the calling thread's irec_last_error text, and what the launches need to know of a context)
-namespace irec { irec_status set_last_error(irec_status code, const char *who, const char *what); int context_device(const irec_context *ctx); int context_cus(const irec_context *ctx); }
-
-#define FIT_HIP(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return irec::set_last_error(IREC_E_HIP, #expr, hipGetErrorString(e_));         \
-  } while (0)
+namespace irec { int context_device(const irec_context *ctx); int context_cus(const irec_context *ctx); }
 
 extern "C" {
 
@@ -515,19 +510,19 @@ irec_status irec_fit_partitions(irec_context *ctx, float kl_per_partition, int64
   const FitLayout L = fit_layout(n_rows, dim);
   if (workspace_bytes < L.bytes) return set_last_error(IREC_E_WORKSPACE, who, "workspace smaller than irec_fit_workspace_bytes()");
   int prev = -1;
-  FIT_HIP(hipGetDevice(&prev));
+  IREC_HIP(hipGetDevice(&prev));
   const int dev = context_device(ctx);
-  if (prev != dev) FIT_HIP(hipSetDevice(dev));
+  if (prev != dev) IREC_HIP(hipSetDevice(dev));
   struct Back { int prev, dev; ~Back() { if (prev != dev) (void)hipSetDevice(prev); } } back{prev, dev};
   hipStream_t st = (hipStream_t)hip_stream;
   char *ws = (char *)workspace;
   FitRowsArgs A{};
   A.mq = q_loc; A.sq = q_scale; A.mp = p_loc; A.sp = p_scale; A.sel = nullptr; A.n_sel = (int32_t)n_rows; A.D = dim;
   A.tot = (double *)(ws + L.tot); A.kl = (float *)(ws + L.kl); A.num = (int32_t *)(ws + L.num); A.omega = kl_per_partition;
-  FIT_HIP(launch_fit_rows(A, (int)std::min<int64_t>(n_rows, 8LL * std::max(1, context_cus(ctx))), st));
-  FIT_HIP(hipMemcpyAsync(out_kl, A.kl, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
-  FIT_HIP(hipMemcpyAsync(out_num, A.num, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
-  FIT_HIP(hipStreamSynchronize(st));
+  IREC_HIP(launch_fit_rows(A, (int)std::min<int64_t>(n_rows, 8LL * std::max(1, context_cus(ctx))), st));
+  IREC_HIP(hipMemcpyAsync(out_kl, A.kl, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
+  IREC_HIP(hipMemcpyAsync(out_num, A.num, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
+  IREC_HIP(hipStreamSynchronize(st));
   return IREC_OK;
 } catch (const std::exception &e) { return irec::set_last_error(IREC_E_INVALID, "irec_fit_partitions", e.what()); }
 
@@ -556,19 +551,19 @@ irec_status irec_fit_aux_ratios(irec_context *ctx, const irec_fit_params *p, int
   if (std::max(M, cur) > capacity) return set_last_error(IREC_E_INVALID, who, "capacity smaller than the partitions the rows need");
   if (M > 1 && (!normal_table || table_steps < M - 1 || !out_iters)) return set_last_error(IREC_E_INVALID, who, "the normal table covers fewer than M - 1 steps");
   int prev = -1;
-  FIT_HIP(hipGetDevice(&prev));
+  IREC_HIP(hipGetDevice(&prev));
   const int dev = context_device(ctx);
-  if (prev != dev) FIT_HIP(hipSetDevice(dev));
+  if (prev != dev) IREC_HIP(hipSetDevice(dev));
   struct Back { int prev, dev; ~Back() { if (prev != dev) (void)hipSetDevice(prev); } } back{prev, dev};
   hipStream_t st = (hipStream_t)hip_stream;
   const int n_cu = std::max(1, context_cus(ctx));
   char *ws = (char *)workspace;
   float *mq = (float *)(ws + L.stats[0]), *sq = (float *)(ws + L.stats[1]), *mp = (float *)(ws + L.stats[2]), *sp = (float *)(ws + L.stats[3]);
   if (M > 1) {
-    FIT_HIP(hipMemcpyAsync(mq, q_loc, E * 4, hipMemcpyDeviceToDevice, st));
-    FIT_HIP(hipMemcpyAsync(sq, q_scale, E * 4, hipMemcpyDeviceToDevice, st));
-    FIT_HIP(hipMemcpyAsync(mp, p_loc, E * 4, hipMemcpyDeviceToDevice, st));
-    FIT_HIP(hipMemcpyAsync(sp, p_scale, E * 4, hipMemcpyDeviceToDevice, st));
+    IREC_HIP(hipMemcpyAsync(mq, q_loc, E * 4, hipMemcpyDeviceToDevice, st));
+    IREC_HIP(hipMemcpyAsync(sq, q_scale, E * 4, hipMemcpyDeviceToDevice, st));
+    IREC_HIP(hipMemcpyAsync(mp, p_loc, E * 4, hipMemcpyDeviceToDevice, st));
+    IREC_HIP(hipMemcpyAsync(sp, p_scale, E * 4, hipMemcpyDeviceToDevice, st));
   }
   for (int32_t i = cur; i < M; ++i) { ratios[i] = 0.0f; average_counts[i] = 0.0f; }
   *length = std::max(M, cur);
@@ -581,12 +576,12 @@ irec_status irec_fit_aux_ratios(irec_context *ctx, const irec_fit_params *p, int
     int32_t ns = 0;
     for (int64_t i = 0; i < n; ++i) if (num[i] >= ratio) sel[ns++] = (int32_t)i;
     // (pageable source: the copy has left `sel` when the call returns; the stream is drained before `sel` changes anyway)
-    FIT_HIP(hipMemcpyAsync(ws + L.sel, sel.data(), (size_t)ns * 4, hipMemcpyHostToDevice, st));
+    IREC_HIP(hipMemcpyAsync(ws + L.sel, sel.data(), (size_t)ns * 4, hipMemcpyHostToDevice, st));
     FitRowsArgs R{};
     R.mq = mq; R.sq = sq; R.mp = mp; R.sp = sp; R.sel = (const int32_t *)(ws + L.sel); R.n_sel = ns; R.D = dim;
     R.tot = (double *)(ws + L.tot); R.W = (double *)(ws + L.W); R.S = (double *)(ws + L.S);
     R.state = d_state; R.theta0 = fit_theta0(ratios, ratio, M);
-    FIT_HIP(launch_fit_rows(R, std::min(ns, 8 * n_cu), st));
+    IREC_HIP(launch_fit_rows(R, std::min(ns, 8 * n_cu), st));
     FitIterArgs I{};
     I.state = d_state; I.W = R.W; I.S = R.S; I.tot = R.tot; I.pair = (double *)(ws + L.pair);
     I.n_sel = ns; I.D = dim; I.max_iters = p->max_iters; I.om = om; I.om_rest = om * (double)(ratio - 1);
@@ -596,10 +591,10 @@ irec_status irec_fit_aux_ratios(irec_context *ctx, const irec_fit_params *p, int
     for (int64_t launched = 0; launched < p->max_iters && !hs.done;) {
       const int c = (int)std::min<int64_t>(chunk, p->max_iters - launched);
       for (int i = 0; i < c; ++i) hipLaunchKernelGGL(fit_iter_kernel, dim3(grid), dim3(FIT_NT), 0, st, I);
-      FIT_HIP(hipGetLastError());
+      IREC_HIP(hipGetLastError());
       launched += c;
-      FIT_HIP(hipMemcpyAsync(&hs, d_state, sizeof(hs), hipMemcpyDeviceToHost, st));
-      FIT_HIP(hipStreamSynchronize(st));
+      IREC_HIP(hipMemcpyAsync(&hs, d_state, sizeof(hs), hipMemcpyDeviceToHost, st));
+      IREC_HIP(hipStreamSynchronize(st));
     }
     if (!hs.done) return set_last_error(IREC_E_HIP, who, "a fit step did not finish within max_iters launches");
     out_iters[j] = hs.iters;
@@ -610,9 +605,9 @@ irec_status irec_fit_aux_ratios(irec_context *ctx, const irec_fit_params *p, int
     H.n_sel = ns; H.D = dim; H.S_pad = (int32_t)S_pad; H.r_last = r_last; H.r_avg = r_avg;
     const int64_t hg = ((int64_t)ns * D + FIT_NT - 1) / FIT_NT;
     hipLaunchKernelGGL(fit_handover_kernel, dim3((unsigned)std::min<int64_t>(hg, 16LL * n_cu)), dim3(FIT_NT), 0, st, H);
-    FIT_HIP(hipGetLastError());
+    IREC_HIP(hipGetLastError());
   }
-  FIT_HIP(hipStreamSynchronize(st));   // (the next call may reuse the workspace, and `sel` goes out of scope)
+  IREC_HIP(hipStreamSynchronize(st));   // (the next call may reuse the workspace, and `sel` goes out of scope)
   return IREC_OK;
 } catch (const std::exception &e) { return irec::set_last_error(IREC_E_INVALID, "irec_fit_aux_ratios", e.what()); }
 

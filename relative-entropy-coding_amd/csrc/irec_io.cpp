@@ -8,10 +8,10 @@
 #include <cstring>
 #include <exception>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "irec.h"
+#include "irec_call.h"
 
 namespace {
 thread_local std::string g_io_error;
@@ -324,22 +324,6 @@ irec_status irec_rec_decode_file(const uint8_t *bytes, int64_t n_bytes, uint32_t
 // again with room), -1 on invalid input.
 } // extern "C"
 namespace {
-template <class F>
-void for_each_image(int32_t n_images, int32_t n_threads, F &&body) {
-  int T = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-  T = T < 1 ? 1 : (T > 32 ? 32 : T);
-  if (T > n_images) T = n_images;
-  if (T <= 1) { for (int32_t i = 0; i < n_images; ++i) body(i); return; }
-  std::vector<std::thread> pool;
-  for (int t = 0; t < T; ++t)   // (body() reports through its own error slot and must not throw: an exception leaving a thread ends the process)
-    pool.emplace_back([&, t]() { for (int32_t i = t; i < n_images; i += T) body(i); });
-  for (auto &th : pool) th.join();
-}
-} // namespace
-extern "C" {
-
-} // extern "C"
-namespace {
 // blocks per image of a call's layout, or -1: an entry < 1 or a sum that leaves int32
 int64_t layout_blocks(const std::vector<int32_t> &bpr) {
   int64_t t = 0;
@@ -354,7 +338,8 @@ int64_t encode_files_impl(uint32_t seed, uint32_t block_size, uint32_t max_index
   std::vector<std::vector<uint8_t>> files((size_t)n_images);
   std::vector<std::string> errs((size_t)n_images);
   const int64_t per_img = layout_blocks(bpr);
-  for_each_image(n_images, n_threads, [&](int32_t i) { try {
+  // (an image reports through its own error slot and does not throw: an exception leaving a thread ends the process)
+  const auto image = [&](int64_t i) { try {
     const int32_t *Ki = K + (int64_t)i * per_img;
     std::vector<int32_t> flat;
     flat.reserve((size_t)per_img * 8);
@@ -375,7 +360,8 @@ int64_t encode_files_impl(uint32_t seed, uint32_t block_size, uint32_t max_index
     }
     if (n < 0) { errs[(size_t)i] = g_io_error; return; }
     f.resize((size_t)n);
-  } catch (const std::exception &e) { errs[(size_t)i] = std::string("irec_rec_encode_files: ") + e.what(); } });
+  } catch (const std::exception &e) { errs[(size_t)i] = std::string("irec_rec_encode_files: ") + e.what(); } };
+  irec::parallel_chunks(n_images, n_threads, 1, [&](int64_t lo, int64_t hi) { for (int64_t i = lo; i < hi; ++i) image(i); });
   int64_t total = 0;
   for (int32_t i = 0; i < n_images; ++i) {
     if (!errs[(size_t)i].empty()) { g_io_error = errs[(size_t)i] + " (image " + std::to_string(i) + ")"; return -1; }
@@ -420,7 +406,8 @@ irec_status decode_files_impl(const uint8_t *bytes, const int64_t *offsets, int3
   const int32_t n_res_blocks = (int32_t)want.size();
   std::vector<std::string> errs((size_t)n_images);
   const int64_t per_img = layout_blocks(want);
-  for_each_image(n_images, n_threads, [&](int32_t i) { try {
+  // (an image reports through its own error slot and does not throw: an exception leaving a thread ends the process)
+  const auto image = [&](int64_t i) { try {
     std::vector<int32_t> bpr((size_t)n_res_blocks), flat;
     int64_t sizes[3] = {0, 0, 0};
     int32_t *Ki = K + (int64_t)i * per_img;
@@ -453,7 +440,8 @@ irec_status decode_files_impl(const uint8_t *bytes, const int64_t *offsets, int3
       }
     }
     if (st != IREC_OK) errs[(size_t)i] = g_io_error.empty() ? std::string("irec_rec_decode_files: failed") : g_io_error;
-  } catch (const std::exception &e) { errs[(size_t)i] = std::string("irec_rec_decode_files: ") + e.what(); } });
+  } catch (const std::exception &e) { errs[(size_t)i] = std::string("irec_rec_decode_files: ") + e.what(); } };
+  irec::parallel_chunks(n_images, n_threads, 1, [&](int64_t lo, int64_t hi) { for (int64_t i = lo; i < hi; ++i) image(i); });
   for (int32_t i = 0; i < n_images; ++i)
     if (!errs[(size_t)i].empty()) { g_io_error = errs[(size_t)i] + " (image " + std::to_string(i) + ")"; return IREC_E_INVALID; }
   return IREC_OK;

@@ -11,14 +11,12 @@
 
 #include <cstdint>
 #include <exception>
-#include <thread>
 #include <vector>
 
+#include "irec_call.h"
 #include "irec_quality_core.h"
 
 namespace irec {
-irec_status set_last_error(irec_status code, const char *who, const char *what);   // irec_host.cpp
-
 namespace {
 namespace Q = irec_quality;
 
@@ -84,23 +82,6 @@ size_t workspace_bytes_of(int32_t n, int32_t c, int32_t h, int32_t w, int32_t n_
   return (size_t)(8 * doubles + 4 * floats);
 }
 
-// the blocks of a scale on T host threads (body must not throw)
-struct ThreadedBlocks {
-  int32_t n_threads;
-  template <class F>
-  void operator()(int64_t n, F &&body) const {
-    int64_t T = n_threads > 0 ? n_threads : (int64_t)std::thread::hardware_concurrency();
-    T = T < 1 ? 1 : (T > 32 ? 32 : T);
-    if (T > n / 4) T = n / 4;                                                    // (a thread is not worth fewer than 4 tiles)
-    if (T <= 1) { body((int64_t)0, n); return; }
-    std::vector<std::thread> pool;
-    const int64_t per = (n + T - 1) / T;
-    for (int64_t t = 0; t < T; ++t)
-      pool.emplace_back([&body, t, per, n]() { const int64_t lo = t * per, hi = lo + per < n ? lo + per : n; if (lo < hi) body(lo, hi); });
-    for (auto &th : pool) th.join();
-  }
-};
-
 // IREC_OK, or the argument error of both entries
 irec_status check_args(const char *who, const float *a, const float *b, int32_t n, int32_t c, int32_t h, int32_t w, int32_t n_scales,
                        const irec_quality_params *p, const float *per_scale, const float *sse) {
@@ -110,12 +91,6 @@ irec_status check_args(const char *who, const float *a, const float *b, int32_t 
 }
 } // namespace
 } // namespace irec
-
-#define QUALITY_HIP(expr)                                                                               \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return irec::set_last_error(IREC_E_HIP, #expr, hipGetErrorString(e_));         \
-  } while (0)
 
 extern "C" {
 
@@ -130,8 +105,7 @@ irec_status irec_quality_device(const float *a, const float *b, int32_t n, int32
                                 size_t workspace_bytes, void *hip_stream) {
   using namespace irec;
   if (irec_status st = check_args("irec_quality_device", a, b, n, c, h, w, n_scales, params, per_scale, sse)) return st;
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < workspace_bytes_of(n, c, h, w, n_scales))
-    return set_last_error(IREC_E_WORKSPACE, "irec_quality_device", "workspace too small (irec_quality_workspace_bytes) or not 8-byte aligned");
+  if (irec_status st = check_workspace(workspace_bytes_of(n, c, h, w, n_scales), workspace, workspace_bytes, "irec_quality_device", "irec_quality_workspace_bytes")) return st;
   Q::Call call;
   Q::bind(call, a, b, n, c, h, w, n_scales, params, per_scale, sse, workspace);
   hipStream_t st = (hipStream_t)hip_stream;
@@ -139,10 +113,10 @@ irec_status irec_quality_device(const float *a, const float *b, int32_t n, int32
   for (int32_t k = 0; k < n_scales; ++k) {
     const Q::Level L = Q::level_of(planes, h, w, k);
     hipLaunchKernelGGL(quality_scale_kernel, dim3((unsigned)(planes * L.tiles())), dim3(Q::NT), 0, st, call, k);
-    QUALITY_HIP(hipGetLastError());
+    IREC_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(quality_finish_kernel, dim3((unsigned)Q::n_values(call)), dim3(Q::FINISH_NT), 0, st, call);
-  QUALITY_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   return IREC_OK;
 }
 
@@ -153,7 +127,7 @@ irec_status irec_quality_host(const float *a, const float *b, int32_t n, int32_t
   std::vector<double> ws(workspace_bytes_of(n, c, h, w, n_scales) / 8 + 1);
   Q::Call call;
   Q::bind(call, a, b, n, c, h, w, n_scales, params, per_scale, sse, ws.data());
-  Q::call_host(call, ThreadedBlocks{n_threads});
+  Q::call_host(call, Chunks{n_threads, 4});   // (a thread is not worth fewer than 4 tiles)
   return IREC_OK;
 } catch (const std::exception &e) { return irec::set_last_error(IREC_E_INVALID, "irec_quality_host", e.what()); }
 

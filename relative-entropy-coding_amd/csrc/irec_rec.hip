@@ -147,14 +147,14 @@ irec_status launch_encode(irec_rec::EncodeCall &c, const T &tb, void *workspace,
   if (streams > 0) {
     if constexpr (T::any) hipLaunchKernelGGL(rec_tables_size_kernel, dim3(rec_grid(streams)), dim3(REC_NT), 0, st, c, tb);
     else hipLaunchKernelGGL(rec_size_kernel, dim3(rec_grid(streams)), dim3(REC_NT), 0, st, c);
-    REC_HIP(hipGetLastError());
+    IREC_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(rec_layout_kernel, dim3(1), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   if (streams > 0) {
     if constexpr (T::any) hipLaunchKernelGGL(rec_tables_write_kernel, dim3(rec_grid(streams + c.N)), dim3(REC_NT), 0, st, c, tb);
     else hipLaunchKernelGGL(rec_write_kernel, dim3(rec_grid(streams + c.N)), dim3(REC_NT), 0, st, c);
-    REC_HIP(hipGetLastError());
+    IREC_HIP(hipGetLastError());
   }
   return IREC_OK;
 }
@@ -165,12 +165,12 @@ irec_status launch_decode(const irec_rec::DecodeCall &c, const T &tb, void *hip_
   const int64_t lanes = (int64_t)c.N * c.R;
   if constexpr (T::any) hipLaunchKernelGGL(rec_tables_decode_counts_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c, tb);
   else hipLaunchKernelGGL(rec_decode_counts_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   if constexpr (T::any) hipLaunchKernelGGL(rec_tables_decode_indices_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c, tb);
   else hipLaunchKernelGGL(rec_decode_indices_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   hipLaunchKernelGGL(rec_decode_status_kernel, dim3(c.N < 65536 ? c.N : 65536), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   return IREC_OK;
 }
 } // namespace

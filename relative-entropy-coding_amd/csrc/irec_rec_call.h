@@ -6,15 +6,13 @@
 #define IREC_REC_CALL_H_
 #include <cstdint>
 #include <exception>
-#include <thread>
 #include <vector>
 
+#include "irec_call.h"
 #include "irec_internal.h"
 #include "irec_rec_core.h"
 
 namespace irec {
-irec_status set_last_error(irec_status code, const char *who, const char *what);   // irec_host.cpp
-
 namespace {
 constexpr int REC_NT = 256;   // lanes of a workgroup
 inline int rec_grid(int64_t lanes) { const int64_t g = (lanes + REC_NT - 1) / REC_NT; return (int)(g < 1 ? 1 : g); }
@@ -65,21 +63,7 @@ irec_status prepare(Call &c, const Layout &lay, const irec_rec::Tables *tb, cons
 template <class Call>
 irec_status prepare_device(Call &c, const Layout &lay, const irec_rec::Tables *tb, const void *workspace, size_t workspace_bytes, const char *who) {
   if (irec_status e = prepare(c, lay, tb, who)) return e;
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < irec_rec_device_workspace_bytes(c.N, c.R))
-    return set_last_error(IREC_E_WORKSPACE, who, "workspace too small (irec_rec_device_workspace_bytes) or not 8-byte aligned");
-  return IREC_OK;
-}
-
-// [0, n) dealt to n_threads host threads (0 = one per core, at most 32) in contiguous ranges; body(e) must not throw
-template <class F>
-void parallel_range(int64_t n, int32_t n_threads, F &&body) {
-  int64_t T = n_threads > 0 ? n_threads : (int64_t)std::thread::hardware_concurrency();
-  T = T < 1 ? 1 : (T > 32 ? 32 : T);
-  if (T > n) T = n;
-  if (T <= 1) { for (int64_t e = 0; e < n; ++e) body(e); return; }
-  std::vector<std::thread> pool;
-  for (int64_t t = 0; t < T; ++t) pool.emplace_back([&, t]() { for (int64_t e = n * t / T; e < n * (t + 1) / T; ++e) body(e); });
-  for (auto &th : pool) th.join();
+  return check_workspace(irec_rec_device_workspace_bytes(c.N, c.R), workspace, workspace_bytes, who, "irec_rec_device_workspace_bytes");
 }
 
 // A prepared call over host memory, what the three launches of a direction do: the lanes sized, the files laid out, the lanes written
@@ -89,11 +73,11 @@ irec_status run_encode_host(irec_rec::EncodeCall &c, const T &tb, int32_t n_thre
   std::vector<int64_t> ws((size_t)(irec_rec::encode_workspace_bytes(c.N, c.R) / 8 + 1));
   irec_rec::encode_bind_workspace(c, ws.data());
   const int64_t streams = 2 * (int64_t)c.N * c.R;
-  parallel_range(streams, n_threads, [&](int64_t lane) { irec_rec::encode_size_lane(c, tb, lane); });
+  parallel_chunks(streams, n_threads, 1, [&](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) irec_rec::encode_size_lane(c, tb, l); });
   int64_t at = 0;
   for (int64_t i = 0; i < c.N; ++i) { c.offsets[i] = at; at += irec_rec::encode_image_bytes(c, i); }
   c.offsets[c.N] = at;
-  parallel_range(streams + c.N, n_threads, [&](int64_t lane) { irec_rec::encode_write_lane(c, tb, lane); });
+  parallel_chunks(streams + c.N, n_threads, 1, [&](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) irec_rec::encode_write_lane(c, tb, l); });
   return IREC_OK;
 } catch (const std::exception &e) { return set_last_error(IREC_E_INVALID, who, e.what()); }
 
@@ -102,18 +86,12 @@ irec_status run_decode_host(irec_rec::DecodeCall &c, const T &tb, int32_t n_thre
   std::vector<int32_t> ws((size_t)(2 * (int64_t)c.N * c.R + 1));
   c.stream_status = ws.data();
   const int64_t lanes = (int64_t)c.N * c.R;
-  parallel_range(lanes, n_threads, [&](int64_t s) { irec_rec::decode_counts_lane(c, tb, s); });
-  parallel_range(lanes, n_threads, [&](int64_t s) { irec_rec::decode_indices_lane(c, tb, s); });
+  parallel_chunks(lanes, n_threads, 1, [&](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) irec_rec::decode_counts_lane(c, tb, l); });
+  parallel_chunks(lanes, n_threads, 1, [&](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) irec_rec::decode_indices_lane(c, tb, l); });
   irec_rec::decode_finish_host(c);
   return IREC_OK;
 } catch (const std::exception &e) { return set_last_error(IREC_E_INVALID, who, e.what()); }
 } // namespace
 } // namespace irec
-
-#define REC_HIP(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return irec::set_last_error(IREC_E_HIP, #expr, hipGetErrorString(e_));         \
-  } while (0)
 
 #endif // IREC_REC_CALL_H_

@@ -181,19 +181,13 @@ irec_status prepare_segmented(Call &inner, SegLayout &L, const int32_t *blocks_p
   if ((2 * (int64_t)inner.N * L.S + inner.N) / REC_NT >= 0x7fffffff) return set_last_error(IREC_E_INVALID, who, "more segments than a launch holds");
   return IREC_OK;
 }
-irec_status check_workspace(int64_t need, const void *workspace, size_t workspace_bytes, const char *who) {
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < (size_t)need)
-    return set_last_error(IREC_E_WORKSPACE, who, "workspace too small (irec_rec_seg_workspace_bytes) or not 8-byte aligned");
-  return IREC_OK;
-}
 
 // The threads worth starting for a call of `rows` blocks: starting and joining a thread costs what coding some two thousand symbols
 // does, so a thread is started per SEG_SLOTS_PER_THREAD symbol slots (rows (1 + max_K): an upper bound that needs no pass over K), at
-// most n_threads (0 = one per core, at most 32).  The two per-image steps (a few adds per segment) run on the calling thread.
+// most irec_call.h's host_threads(n_threads).  The two per-image steps (a few adds per segment) run on the calling thread.
 constexpr int64_t SEG_SLOTS_PER_THREAD = 8192;
 inline int32_t seg_threads(int32_t n_threads, int64_t rows, int32_t max_K) {
-  int64_t T = n_threads > 0 ? n_threads : (int64_t)std::thread::hardware_concurrency();
-  T = T < 1 ? 1 : (T > 32 ? 32 : T);
+  const int64_t T = host_threads(n_threads);
   const int64_t worth = 1 + rows * (1 + (int64_t)max_K) / SEG_SLOTS_PER_THREAD;
   return (int32_t)(T < worth ? T : worth);
 }
@@ -205,11 +199,11 @@ irec_status run_seg_encode_host(SegEncodeCall &c, int32_t n_threads, bool plain_
   if (plain_loop) { irec_rec::seg_encode_call_host(c); return IREC_OK; }
   const int64_t streams = 2 * (int64_t)c.e.N * c.L.S;
   const int32_t T = seg_threads(n_threads, (int64_t)c.e.N * c.e.first[c.e.R], c.e.max_K);
-  parallel_range(streams, T, [&](int64_t lane) { irec_rec::seg_encode_size_lane(c, lane); });
+  parallel_chunks(streams, T, 1, [&](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) irec_rec::seg_encode_size_lane(c, l); });
   int64_t at = 0;
   for (int64_t i = 0; i < c.e.N; ++i) { irec_rec::seg_encode_layout_image(c, i); c.e.offsets[i] = at; at += c.image_bytes[i]; }
   c.e.offsets[c.e.N] = at;
-  parallel_range(streams + c.e.N, T, [&](int64_t lane) { irec_rec::seg_encode_write_lane(c, lane); });
+  parallel_chunks(streams + c.e.N, T, 1, [&](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) irec_rec::seg_encode_write_lane(c, l); });
   return IREC_OK;
 } catch (const std::exception &e) { return set_last_error(IREC_E_INVALID, who, e.what()); }
 
@@ -220,8 +214,8 @@ irec_status run_seg_decode_host(SegDecodeCall &c, int32_t n_threads, bool plain_
   const int64_t lanes = (int64_t)c.d.N * c.L.S;
   const int32_t T = seg_threads(n_threads, (int64_t)c.d.N * c.d.first[c.d.R], c.d.max_K);
   for (int64_t i = 0; i < c.d.N; ++i) irec_rec::seg_decode_locate_image(c, i);
-  parallel_range(lanes, T, [&](int64_t n) { irec_rec::seg_decode_counts_lane(c, n); });
-  parallel_range(lanes, T, [&](int64_t n) { irec_rec::seg_decode_indices_lane(c, n); });
+  parallel_chunks(lanes, T, 1, [&](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) irec_rec::seg_decode_counts_lane(c, l); });
+  parallel_chunks(lanes, T, 1, [&](int64_t lo, int64_t hi) { for (int64_t l = lo; l < hi; ++l) irec_rec::seg_decode_indices_lane(c, l); });
   irec_rec::seg_decode_finish_host(c);
   return IREC_OK;
 } catch (const std::exception &e) { return set_last_error(IREC_E_INVALID, who, e.what()); }
@@ -252,21 +246,21 @@ irec_status irec_rec_encode_files_device_segmented(uint32_t seed, uint32_t block
   const char *who = "irec_rec_encode_files_device_segmented";
   SegEncodeCall c{EncodeCall{seed, block_size, max_index, height, width, channels, n_images, n_res_blocks, 0, max_K, K, k_stride, idx, idx_stride, out, cap, offsets, status}};
   if (irec_status e = prepare_segmented(c.e, c.L, blocks_per_res, segment_blocks, who)) return e;
-  if (irec_status e = check_workspace(irec_rec::seg_encode_workspace_bytes(c.e.N, c.L.S), workspace, workspace_bytes, who)) return e;
+  if (irec_status e = check_workspace(irec_rec::seg_encode_workspace_bytes(c.e.N, c.L.S), workspace, workspace_bytes, who, "irec_rec_seg_workspace_bytes")) return e;
   irec_rec::seg_encode_bind_workspace(c, workspace);
   hipStream_t st = (hipStream_t)hip_stream;
   const int64_t streams = 2 * (int64_t)c.e.N * c.L.S;
   if (streams > 0) {
     hipLaunchKernelGGL(rec_seg_size_kernel, dim3(rec_grid(streams)), dim3(REC_NT), 0, st, c);
-    REC_HIP(hipGetLastError());
+    IREC_HIP(hipGetLastError());
     hipLaunchKernelGGL(rec_seg_layout_kernel, dim3(per_image_grid(c.e.N)), dim3(REC_NT), 0, st, c);
-    REC_HIP(hipGetLastError());
+    IREC_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(rec_seg_offsets_kernel, dim3(1), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   if (streams > 0) {
     hipLaunchKernelGGL(rec_seg_write_kernel, dim3(rec_grid(streams + c.e.N)), dim3(REC_NT), 0, st, c);
-    REC_HIP(hipGetLastError());
+    IREC_HIP(hipGetLastError());
   }
   return IREC_OK;
 }
@@ -278,19 +272,19 @@ irec_status irec_rec_decode_files_device_segmented(const uint8_t *bytes, const i
   const char *who = "irec_rec_decode_files_device_segmented";
   SegDecodeCall c{DecodeCall{bytes, offsets, n_images, n_res_blocks, 0, max_K, headers, K, idx, status}};
   if (irec_status e = prepare_segmented(c.d, c.L, blocks_per_res, segment_blocks, who)) return e;
-  if (irec_status e = check_workspace(irec_rec::seg_decode_workspace_bytes(c.d.N, c.L.S), workspace, workspace_bytes, who)) return e;
+  if (irec_status e = check_workspace(irec_rec::seg_decode_workspace_bytes(c.d.N, c.L.S), workspace, workspace_bytes, who, "irec_rec_seg_workspace_bytes")) return e;
   irec_rec::seg_decode_bind_workspace(c, workspace);
   if (c.d.N == 0) return IREC_OK;
   hipStream_t st = (hipStream_t)hip_stream;
   const int64_t lanes = (int64_t)c.d.N * c.L.S;
   hipLaunchKernelGGL(rec_seg_locate_kernel, dim3(per_image_grid(c.d.N)), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   hipLaunchKernelGGL(rec_seg_decode_counts_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   hipLaunchKernelGGL(rec_seg_decode_indices_kernel, dim3(rec_grid(lanes)), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   hipLaunchKernelGGL(rec_seg_decode_status_kernel, dim3(per_image_grid(c.d.N)), dim3(REC_NT), 0, st, c);
-  REC_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   return IREC_OK;
 }
 

@@ -112,7 +112,7 @@ irec_status irec_rec_hist_rows_device(int32_t n_images, int32_t n_res_blocks, co
   HistCall c{n_images, n_res_blocks, max_K, n_index_values, n_count_values, K, k_stride, idx, idx_stride, index_hist, count_hist, streams, rejected, {}};
   if (const char *why = hist_args(c, blocks_per_res)) return set_last_error(IREC_E_INVALID, "irec_rec_hist_rows_device", why);
   hipLaunchKernelGGL(rec_hist_rows_kernel, dim3(rec_grid((int64_t)n_images * c.first[c.R])), dim3(REC_NT), 0, (hipStream_t)hip_stream, c);
-  REC_HIP(hipGetLastError());
+  IREC_HIP(hipGetLastError());
   return IREC_OK;
 }
 

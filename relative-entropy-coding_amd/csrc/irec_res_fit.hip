@@ -14,14 +14,12 @@
 #include <cmath>
 #include <cstdint>
 #include <exception>
-#include <thread>
 #include <vector>
 
+#include "irec_call.h"
 #include "irec_res_fit_core.h"
 
 namespace irec {
-irec_status set_last_error(irec_status code, const char *who, const char *what);   // irec_host.cpp
-
 namespace {
 constexpr int FIT_NT = 256, FIT_WAVES = FIT_NT / 64, FIT_PER_LANE = (int)(irec_res_fit::TILE / FIT_NT);
 static_assert(irec_res_fit::TILE % FIT_NT == 0 && irec_res_fit::MAX_CANDIDATES + 1 <= FIT_NT, "a lane per column in the last step");
@@ -93,22 +91,6 @@ bool make_fit_call(irec_res_fit::FitCall &c, const uint8_t *pixels, const float 
   return true;
 }
 
-// units of a pass on T host threads (a unit is a tile under every candidate: worth a thread of its own)
-struct ThreadedUnits {
-  int32_t n_threads;
-  template <class F>
-  void operator()(int64_t n, F &&body) const {
-    int64_t T = n_threads > 0 ? n_threads : (int64_t)std::thread::hardware_concurrency();
-    T = T < 1 ? 1 : (T > 32 ? 32 : T);
-    if (T > n) T = n;
-    if (T <= 1) { body((int64_t)0, n); return; }
-    std::vector<std::thread> pool;
-    const int64_t per = (n + T - 1) / T;
-    for (int64_t t = 0; t < T; ++t)
-      pool.emplace_back([&body, t, per, n]() { const int64_t lo = t * per, hi = lo + per < n ? lo + per : n; if (lo < hi) body(lo, hi); });
-    for (auto &th : pool) th.join();
-  }
-};
 } // namespace
 } // namespace irec
 
@@ -134,16 +116,17 @@ irec_status irec_res_scale_bits_device(const uint8_t *pixels, const float *loc, 
   irec_res_fit::FitCall c;
   if (!make_fit_call(c, pixels, loc, scales, cost, n_images, height, width, channels, n_candidates, bits, skipped))
     return set_last_error(IREC_E_INVALID, "irec_res_scale_bits_device", "bad arguments (1 .. 64 candidates)");
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < irec_res_scale_bits_workspace_bytes(n_images, height, width, channels, n_candidates))
-    return set_last_error(IREC_E_WORKSPACE, "irec_res_scale_bits_device", "workspace too small (irec_res_scale_bits_workspace_bytes) or not 8-byte aligned");
+  if (irec_status e = check_workspace(irec_res_scale_bits_workspace_bytes(n_images, height, width, channels, n_candidates), workspace, workspace_bytes,
+                                      "irec_res_scale_bits_device", "irec_res_scale_bits_workspace_bytes"))
+    return e;
   if (n_images == 0) return IREC_OK;
   c.part = (int64_t *)workspace;
   hipStream_t st = (hipStream_t)hip_stream;
   hipLaunchKernelGGL(res_fit_tiles_kernel, dim3((unsigned)((int64_t)c.N * c.C * c.tiles)), dim3(FIT_NT), 0, st, c);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return set_last_error(IREC_E_HIP, "res_fit_tiles_kernel", hipGetErrorString(e));
+  IREC_HIP_AS("res_fit_tiles_kernel", hipGetLastError());
   const int64_t lanes = (int64_t)c.N * c.C * (c.n_cand + 1);
   hipLaunchKernelGGL(res_fit_finish_kernel, dim3((unsigned)((lanes + FIT_NT - 1) / FIT_NT)), dim3(FIT_NT), 0, st, c);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return set_last_error(IREC_E_HIP, "res_fit_finish_kernel", hipGetErrorString(e));
+  IREC_HIP_AS("res_fit_finish_kernel", hipGetLastError());
   return IREC_OK;
 }
 
@@ -157,7 +140,7 @@ irec_status irec_res_scale_bits(const uint8_t *pixels, const float *loc, const f
   if (n_images == 0) return IREC_OK;
   std::vector<int64_t> ws((size_t)(irec_res_fit::workspace_bytes(n_images, channels, c.plane, n_candidates) / 8 + 1));
   c.part = ws.data();
-  irec_res_fit::scale_bits_host(c, ThreadedUnits{n_threads});
+  irec_res_fit::scale_bits_host(c, Chunks{n_threads, 1});   // (a unit is a tile under every candidate: worth a thread of its own)
   return IREC_OK;
 } catch (const std::exception &e) { return irec::set_last_error(IREC_E_INVALID, "irec_res_scale_bits", e.what()); }
 

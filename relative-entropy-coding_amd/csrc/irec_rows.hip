@@ -8,12 +8,11 @@
 
 #include <cstdint>
 
+#include "irec_call.h"
 #include "irec_internal.h"
 #include "irec_rows_core.h"
 
 namespace irec {
-irec_status set_last_error(irec_status code, const char *who, const char *what);   // irec_host.cpp
-
 namespace {
 constexpr int ROWS_NT = 256;
 
@@ -44,8 +43,7 @@ irec_status irec_decode_rows_status(int64_t n_groups, int32_t blocks_per_group, 
   if (!irec_rows::args_ok(c)) return set_last_error(IREC_E_INVALID, "irec_decode_rows_status", "bad arguments");
   if (n_groups == 0) return IREC_OK;
   hipLaunchKernelGGL(rows_status_kernel, dim3((unsigned)(n_groups < 65536 ? n_groups : 65536)), dim3(ROWS_NT), 0, (hipStream_t)hip_stream, c);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return set_last_error(IREC_E_HIP, "irec_decode_rows_status", hipGetErrorString(e));
+  IREC_HIP_AS("irec_decode_rows_status", hipGetLastError());
   return IREC_OK;
 }
 
