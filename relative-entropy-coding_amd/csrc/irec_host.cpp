@@ -899,6 +899,7 @@ struct CallPlan : Plan {
   bool margins = false;     // IREC_FLAG_MARGINS: the call returns top-B margins ...
   bool margin_build = false;   // ... from a margin build of the team encoder (irec_team_margin.hip), not from the generic kernel
   bool ten = false;         // encode_ten_kernel<teams> (irec_ten.hip): a plain team call of at most ten beams
+  int swaps = 0;            // lane-swap masks (irec_kernels.h, "Lane swaps"): 0 none, 1 searched by swap_mask_kernel, 2 all ones (test pattern)
   int deferred = DEFER_NONE, deferred_grid = 0;   // second pass over the blocks whose K lies beyond the table window
   size_t ws_bytes = 0;      // what this layout occupies: the workspace must hold it
   size_t ws_bytes_call = 0; // what THIS call indexes of it (irec_encode_workspace_bytes_for)
@@ -972,6 +973,14 @@ CallPlan plan_call(int n_cu, const irec_params *p, int64_t n_blocks, int32_t max
       const int n_teams = irec::team_count_for(B, S, pl.shape);
       const int64_t tg = share_W >= 2 ? share_grid : batch_grid(n_blocks, std::min(pl.grid_cap / n_teams, n_cu));
       if (n_blocks > tg && d.n_slots <= tg * n_teams && n_teams == 2 && B > 10 && irec::team_placeable(B, S, pl.shape)) d.placed = 1;
+    }
+    // Lane swaps: only where the planned kernel applies them (the 168-VGPR builds on whole rows, without margins; their masks lie where a
+    // placed call's row costs would), and the search only where it pays: calls of at least one block per team slot.  Smaller calls keep
+    // mask 0 and their latency unless a diagnostic flag says otherwise.
+    if (!d.ten && !d.margins && share_W < 2 && !d.placed && S <= irec::SWAP_MAX_S && irec::team_takes_swaps(B, S, pl.shape)) {
+      const int64_t team_slots = (int64_t)d.teams * std::min(pl.grid_cap / d.teams, n_cu);
+      if (p->flags & IREC_FLAG_LANE_SWAPS_ONES) d.swaps = 2;
+      else if ((p->flags & IREC_FLAG_LANE_SWAPS) || n_blocks >= team_slots) d.swaps = 1;
     }
   } else if (pl.table) {
     d.kind = KIND_TABLE;
@@ -1266,7 +1275,7 @@ irec_status irec_beam_encode_ex(irec_context *ctx, const irec_params *p, int64_t
   if (cp.table)
     for (int q = 0; q < cp.n_tab; ++q) {
       uint32_t *w = stamps.w[q];
-      w[0] = 0x7ab1e000u | ((cp.team || cp.chunk) ? 1u : 2u);   // (rows with copy bits / plain byte offsets)
+      w[0] = 0x7ab1e000u | ((cp.team || cp.chunk) ? 1u : 2u) | ((uint32_t)cp.swaps << 2);   // (rows with copy bits / plain byte offsets; copy bits for which grouping)
       w[1] = (uint32_t)(uint64_t)seed; w[2] = (uint32_t)((uint64_t)seed >> 32);
       w[3] = (uint32_t)p->n_samples; w[4] = (uint32_t)cp.tab_dim[q]; w[5] = (uint32_t)cp.K_tab;
       w[6] = (uint32_t)cp.tab_off[q];
@@ -1296,8 +1305,13 @@ irec_status irec_beam_encode_ex(irec_context *ctx, const irec_params *p, int64_t
     }
     if (cp.n_tab > 0 && !(p->flags & IREC_FLAG_TABLES_PRESENT)) {   // (TABLES_PRESENT: the caller's previous call on this workspace built exactly these)
       P.table_kind = (cp.team || cp.chunk) ? 1 : 2;                  // rows with copy bits / plain rows
+      // lane-swap masks: searched before the tables whose copy bits are assigned for the grouping they give (the same stamps cover both)
+      uint32_t *masks = irec::swap_masks_of(workspace);
+      if (cp.swaps && cp.kind == KIND_TEAM) P.jobs.swap = masks;
       P.n_table_wgs = (int32_t)irec::prep_table_wgs(P.table_kind, p->n_samples, cp.K_tab, cp.n_tab, cp.tab_dim, &P.jobs);
+      if (P.jobs.swap) HIP_TRY(irec::launch_swap_masks(P, masks, cp.swaps, st));
     }
+    if (cp.swaps && cp.kind == KIND_TEAM && cp.n_tab > 0) A.lane_swaps = 1;
   }
   HIP_TRY(irec::launch_prep(P, A, st));
   if (cp.W >= 2) {   // gang members per block / teams per shared row / workgroups per block

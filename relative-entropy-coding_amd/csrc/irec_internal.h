@@ -27,6 +27,9 @@ extern "C" {
                                   /* that the longest rows do not meet on one CU.  Results do not depend on it (diagnostics, A/B).     */
 #define IREC_FLAG_NO_TEN 1048576   /* diagnostics (A/B, tests): plain calls of at most ten beams and S * 10 <= 256 stay on encode_team_kernel<10,..> instead */
                                   /* of encode_ten_kernel (irec_ten.hip).  Results do not depend on it.                                  */
+#define IREC_FLAG_LANE_SWAPS 2097152 /* diagnostics (tests): search lane-swap masks (csrc/irec_kernels.h, "Lane swaps") also for calls of fewer blocks   */
+                                  /* than team slots, which keep mask 0 otherwise.  Results do not depend on it.                         */
+#define IREC_FLAG_LANE_SWAPS_ONES 4194304 /* diagnostics (tests): every lane-swap mask all ones instead of searched.  Results do not depend on it. */
 #define IREC_FLAG_SPLIT_SHIFT 12  /* bits 12-15: workgroups per block of the split encoder / sample stripes per chunk of a gang, at most; */
                                   /* 0 = chosen by the library (diagnostics) */
 #define IREC_FLAG_SPLIT_MASK (0xF << IREC_FLAG_SPLIT_SHIFT)

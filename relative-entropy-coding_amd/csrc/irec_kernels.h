@@ -64,6 +64,10 @@ struct EncArgs {
   int32_t gang_chunks;        // the coop_W members of a gang = gang_chunks chunk owners x coop_W / gang_chunks sample stripes
   int32_t coop_beams;         // 1: the workgroups of a block share its beams (slots w, w + coop_W) instead of its samples
   int32_t coop_test_orphan;   // IREC_FLAG_TEST_SPLIT_ORPHAN: partners leave at once (exercises the give-up exit)
+  // Lane swaps of the 168-VGPR builds of the team encoder ("Lane swaps" below): 1 = the call's masks lie in the workspace head
+  // (swap_masks_of(ws_head)); word (q * SWAP_STEPS + t) * 4 + g is the mask of table slot q, step t, dim group g.  0: every mask 0, the
+  // identity grouping.  (In the padding before out_margin: no other field moves, the argument block keeps its size.)
+  int32_t lane_swaps;
   // top-B margins (irec_beam_encode_ex, IREC_FLAG_MARGINS): [n_blocks][4] floats, see "top-B margins" in irec_fast_common.h; nullptr in
   // every other call.  Read by the margin builds of the team encoder (irec_team_margin.hip) and by the generic kernel only.
   float *out_margin;
@@ -169,13 +173,27 @@ struct TableStamps { uint32_t w[4][WS_STAMP_WORDS]; int32_t reuse; };   // all-z
 //   the rest (n_cost)   write the cost key (K * dims) << 10 | row of one row each (EncArgs::row_cost).
 // The first workgroup of the encode kernel that follows copies the pending key over the stamp (commit_table_stamps): a table is
 // stamped only once it has been built.
-struct ChoiceJobs { int32_t D[4]; uint16_t *tab[4]; const uint32_t *keep[4]; int64_t hw_end[4]; int32_t n; };
+// Lane swaps (the preparation side of EncArgs::lane_swaps).  The first level of the canonical lane tree adds lane l and lane l ^ 32, and
+// IEEE addition is commutative bit for bit, so the quads j and j + 32 of a dim group may trade lanes without changing any total.  Which
+// 32 quads form a look-up group decides how well the copy bits can spread it over the banks, and -- bank(alpha' + beta) = bank(alpha') +
+// beta -- that depends on the call's proposal table only: swap_mask_kernel picks one 32-bit mask per (table, step, dim group) (bit j: quads
+// j and j + 32 trade lanes) by a greedy search on the exact min-max assignment, and choice_table_rows assigns the copy bits for the
+// grouping the masks give.  The 1024 mask words lie in the workspace head where the row costs of the cost-ordered hand-out lie
+// (WS_COST_BYTES): only two-team builds take row costs, only the 168-VGPR builds take masks.  Steps from SWAP_STEPS on keep mask 0.
+constexpr int SWAP_STEPS = 64;        // steps of a table that carry masks
+constexpr int SWAP_MAX_S = 64;        // samples per step the search holds in its LDS (S * 4 look-up instructions <= 256 threads)
+struct ChoiceJobs { int32_t D[4]; uint16_t *tab[4]; const uint32_t *keep[4]; int64_t hw_end[4]; int32_t n;
+                    const uint32_t *swap; };   // swap: the call's lane-swap masks, nullptr = identity grouping
 struct PrepArgs {
   uint32_t *head; TableStamps ts;
   int32_t n_granule, n_cost, n_table_wgs, table_kind;   // table_kind: 0 none, 1 rows with copy bits (team / chunk encoders), 2 plain rows
   int64_t seed; int32_t S, K_tab; const uint16_t *dlog4r; ChoiceJobs jobs; uint32_t *cost;
 };
 hipError_t launch_prep(const PrepArgs &P, const EncArgs &A, hipStream_t st);
+// the call's lane-swap masks, BEFORE launch_prep on the same stream (mode 1: searched, 2: every mask all ones -- a test pattern); slots
+// whose table is in place (P.ts against the stamps, as the table workgroups compare them) keep their masks
+hipError_t launch_swap_masks(const PrepArgs &P, uint32_t *masks, int mode, hipStream_t st);
+bool team_takes_swaps(int B, int S, int shape_override);   // the build that serves the call applies EncArgs::lane_swaps (irec_team.hip)
 int64_t prep_table_wgs(int kind, int32_t S, int32_t K_tab, int n, const int32_t *dims, ChoiceJobs *jobs);   // fills jobs.hw_end / D / n
 constexpr size_t WS_COUNTER_BYTES = 512 + 8 * 256;        // [0,256): counters, keep words, table stamps; [256,512): 64 arrival counters; [512,2560): XCD counters
 constexpr int COOP_MAX_BLOCKS = 384, COOP_KEYS = 1024;     // key exchange: blocks per call that are shared (split encoder: <= 64 blocks of a small call; team encoder:
@@ -207,6 +225,9 @@ constexpr size_t GANG_XCH_BYTES_MAX = (size_t)1 << 30;          // ... and no mo
 constexpr int COST_MAX_ROWS = 1024;                              // rows of a call whose hand-out is cost-ordered (EncArgs::row_cost)
 constexpr size_t WS_COST_BYTES = (size_t)COST_MAX_ROWS * 4;
 constexpr size_t WS_HEAD_BYTES = WS_COUNTER_BYTES + WS_XCH_BYTES + WS_COST_BYTES;   // (the row costs lie behind the exchange granules)
+// the lane-swap masks of a call share the row costs' words ("Lane swaps" above)
+static_assert((size_t)4 * SWAP_STEPS * 4 * 4 <= WS_COST_BYTES, "the masks of four tables fit the row-cost area");
+__host__ __device__ inline uint32_t *swap_masks_of(void *ws_head) { return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ws_head) + WS_COUNTER_BYTES + WS_XCH_BYTES); }
 hipError_t launch_decode(const DecArgs &A, int n_cu, hipStream_t st);   // irec_decode.hip
 int decode_tensor_waves(int n, int bs, bool table, size_t *lds_out);     // waves per workgroup of the tensor-staged decoder, 0 = does not apply
 // elementwise hand-offs of the RVAE host shim (irec_shim.hip)

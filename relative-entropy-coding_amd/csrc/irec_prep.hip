@@ -1,7 +1,8 @@
 // irec_prep.hip -- the call's preparation kernel (irec_kernels.h, "The call's preparation kernel"): one launch per call that clears the
 // books and the exchange granules, builds the proposal tables with their bank-spreading copy bits (choice_table_rows) that the team
 // encoders (irec_team.hip, irec_ten.hip, irec_chunk.h) and the one-beam encoder (irec_lone.hip) stream, and writes the cost key of every
-// row for the cost-ordered hand-out of encode_team_kernel.  alpha_choice_kernel builds the tables alone.
+// row for the cost-ordered hand-out of encode_team_kernel.  alpha_choice_kernel builds the tables alone.  swap_mask_kernel, launched in front
+// of the preparation kernel by the calls that take them, picks the lane-swap masks (irec_kernels.h, "Lane swaps") the copy bits are assigned for.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
@@ -33,6 +34,28 @@ namespace irec {
 #ifndef IREC_CHOICE_WPE
 #define IREC_CHOICE_WPE 2   // waves per SIMD the table-building kernels are compiled for
 #endif
+// Exact min-max assignment on one 16-ring of banks: n[p] look-ups have node p as their c = 0 bank and node p + 1 as their c = 1 bank.
+// Returns the smallest L for which no node takes more than L, and in x0 how many of node 0's look-ups stay (the others follow from it).
+__device__ __forceinline__ int ring_min_busiest(const int (&n)[16], int tot, int &x0f) {
+  int Lf = 32;                       // (L = 32 with every look-up at c = 0 is always feasible)
+  x0f = n[0];
+  bool done = false;
+  for (int L = tot > 16 ? (tot + 15) >> 4 : 1; L < 32 && !done; ++L)
+    for (int x0 = 0; x0 <= n[0] && !done; ++x0) {
+      int xp = x0;
+      bool ok = true;
+#pragma unroll
+      for (int p = 1; p < 16; ++p) {
+        const int ub = L - n[p - 1] + xp;
+        ok = ok && ub >= 0;
+        xp = n[p] < ub ? n[p] : (ub < 0 ? 0 : ub);
+      }
+      if (ok && x0 + n[15] - xp <= L) { done = true; Lf = L; x0f = x0; }
+    }
+  return Lf;
+}
+// 32-lane groups of a row of NQ quads (with lane swaps both groups of a dim group exist as soon as one does: quads move between them)
+__host__ __device__ inline int choice_groups(int NQ, bool swaps) { return swaps ? ((NQ + 63) >> 6) << 1 : (NQ + 31) >> 5; }
 // rows with copy bits: workgroup `wg` of `n_wg` (256 threads: 8 half-waves); skip bit q set: table q is in place already
 __device__ __forceinline__ void choice_table_rows(int64_t seed, int32_t S, int32_t K_tab, const uint16_t *__restrict__ dlog4r,
                                                   const ChoiceJobs &jobs, uint32_t skip, int64_t wg, int64_t n_wg) {
@@ -50,11 +73,14 @@ __device__ __forceinline__ void choice_table_rows(int64_t seed, int32_t S, int32
     const int D = jobs.D[q];
     const int Dp = (D + 3) & ~3;
     const int NQ = Dp >> 2;             // quads per row
-    const int NM = (NQ + 31) >> 5;      // 32-lane groups per row
+    const int NM = choice_groups(NQ, jobs.swap != nullptr);   // 32-lane groups per row
     const int64_t row = hw_ok ? hw / NM : 0;           // t * S + s
     const int m = hw_ok ? (int)(hw - row * NM) : 0;
     const int t = (int)(row / S), s = (int)(row - (int64_t)t * S);
-    const int quad = 32 * m + j;
+    // lane swaps: lane j of group m holds quad 32 m + j, or that of the other group of its dim group where bit j of the mask is set
+    uint32_t msk = 0u;
+    if (jobs.swap != nullptr && hw_ok && t < SWAP_STEPS) msk = jobs.swap[(q * SWAP_STEPS + t) * 4 + (m >> 1)];
+    const int quad = 32 * (m ^ (int)((msk >> j) & 1u)) + j;
     const bool q_ok = hw_ok && quad < NQ;
     uint32_t al[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -81,20 +107,8 @@ __device__ __forceinline__ void choice_table_rows(int64_t seed, int32_t S, int32
       int tot = 0;
 #pragma unroll
       for (int p = 0; p < 16; ++p) { n[p] = (int)n_s[hwl][slot][(ring + 22 * p) & 31]; tot += n[p]; }
-      int Lf = 32, x0f = n[0];           // (L = 32 with every look-up at c = 0 is always feasible)
-      bool done = false;
-      for (int L = tot > 16 ? (tot + 15) >> 4 : 1; L < 32 && !done; ++L)
-        for (int x0 = 0; x0 <= n[0] && !done; ++x0) {
-          int xp = x0;
-          bool ok = true;
-#pragma unroll
-          for (int p = 1; p < 16; ++p) {
-            const int ub = L - n[p - 1] + xp;
-            ok = ok && ub >= 0;
-            xp = n[p] < ub ? n[p] : (ub < 0 ? 0 : ub);
-          }
-          if (ok && x0 + n[15] - xp <= L) { done = true; Lf = L; x0f = x0; }
-        }
+      int x0f;
+      const int Lf = ring_min_busiest(n, tot, x0f);
       int xp = x0f;
       x_s[hwl][slot][ring] = (uint8_t)xp;
 #pragma unroll
@@ -117,6 +131,114 @@ __device__ __forceinline__ void choice_table_rows(int64_t seed, int32_t S, int32
 __global__ __launch_bounds__(256, IREC_CHOICE_WPE) void alpha_choice_kernel(int64_t seed, int32_t S, int32_t K_tab,
                                                            const uint16_t *__restrict__ dlog4r, ChoiceJobs jobs) {
   choice_table_rows(seed, S, K_tab, dlog4r, jobs, 0u, (int64_t)blockIdx.x, (int64_t)gridDim.x);
+}
+
+// ======================================================================================================
+//  lane-swap masks (irec_kernels.h, "Lane swaps"): one workgroup per (table, step, dim group)
+//
+//  The step's S * 4 look-up instructions of the dim group are charged L(lanes 0-31) + L(lanes 32-63), L the busiest
+//  bank of the exact assignment above (0 for an empty group).  Greedy, two passes over the 32 bits: flip a bit, keep the flip if the
+//  step's sum drops.  Quads past the row's end are not counted, as in choice_table_rows.
+// ======================================================================================================
+__device__ __forceinline__ uint32_t tables_in_place(const uint32_t *head, const TableStamps &ts) {   // bit q: slot q's stamp is the call's key
+  uint32_t skip = 0u;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    bool same = ts.reuse != 0 && ts.w[q][0] != 0u;
+#pragma unroll
+    for (int k = 0; k < WS_STAMP_WORDS; ++k) same = same && __builtin_nontemporal_load(head + WS_STAMP_WORD + q * WS_STAMP_WORDS + k) == ts.w[q][k];
+    skip |= same ? (1u << q) : 0u;
+  }
+  return skip;
+}
+// 1024 threads: thread (instruction, 32-lane group h, ring) keeps the 16 counts of its ring of banks (a column of cnt_s) and solves that
+// ring alone; the two rings of a group sit in neighbouring lanes.  (One thread per instruction with all four rings took 930 us a call.)
+__global__ __launch_bounds__(1024) void swap_mask_kernel(PrepArgs P, uint32_t *masks, int32_t mode, int32_t steps) {
+  __shared__ uint8_t bank_s[64][256];      // [quad of the dim group][instruction s * 4 + slot]: c = 0 bank, 0xFF = no such quad
+  __shared__ uint8_t cnt_s[16][1024];      // [node of the ring][thread]: look-ups of the thread's group whose c = 0 bank the node is
+  __shared__ int32_t sum_s[3];
+  const int tid = (int)threadIdx.x;
+  const int unit = (int)blockIdx.x;        // (q * steps + t) * 4 + g
+  const int g = unit & 3, t = (unit >> 2) % steps, q = (unit >> 2) / steps;
+  if (q >= P.jobs.n) return;
+  if ((tables_in_place(P.head, P.ts) >> q) & 1u) return;   // the table stays, and so do its masks
+  uint32_t *out = masks + (q * SWAP_STEPS + t) * 4 + g;
+  const int D = P.jobs.D[q], S = P.S;
+  const int NQ = (((D + 3) & ~3) >> 2) - 64 * g;           // quads of this dim group (<= 0: none)
+  if (mode != 1 || NQ <= 0 || S > SWAP_MAX_S) {
+    if (tid == 0) *out = (mode == 2 && NQ > 0) ? 0xFFFFFFFFu : 0u;
+    return;
+  }
+  const StepSeed ss = make_step_seed(P.seed + t);
+  for (int item = tid; item < S * 64; item += 1024) {
+    const int s = item >> 6, ql = item & 63, quad = 64 * g + ql;
+    uint32_t b[4] = {0xFFu, 0xFFu, 0xFFu, 0xFFu};
+    if (ql < NQ) {
+      uint32_t rm1[4];
+      draw_rm1_x4(ss, (uint64_t)s * (uint64_t)D + (uint64_t)(4 * quad), rm1);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) b[i] = 4 * quad + i < D ? ((uint32_t)P.dlog4r[rm1[i]] >> 2) & 31u : 0u;   // (dims past D: entry 0)
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bank_s[ql][s * 4 + i] = (uint8_t)b[i];
+  }
+#pragma unroll
+  for (int p = 0; p < 16; ++p) cnt_s[p][tid] = 0;
+  if (tid < 3) sum_s[tid] = 0;
+  __syncthreads();
+  const int ins = tid >> 2, h = (tid >> 1) & 1, ring = tid & 1;
+  const bool mine = ins < S * 4;           // my look-up instruction
+  // bank b of my ring is its node p with (ring + 22 p) mod 32 = b: p = 3 (b - ring) / 2 mod 16
+  auto move = [&](uint32_t b, int d) { if (b != 0xFFu && (int)(b & 1u) == ring) cnt_s[(3 * ((b - (uint32_t)ring) >> 1)) & 15][tid] += (uint8_t)d; };
+  if (mine)
+    for (int ql = 32 * h; ql < 32 * h + 32; ++ql) move(bank_s[ql][ins], 1);
+  auto cost = [&]() {                      // of my group, in the lane of its ring 0; every lane of the wave comes here
+    int L = 0;
+    if (mine) {
+      int n[16], tot = 0, x0;
+#pragma unroll
+      for (int p = 0; p < 16; ++p) { n[p] = (int)cnt_s[p][tid]; tot += n[p]; }
+      L = tot ? ring_min_busiest(n, tot, x0) : 0;
+    }
+    const int Lo = __shfl_xor(L, 1, 64);
+    int c = ring == 0 ? (L > Lo ? L : Lo) : 0;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
+    return c;                              // the wave's sum
+  };
+  auto flip = [&](int j, uint32_t m) {     // quads j and j + 32 trade groups (m: the mask before the flip)
+    const int h0 = (int)((m >> j) & 1u);   // where quad j is now
+    move(bank_s[j][ins], h == h0 ? -1 : 1);
+    move(bank_s[j + 32][ins], h == h0 ? 1 : -1);
+  };
+  // three counters in turn: the one of the round after next is cleared while this round's is summed (its last reader passed a barrier since)
+  {
+    const int c = cost();
+    if ((tid & 63) == 0) atomicAdd(&sum_s[0], c);
+  }
+  __syncthreads();
+  int best = sum_s[0];
+  uint32_t m = 0u;
+  const int nj = NQ < 32 ? NQ : 32;        // (a bit whose two quads both lie past the row's end moves nothing)
+  int round = 1;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int j = 0; j < nj; ++j, ++round) {
+      if (tid == 0) sum_s[(round + 1) % 3] = 0;
+      if (mine) flip(j, m);
+      const int c = cost();
+      if ((tid & 63) == 0) atomicAdd(&sum_s[round % 3], c);
+      __syncthreads();
+      const int tot = sum_s[round % 3];
+      if (tot < best) { best = tot; m ^= 1u << j; }
+      else if (mine) flip(j, m ^ (1u << j));   // back
+    }
+  if (tid == 0) *out = m;
+}
+hipError_t launch_swap_masks(const PrepArgs &P, uint32_t *masks, int mode, hipStream_t st) {
+  if (P.jobs.n < 1 || masks == nullptr) return hipErrorInvalidValue;
+  const int steps = P.K_tab < SWAP_STEPS ? P.K_tab : SWAP_STEPS;
+  hipLaunchKernelGGL(swap_mask_kernel, dim3((unsigned)(P.jobs.n * steps * 4)), dim3(1024), 0, st, P, masks, (int32_t)mode, (int32_t)steps);
+  return hipGetLastError();
 }
 
 // cost key of one row by one 256-thread workgroup: the row's KL summed in any order -- it places the row, it does not code it.
@@ -196,14 +318,7 @@ __global__ __launch_bounds__(256, IREC_CHOICE_WPE) void prep_kernel(PrepArgs P, 
   wg -= P.n_granule;
   if (wg < P.n_table_wgs) {
     // ---- proposal tables: which slots are in place?  (read-only; see irec_kernels.h for why the race with workgroup 0 is benign)
-    uint32_t skip = 0u;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      bool same = P.ts.reuse != 0 && P.ts.w[q][0] != 0u;
-#pragma unroll
-      for (int k = 0; k < WS_STAMP_WORDS; ++k) same = same && __builtin_nontemporal_load(p + WS_STAMP_WORD + q * WS_STAMP_WORDS + k) == P.ts.w[q][k];
-      skip |= same ? (1u << q) : 0u;
-    }
+    const uint32_t skip = tables_in_place(p, P.ts);
     if (P.table_kind == 1) choice_table_rows(P.seed, P.S, P.K_tab, P.dlog4r, P.jobs, skip, (int64_t)wg, (int64_t)P.n_table_wgs);
     else if (P.table_kind == 2) {
       // plain rows: the workgroups are dealt to the tables in proportion to their rows (jobs.hw_end counts 1024-entry units)
@@ -228,11 +343,11 @@ __global__ __launch_bounds__(256, IREC_CHOICE_WPE) void prep_kernel(PrepArgs P, 
 }
 
 // workgroups that build the call's tables (kind 1: 8 half-waves per workgroup, at most 4096 workgroups, grid-stride; kind 2: per table
-// one workgroup per 1024 entries, at most 1024 per table, grid-stride inside the table); fills jobs->D / hw_end / n
+// one workgroup per 1024 entries, at most 1024 per table, grid-stride inside the table); fills jobs->D / hw_end / n (jobs->swap: set before)
 int64_t prep_table_wgs(int kind, int32_t S, int32_t K_tab, int n, const int32_t *dims, ChoiceJobs *jobs) {
   int64_t end = 0;
   for (int q = 0; q < n; ++q) {
-    if (kind == 1) end += (int64_t)K_tab * S * ((((dims[q] + 3) >> 2) + 31) >> 5);   // half-waves: one per (step, sample, 32-quad group)
+    if (kind == 1) end += (int64_t)K_tab * S * choice_groups((dims[q] + 3) >> 2, jobs->swap != nullptr);   // half-waves: one per (step, sample, 32-quad group)
     else {
       const int64_t total = (int64_t)K_tab * S * ((dims[q] + 3) & ~3);
       end += std::min<int64_t>((total + 1023) / 1024, 1024);

@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 #include "irec_device.h"
 #include "irec_kernels.h"
@@ -47,6 +48,16 @@ namespace irec {
 #else
 #define TSTAMP(slot) do { } while (0)
 #endif
+
+// Lane swaps (irec_kernels.h): first dim of the quad that lane `lane` of dim group g holds at step t of a block of table slot q
+__device__ __forceinline__ int swapped_quad_dim(const EncArgs &A, int q, int t, int g, int lane) {
+  int l = lane;
+  if (A.lane_swaps && t < SWAP_STEPS) {
+    const uint32_t msk = (uint32_t)__builtin_amdgcn_readfirstlane((int)swap_masks_of(A.ws_head)[(q * SWAP_STEPS + t) * 4 + g]);
+    l ^= (int)((msk >> (lane & 31)) & 1u) << 5;
+  }
+  return g * 256 + l * 4;
+}
 
 // LDS carve (bytes): lut2 x 3 [120080] | team 0: part [4][S][NB] f32 | sort keys [S*NB] | TeamLds | barrier | team 1: same
 // BS = beam stripes: with BS == 2 a team has 8 waves, wave w serves dim group / sample stripe (w & 3) and the beams
@@ -178,6 +189,11 @@ __global__ __launch_bounds__(TEAMS * BS * TEAM_NT, 1) void encode_team_kernel(En
   // Three-team builds have 168 VGPRs: the cumulative variance and the sample scale (needed only by the update) are parked
   // in the slab across the scoring loop instead of being spilled inside it
   constexpr bool PARK = SHORT;
+  // Lane swaps (irec_kernels.h): in the builds that park their per-dim state in the slab every value a lane holds for its dims makes a
+  // round trip through the slab once per step, so the lane -> quad map may differ from step to step at no cost: lane l of dim group g
+  // holds quad l ^ 32 where bit l & 31 of the step's mask (A.lane_swaps) is set.  The first level of every lane tree adds lanes
+  // l and l ^ 32 (commutative bit for bit), so no total moves; the preparation kernel picks the masks that spread the look-ups best.
+  constexpr bool SWAP = PARK && !SHARE && !MARGIN;
   constexpr bool LATE_G = false;   // (tried: new beams wait in G's registers and G is formed after the batches -- the
                                    //  register allocator then shuffles eight registers through scratch per beam: 844 B)
 
@@ -227,9 +243,10 @@ __global__ __launch_bounds__(TEAMS * BS * TEAM_NT, 1) void encode_team_kernel(En
     const int64_t base = A.block_base[blk];
     const int32_t pos = A.block_pos[blk];
     const uint16_t *tab = nullptr;
+    int tab_q = 0;                          // (SWAP builds: the slot's masks)
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      if (A.tab_dim[q] == D) tab = A.tab[q];
+      if (A.tab_dim[q] == D) { tab = A.tab[q]; tab_q = q; }
     if (D < 1 || D > FAST_MAX_DIM || tab == nullptr) { // host promised D <= 1024 and listed dims
       if (tid == 0 && qsh == 0) A.out_K[blk] = -1;
       continue;
@@ -240,7 +257,9 @@ __global__ __launch_bounds__(TEAMS * BS * TEAM_NT, 1) void encode_team_kernel(En
     const bool active = wave < NG * NSW;
     const int g = wave % NG, sw = wave / NG;
     const int NSWe = NSW * Wrow, swe = sw * Wrow + qsh;   // ... of the row over all the teams that code it: my samples are swe, swe + NSWe, ...
-    const int d0 = g * 256 + lane * 4;
+    // first dim of my quad (SWAP builds: d0 and valid[] move with the step's mask; everywhere else they never change)
+    std::conditional_t<SWAP, int, const int> d0 = g * 256 + lane * 4;
+    if constexpr (SWAP) d0 = swapped_quad_dim(A, tab_q, 0, g, lane);
 
     // ---- my 4 dims (split == gather through perm) and the block's KL ----
     float c[4];
@@ -377,7 +396,7 @@ __global__ __launch_bounds__(TEAMS * BS * TEAM_NT, 1) void encode_team_kernel(En
       // coefficients) read the row's LAST quad: finite z, and the same addresses as the last real lane of their 32-lane
       // group -- the LDS serves identical addresses as one broadcast, so they add no bank conflict to the look-ups
       const uint32_t tab_lo = (uint32_t)(d0 < Dp ? d0 : Dp - 4);
-      const uint16_t *tab_t = tab_tu + tab_lo;
+      const uint16_t *tab_t = tab_tu + tab_lo;   // (SWAP builds: the update moves it to the next step's quad)
       uint32_t bet[NBW];
       {
 #pragma unroll
@@ -809,6 +828,11 @@ __global__ __launch_bounds__(TEAMS * BS * TEAM_NT, 1) void encode_team_kernel(En
       const bool last = (t == K - 1);
       __builtin_amdgcn_s_setprio(2); // serial phase: ahead of the other team's scoring waves
       // new beams' table offsets: lane j looks up dlog(hash(path_j)) -- a global load, consumed at the end of the update
+      if constexpr (SWAP) {
+        // words of park_g, stats_g and the beams that ANOTHER lane of this wave stored (the last update, at this step's map) are loaded
+        // below at the next step's: the stores have left the wave before the first such load is issued
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
       uint32_t bv_new;
       {
         const int32_t nh = hsum[(cur ^ 1) * TEAM_MB + (lane < Bnew ? lane : 0)];
@@ -819,6 +843,16 @@ __global__ __launch_bounds__(TEAMS * BS * TEAM_NT, 1) void encode_team_kernel(En
 #else
       if (active) {
 #endif
+        if constexpr (SWAP) {
+          // the whole update runs at the NEXT step's map: parents, new beams and their look-ups, c and sa out of the slab, the next
+          // step's constants, G and the C_b terms.  (The last step keeps its map: the sample leaves from it.)
+          if (!last && A.lane_swaps) {
+            d0 = swapped_quad_dim(A, tab_q, t + 1, g, lane);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) valid[i] = d0 + i < D;
+            tab_t = tab_tu + (uint32_t)(d0 < Dp ? d0 : Dp - 4);
+          }
+        }
         unpark();
         const float sa_t[4] = {sa[0], sa[1], sa[2], sa[3]};   // this step's sample scale
         const float *bold = beams_g + ((size_t)cur * NB) * FAST_MAX_DIM + d0;
@@ -1076,6 +1110,10 @@ int team_count_for(int B, int S, int ovr) { return team_shape(B, S, ovr).teams; 
 int team_shareable(int B, int S, int ovr) {
   const TeamShape sh = team_shape(B, S, ovr);
   return (sh.nb && sh.teams >= 2 && sh.bs == 1 && !sh.passes && !sh.one && (int64_t)S * sh.nb <= COOP_KEYS) ? sh.teams : 0;
+}
+bool team_takes_swaps(int B, int S, int ovr) {   // the builds that apply EncArgs::lane_swaps (SWAP in encode_team_kernel; the host
+  const TeamShape sh = team_shape(B, S, ovr);    // leaves the masks out of shared-row and margin calls, whose builds do not)
+  return sh.nb != 0 && sh.teams * sh.bs >= 3 && sh.nb / sh.bs == 20;
 }
 bool team_placeable(int B, int S, int ovr) {   // the builds that can deal their rows by cost (CAN_PLACE in encode_team_kernel)
   const TeamShape sh = team_shape(B, S, ovr);

@@ -21,6 +21,12 @@ IREC_FLAG_TEST_SPLIT_ORPHAN = 32   # test hook: the partner workgroups / teams o
 IREC_FLAG_LISTED_ORDER = 262144     # team encoder: deal the rows of a mid-size call as listed, not by cost (diagnostics)
 IREC_FLAG_MARGINS = 524288           # irec_beam_encode_ex: the call reports its top-B margins (out_margin)
 IREC_FLAG_NO_TEN = 1048576            # diagnostics: plain calls of at most ten beams stay on encode_team_kernel<10,..> (not encode_ten_kernel)
+IREC_FLAG_LANE_SWAPS = 2097152        # diagnostics: search lane-swap masks also for calls of fewer blocks than team slots
+IREC_FLAG_LANE_SWAPS_ONES = 4194304   # diagnostics: every lane-swap mask all ones
+# layout of the workspace head that the tests of the lane swaps read back (csrc/irec_kernels.h: WS_COUNTER_BYTES, WS_XCH_BYTES, WS_COST_BYTES)
+WS_SWAP_MASKS_OFFSET = 2560 + 2 * 384 * 1024 * 8   # uint32 [4 table slots][SWAP_STEPS][4 dim groups], in the row costs' words
+WS_HEAD_BYTES = WS_SWAP_MASKS_OFFSET + 4096          # the proposal tables start here
+SWAP_STEPS = 64
 IREC_FLAG_TABLES_PRESENT = 65536     # the previous call on this workspace / stream was this call's twin: no table launches
 IREC_FLAG_REUSE_TABLES = 64        # keep a proposal table whose stamp in the workspace head matches the call's key
 IREC_FLAG_SHAPE_SHIFT = 8          # diagnostic workgroup shapes of the team encoder (include/irec.h)
