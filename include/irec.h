@@ -812,6 +812,49 @@ irec_status irec_quality_device(const float *a, const float *b, int32_t n, int32
 irec_status irec_quality_host(const float *a, const float *b, int32_t n, int32_t c, int32_t h, int32_t w, int32_t n_scales,
                               const irec_quality_params *params, float *per_scale, float *sse, int32_t n_threads);
 
+/* ---- the ideal half of a results row: seeded posterior draws with their KL, and the log-likelihood of a batch ----------------------
+ * (csrc/irec_ideal.hip over csrc/irec_ideal_core.h, which writes every operation sequence down.)  What the reference's evaluation
+ * drivers take from a sampling forward pass `model(image)`: the latents are draws from the posteriors, KL is the closed form, and the
+ * residual is minus the discretized-logistic log-likelihood of the image under the clipped reconstruction.
+ *
+ * irec_posterior_draw_*: n_images images of `dims` contiguous float32 each; mq, sq, mp, sp are four separate arrays
+ * [n_images][dims] (posterior loc and scale, prior loc and scale).  Outputs:
+ *   sample [n_images][dims] float32   mq + sq * eps(seed, tag, image_base + i, e): one rounding for the product, one for the sum
+ *   kl [n_images] float64             sum over e of KL(N(mq, sq) || N(mp, sp)) in nats, every term in float64
+ * The noise is this library's OWN seeded stream, not TensorFlow's (the reference's pass is unseeded: there is nothing to be faithful
+ * to): Philox4x32-10 under the key (seed lo32, seed hi32) of the int64 seed in two's complement -- any int64 is a valid seed -- and the
+ * counter (block lo32, block hi32, image number, tag); element e takes word e & 3 of block e >> 2; u = ((word >> 8) + 0.5) 2^-24;
+ * eps = (float)ndtri64(u), the Cephes rational form in float64 over the library's deterministic log and IEEE sqrt, so |eps| < 5.5.
+ * tag names the tensor (a residual block's index, a level).  image_base + i lies in [0, 2^32).  A draw is a property of
+ * (seed, tag, image number, e) only: image i of a batch with base b has the bits of a one-image call with base b + i.
+ *
+ * irec_loglik_*: x (the image) and loc (the clipped reconstruction), float32 [n_images][channels][plane] each, plane = h w;
+ * log_scales float32 [n_scales], n_scales 1 (one scale) or channels; scale = exp(log_scale).  Output ll [n_images] float64, nats:
+ *   a = (floor(x / binsize) binsize - loc) / scale;  ll = sum of log(sigmoid(a + binsize / scale) - sigmoid(a) + 1e-7)
+ * in float64 after widening the float32 inputs (rec/models/resnet_vae.py:640-650).
+ *
+ * The device entries follow irec_quality_device: device pointers (log_scales too), asynchronous on hip_stream, no allocation,
+ * synchronisation, copy or atomic inside (two launches each), capturable into a HIP graph; they write exactly their outputs and
+ * the workspace (8-byte aligned, at least irec_ideal_workspace_bytes(n_images, dims) bytes, dims = channels plane for the
+ * likelihood; 0 for a shape the entries refuse).  A sum is added in a fixed order -- lanes of a tile of IREC_IDEAL_TILE elements, tiles
+ * of an image -- so a result is the same bits from run to run and for an image alone or inside any batch, and a NaN in one image
+ * reaches that image's outputs only.  The host entries run the same core over host memory on n_threads threads (0 = one per core, at
+ * most 32) and give the device's bits, whatever n_threads is.  Null or misaligned pointers (float32 arrays 4 bytes, float64 8),
+ * n_images < 1, dims outside 1 .. 2^40, an image number outside [0, 2^32), n_scales neither 1 nor channels, a binsize that is not
+ * positive and finite: IREC_E_INVALID; a workspace smaller than sized: IREC_E_WORKSPACE; no launch either way. */
+#define IREC_IDEAL_TILE 4096
+size_t irec_ideal_workspace_bytes(int32_t n_images, int64_t dims);
+irec_status irec_posterior_draw_device(const float *mq, const float *sq, const float *mp, const float *sp, int32_t n_images, int64_t dims,
+                                       int64_t seed, uint32_t tag, int64_t image_base, float *sample, double *kl, void *workspace,
+                                       size_t workspace_bytes, void *hip_stream);
+irec_status irec_posterior_draw_host(const float *mq, const float *sq, const float *mp, const float *sp, int32_t n_images, int64_t dims,
+                                     int64_t seed, uint32_t tag, int64_t image_base, float *sample, double *kl, int32_t n_threads);
+irec_status irec_loglik_device(const float *x, const float *loc, const float *log_scales, int32_t n_scales, int32_t n_images,
+                               int32_t channels, int64_t plane, double binsize, double *ll, void *workspace, size_t workspace_bytes,
+                               void *hip_stream);
+irec_status irec_loglik_host(const float *x, const float *loc, const float *log_scales, int32_t n_scales, int32_t n_images, int32_t channels,
+                             int64_t plane, double binsize, double *ll, int32_t n_threads);
+
 #ifdef __cplusplus
 }
 #endif

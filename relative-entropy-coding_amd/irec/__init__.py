@@ -7,9 +7,10 @@ fallback: without the built library or without a GPU its entry points raise.  Th
 loop on the host for CPU tensors and for samplers the kernels do not cover, as the reference itself does.
 """
 from . import _lib  # noqa: F401
+from . import ideal  # noqa: F401
 from . import metrics  # noqa: F401
 from .coding import BeamSearchCoder, Coder, CodingError, GaussianCoder  # noqa: F401
 from .coding.samplers import ImportanceSampler, Sampler  # noqa: F401
 from .engine import Engine, get_engine  # noqa: F401
 
-__all__ = ["BeamSearchCoder", "Coder", "GaussianCoder", "ImportanceSampler", "Sampler", "CodingError", "Engine", "get_engine", "metrics"]
+__all__ = ["BeamSearchCoder", "Coder", "GaussianCoder", "ImportanceSampler", "Sampler", "CodingError", "Engine", "get_engine", "metrics", "ideal"]

@@ -178,8 +178,41 @@ def _lossless_leg(model, chunk, names, seed, block_size, out_dir, S, stream_len)
     return rows
 
 
+class _IdealRows:
+    """The rows of a batch (a list, or the future of the packed host leg) that gain the ideal columns when they are asked for: the
+    columns were launched after the batch's compression pass and are read back here, with the batch's one extra copy."""
+
+    def __init__(self, job, columns, h, w):
+        self.job, self.columns, self.h, self.w = job, columns, h, w
+
+    def result(self):
+        rows = self.job if isinstance(self.job, list) else self.job.result()
+        residual, kl, comp_kl = self.columns.cpu().numpy()            # the one extra read-back
+        for i, row in enumerate(rows):
+            if "error" not in row:
+                row.update(_ideal_row(float(residual[i]), float(kl[i]), float(comp_kl[i]), row["comp_codelength"], self.h, self.w))
+        return rows
+
+
+def _ideal_row(residual, kl, comp_kl, comp_codelength, h, w):
+    """The reference's ideal columns (compression_performance.py:337-342) from an image's residual = -log_likelihood and kl, in nats,
+    and the coded pass's comp_kl with what the code spends above it."""
+    ln2 = float(np.log(2.0))
+    return {"residual": residual, "kl": kl, "lossless_bpp": (kl + residual) / (h * w * ln2), "lossy_bpp": kl / (h * w * ln2),
+            "bpd": (kl + residual) / (h * w * 3 * ln2), "comp_kl": comp_kl, "overhead_bits": comp_codelength - comp_kl / ln2}
+
+
+def _ideal_columns(model, chunk, seed, image_base):
+    """float64 [3, m] on the device: residual, kl of a seeded sampling pass over the chunk (model.forward: image i draws as image number
+    image_base + i) and, before it, the KL of the distributions the compression pass just coded under.  No synchronisation."""
+    comp_kl = model.coded_kl()
+    x = chunk.to(torch.float32).mul(1.0 / 256.0).sub(0.5) if chunk.dtype == torch.uint8 else chunk
+    model.forward(x, seed=seed, image_base=image_base)
+    return torch.stack([-model.log_likelihood, model.kl_divergence(), comp_kl])
+
+
 def compress_images(model, images, names, seed, block_size, out_dir, batch=None, packed=True, rec_on_device=False, lossless=False,
-                    stream_len=None, tables=None):
+                    stream_len=None, tables=None, ideal=False):
     """images: [n, 3, H, W] in [-0.5, 0.5] on the model's device.  Returns one dict per image (reference CSV columns where
     they apply: comp_codelength, comp_lossy_bpp, comp_time) plus `indices_recovered`, `code_nats`.
     packed (default): the indices stay packed arrays from the device to the files (model.compress_packed, irec.io.encode_files
@@ -191,7 +224,14 @@ def compress_images(model, images, names, seed, block_size, out_dir, batch=None,
     and decoded to the pixels on the device, and the rows gain comp_residual, comp_lossless_bpp, comp_bpd, residual_model_bits and
     pixels_recovered (_lossless_leg).  stream_len: symbols per .res stream (default irec.io.residual.DEFAULT_STREAM_LEN).
     tables: an irec.io.SymbolTables (fit_symbol_tables) the files are coded under, on the packed host leg or the device leg;
-    decompress_images_tables reads them.  The per-image form and the lossless pair keep the default models (ValueError)."""
+    decompress_images_tables reads them.  The per-image form and the lossless pair keep the default models (ValueError).
+    ideal: every row also carries the ideal half of the reference's results row (compression_performance.py:321-342), from a seeded
+    sampling forward pass over the batch after its compression pass (model.forward(chunk, seed, image_base): the library's own
+    seeded draws, irec.ideal) -- `residual` = -log_likelihood and `kl` in nats, `lossless_bpp` = (kl + residual) / (h w ln 2),
+    `lossy_bpp` = kl / (h w ln 2), `bpd` = lossless_bpp / 3 -- and `comp_kl`, the KL of the distributions the indices were coded
+    under (through the same kernel), with `overhead_bits` = comp_codelength - comp_kl / ln 2: what the files spend above the KL they
+    code.  All of it stays on the device until ONE extra read-back per batch.  image_base is the image's number in the call, not in
+    the batch, so a row's draws do not depend on batch=.  ideal=False: the rows and the work are as before."""
     if tables is not None and (lossless or not (rec_on_device or (packed and hasattr(model, "compress_packed")))):
         raise ValueError("compress_images: tables go with the packed host leg or rec_on_device, not with lossless or packed=False")
     seed = header_seed(seed, "compress_images")            # (before out_dir is made or a batch coded: no leg could write this seed)
@@ -199,6 +239,16 @@ def compress_images(model, images, names, seed, block_size, out_dir, batch=None,
     n = images.shape[0]
     batch = n if not batch else int(batch)
     S = model.residual_blocks[0].coder.n_samples
+    if ideal:
+        h, w = int(images.shape[2]), int(images.shape[3])
+
+        def with_ideal(leg):            # the leg's rows (or their future), then the ideal pass launched behind the compression pass
+            def run(lo, hi):
+                job = leg(lo, hi)
+                return _IdealRows(job, _ideal_columns(model, images[lo:hi], seed, lo), h, w)
+            return run
+    else:
+        with_ideal = lambda leg: leg  # noqa: E731
     if lossless:
         leg = lambda lo, hi: _lossless_leg(model, images[lo:hi], names[lo:hi], seed, block_size, out_dir, S, stream_len)  # noqa: E731
     elif rec_on_device:
@@ -212,10 +262,10 @@ def compress_images(model, images, names, seed, block_size, out_dir, batch=None,
                 K, idx, _ = model.compress_packed(images[lo:hi], seed=seed, update_sampler=False)
                 return pool.submit(_host_leg, tuple(images[lo:hi].shape), names[lo:hi], seed, block_size, out_dir, S, K, idx,
                                    time.perf_counter() - t0, tables)
-            return [row for job in _in_batches(n, batch, names, leg) for row in (job if isinstance(job, list) else job.result())]
+            return [row for job in _in_batches(n, batch, names, with_ideal(leg)) for row in (job if isinstance(job, list) else job.result())]
     else:
         leg = lambda lo, hi: _lists_leg(model, images[lo:hi], names[lo:hi], seed, block_size, out_dir, S)  # noqa: E731
-    return [row for rows in _in_batches(n, batch, names, leg) for row in rows]
+    return [row for rows in _in_batches(n, batch, names, with_ideal(leg)) for row in (rows if isinstance(rows, list) else rows.result())]
 
 
 def _segmented_words(data):
@@ -378,8 +428,18 @@ def _lossy_quality_columns(model, chunk, reconstruction, image_range):
     return torch.stack([psnr, ms_ssim, kld])
 
 
+def _lossy_ideal_columns(model, chunk, seed, image_base, image_range):
+    """float64 [3, m] on the device: psnr, ms_ssim of the reconstruction of a seeded sampling pass over the chunk against the chunk, and
+    the pass's KL (both levels, irec.ideal.posterior_draw's) in nats.  No synchronisation."""
+    from . import metrics
+    _, reconstruction = model.forward(chunk, seed=seed, image_base=image_base)
+    psnr, ms_ssim, _ = metrics.quality(reconstruction, chunk, **metrics.transform_for(image_range))
+    kl_2, kl_1 = model.kl_divergence()
+    return torch.stack([psnr, ms_ssim, kl_2 + kl_1])
+
+
 def compress_images_lossy(model, sampler, images, names, seed, block_size, out_dir, batch=None, rec_on_device=False, tables=None,
-                          quality=False, image_range=(0., 1.), segment_blocks=None):
+                          quality=False, image_range=(0., 1.), segment_blocks=None, ideal=False):
     """compress_images for Large2LevelVAE and its coder `sampler`: images [n, 3, H, W] on the model's device, in batches through
     model.compress_rec (two coder launches per batch, one read-back), one NAME.rec per image -- byte for byte the file
     model.compress(file_path, ...) writes for it -- read back and compared with the rows the files were built from.
@@ -391,8 +451,12 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
     image (irec.metrics on the device: tf.image.psnr / tf.image.ssim_multiscale of clip(reconstruction) * 255 against image * 255 for
     images in image_range, (0, 1) as the reference has them, (-0.5, 0.5) as the shim's tests do; images of at least 161 x 161),
     `kld`, the closed-form Gaussian KL of both levels in nats (float64 on the device), and `lossy_bpp` = kld / (h w ln 2) -- all
-    of it in ONE extra read-back per batch.  The reference's ideal_PSNR / ideal_MS_SSIM columns are left out: they come from an
-    unseeded sampling forward pass, which the compression shim does not have.  quality=False: the rows and the work are as before.
+    of it in ONE extra read-back per batch.  quality=False: the rows and the work are as before.
+    ideal=True: every row also carries the ideal half of that row (compress_with_lossy_model.py:193-215), from a seeded sampling
+    forward pass over the batch (model.forward(chunk, seed=seed, image_base=the image's number in the call): the library's own seeded
+    draws, irec.ideal, where the reference's are unseeded) -- `ideal_psnr` and `ideal_ms_ssim` of that pass's reconstruction
+    (irec.metrics, as above), `ideal_kld`, both levels' KL in nats through irec.ideal's kernel, and `ideal_lossy_bpp` =
+    ideal_kld / (h w ln 2) -- read back with the batch's one extra copy.  ideal=False: the rows and the work are as before.
     segment_blocks: None for the reference's files; g >= 1 writes NAME.recs, the segmented container (model.compress_rec has the
     description; default symbol models only, so together with tables it is a ValueError), on host threads or on the device alike."""
     from .io import decode_files_device_ragged, decode_files_device_segmented, decode_files_ragged, decode_files_segmented
@@ -412,6 +476,9 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
         (blob, off, reconstruction), (K, idx, bpr) = model.compress_rec(chunk, seed, sampler, block_size=block_size, rec_on_device=rec_on_device,
                                                                         return_pendings=True, tables=tables, segment_blocks=segment_blocks)
         columns = _lossy_quality_columns(model, chunk, reconstruction, image_range) if quality else None   # (launched; read below)
+        if ideal:                                                            # (after the quality columns: the pass replaces the model's distributions)
+            ideal_columns = _lossy_ideal_columns(model, chunk, seed, lo, image_range)
+            columns = ideal_columns if columns is None else torch.cat([columns, ideal_columns])
         t_compress, t1 = time.perf_counter() - t0, time.perf_counter()
         if segment_blocks is None:
             decode = lambda b, o: ragged(b, o, bpr, idx.shape[2], tables=tables)  # noqa: E731
@@ -419,11 +486,17 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
             decode = lambda b, o: segmented(b, o, bpr, idx.shape[2], segment_blocks)  # noqa: E731
         rows = _check_leg(out_dir, names[lo:hi], "rec" if segment_blocks is None else "recs", blob, off, K, idx, decode,
                           (seed, block_size, h, w, 3), S, t_compress, t1)
+        host = columns.cpu().numpy() if (quality or ideal) else None         # the one extra read-back
         if quality:
-            psnr, ms_ssim, kld = columns.cpu().numpy()           # the one extra read-back
+            psnr, ms_ssim, kld = host[:3]
             for i, row in enumerate(rows):
                 row.update({"psnr": float(psnr[i]), "ms_ssim": float(ms_ssim[i]), "kld": float(kld[i]),
                             "lossy_bpp": float(kld[i]) / (h * w * float(np.log(2.0)))})
+        if ideal:
+            psnr, ms_ssim, kld = host[-3:]
+            for i, row in enumerate(rows):
+                row.update({"ideal_psnr": float(psnr[i]), "ideal_ms_ssim": float(ms_ssim[i]), "ideal_kld": float(kld[i]),
+                            "ideal_lossy_bpp": float(kld[i]) / (h * w * float(np.log(2.0)))})
         return rows
     return [row for rows in _in_batches(n, batch, names, leg) for row in rows]
 

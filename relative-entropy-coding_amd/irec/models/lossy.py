@@ -66,13 +66,36 @@ class Large2LevelVAE(nn.Module):
         return loc, F.softplus(log_scale) + 1e-7, log_scale
 
     @torch.no_grad()
-    def forward(self, tensor, sampling_fn=None):
+    def forward(self, tensor, sampling_fn=None, seed=None, image_base=0):
         """large_2_level_vae.py:320-404.  tensor: [N, 3, H, W] (the reference's N = 1, or a batch that `sampling_fn` codes with
-        batched=True); returns ([level_2_indices, level_1_indices], reconstruction)."""
-        if sampling_fn is None:
+        batched=True); returns ([level_2_indices, level_1_indices], reconstruction).
+        seed (instead of sampling_fn): the sampling pass of the reference's evaluation script (`model(image)`) -- level 2 is DRAWN from
+        its posterior (irec.ideal.posterior_draw, tag 2), the level-1 prior synthesised from the draw, level 1 drawn (tag 1), image i
+        drawing as image number image_base + i; nothing is coded or read back.  Returns (None, reconstruction) and leaves the two
+        levels' KL for kl_divergence()."""
+        if sampling_fn is None and seed is None:
             raise NotImplementedError("training / sampling passes are outside the compression shim")
+        if seed is not None:
+            if sampling_fn is not None:
+                raise ValueError("forward takes sampling_fn (a coded pass) or seed (a sampling pass), not both")
+            from .. import ideal
+            levels, kls = iter((2, 1)), []
+
+            def sampling_fn(target, coder):
+                sample, kl = ideal.posterior_draw(target, coder, seed, next(levels), image_base)
+                kls.append(kl)
+                return None, sample
+            _, y = self._code_levels(tensor, sampling_fn)
+            self._kl = kls
+            return None, self.synthesis_transform(_nchw(y))
         block_indices, y = self._code_levels(tensor, sampling_fn)
         return block_indices, self.synthesis_transform(_nchw(y))
+
+    def kl_divergence(self):
+        """large_2_level_vae.py's kl_divergence for the last forward(tensor, seed=): [kl_level_2, kl_level_1], float64 [N] each, nats."""
+        if getattr(self, "_kl", None) is None:
+            raise ModelError("kl_divergence needs a forward(tensor, seed=) pass first")
+        return list(self._kl)
 
     def _code_levels(self, tensor, sampling_fn):
         """`forward` up to the coded level-1 sample: ([level_2_indices, level_1_indices], y NHWC)."""

@@ -9,7 +9,8 @@ out of scope -- no checkpoints or datasets exist in the reference tree, SURVEY.m
 the shim pins is the hand-off: tensors are presented to the coder in the reference's NHWC order, the residual blocks
 are coded strictly in sequence (the prior of block n+1 depends on the coded latent of block n), and the keyword
 arguments (`sampler`, `sampler_args`, `coder_args`, `kl_per_partition`, `encoder_args`, `decoder_args`) keep their
-names and meaning.
+names and meaning.  Beside the compression path there is the evaluation script's sampling pass, `forward(images, seed)` with
+`kl_divergence()` and `log_likelihood` (resnet_vae.py:687-750), its draws seeded and made on the device (irec.ideal).
 """
 import numpy as np
 import torch
@@ -150,6 +151,8 @@ class BidirectionalResidualBlock(nn.Module):
         # the kernels cannot take as they are (non-contiguous, channels_last) are made contiguous, not routed around them.
         self.use_handoff_kernels = None
         self.posterior = self.prior = None
+        self.index = 0       # the block's number in its model: the `tag` of its seeded posterior draws (the model sets it)
+        self.kl = None       # float64 [N]: KL(posterior || prior) per image of the last seeded sampling pass (irec.ideal.posterior_draw)
         self._pad = pad
         self._fused = None   # (parameter versions, inference-side weight / bias, generative-side weight / bias)
         self._fuse_mods = None
@@ -239,7 +242,9 @@ class BidirectionalResidualBlock(nn.Module):
     def forward(self, tensor, inference_pass=True, encoder_args=None, decoder_args=None, sample_args=None):
         """resnet_vae.py:372-497.  sample_args={"generator": g}: the generative pass of the reference's `call` -- the latent is a
         draw from the posterior (standard normals from the CPU generator g), nothing is coded; it leaves the block's posterior and
-        prior in place for update_coders."""
+        prior in place for update_coders.  sample_args={"seed": s, "image_base": b}: the same pass with the draw made where the
+        statistics are (irec.ideal.posterior_draw with tag = the block's index: the library's own seeded stream, image i of the batch
+        drawing as image b + i), no host round trip; it also leaves self.kl, float64 [N], the block's KL per image."""
         inp = tensor
         pre = getattr(tensor, "_irec_elu", None)          # the previous block's residual kernel already formed elu(tensor)
         tensor = pre if pre is not None else F.elu(tensor)
@@ -285,6 +290,10 @@ class BidirectionalResidualBlock(nn.Module):
                 self.prior, self.posterior = _Normal(st[0], st[1]), _Normal(st[2], st[3])
                 if encoder_args is not None:
                     indices, latent_code = self.coder.encode(self.posterior, self.prior, **encoder_args)
+                elif "seed" in sample_args:                                       # :471-473, posterior.sample(), seeded on the device
+                    from .. import ideal
+                    latent_code, self.kl = ideal.posterior_draw(self.posterior, self.prior, sample_args["seed"], self.index,
+                                                                sample_args.get("image_base", 0))
                 else:                                                             # :471-473, posterior.sample()
                     noise = torch.randn(self.posterior.loc.shape, generator=sample_args["generator"], dtype=torch.float32)
                     latent_code = self.posterior.loc + self.posterior.scale * noise.to(self.posterior.loc.device)
@@ -335,6 +344,10 @@ class BidirectionalResNetVAE(nn.Module):
                                        kernel_size=kernel_size, is_last=res_block_idx == 0, use_iaf=use_iaf,
                                        kl_per_partition=kl_per_partition, name=f"resnet_block_{res_block_idx}")
             for res_block_idx in range(num_res_blocks)])
+        for res_block_idx, block in enumerate(self.residual_blocks):
+            block.index = res_block_idx
+        self.likelihood_function_name = str(likelihood_function)   # (only `forward` reads it: the one family its likelihood term is built for)
+        self.log_likelihood = None                                 # float64 [N] of the last `forward`
         self._generative_base = nn.Parameter(torch.zeros(deterministic_filters))
         # resnet_vae.py:581: the log of the discretized-logistic likelihood's one scale (the .res coder's model, compress_lossless).
         # Created after every other parameter and without a random draw: no existing initialisation moves.
@@ -353,6 +366,49 @@ class BidirectionalResNetVAE(nn.Module):
         pre = getattr(tensor, "_irec_elu", None)
         reconstruction = self.last_gen_conv(pre if pre is not None else F.elu(tensor))
         return torch.clamp(reconstruction, -0.5 + 1. / 512., 0.5 - 1. / 512.)
+
+    @torch.no_grad()
+    def forward(self, images, seed, image_base=0, binsize=1. / 256.):
+        """resnet_vae.py:687-727, the reference's `call` as its evaluation script uses it (`model(image)`): the inference pass, the
+        generative pass with every latent DRAWN from its posterior, the clipped reconstruction; returns reconstruction + 0.5.
+        images: [N, 3, H, W] in [-0.5, 0.5].  The reference's draws are unseeded; these are seeded (irec.ideal.posterior_draw: seed,
+        tag = the residual block's index, image i drawing as image number image_base + i), made on the device with no host round trip.
+        Leaves self.log_likelihood, float64 [N] in nats PER IMAGE (the reference's scalar attribute is the mean of these over the
+        batch), under the scalar likelihood_log_scale or, when they are set, the per-channel likelihood_log_scales; and every block's
+        kl for kl_divergence().  Nothing is read back.  Only likelihood_function='discretized_logistic' is built."""
+        from .. import ideal
+        if self.likelihood_function_name != "discretized_logistic":
+            raise ModelError(f"forward: the likelihood term is built for 'discretized_logistic' only, not for '{self.likelihood_function_name}'")
+        batch_size, _, height, width = images.shape
+        sample_args = {"seed": seed, "image_base": image_base}
+        with deterministic_transforms():
+            tensor = self.first_infer_conv(images)
+            for resnet_block in list(self.residual_blocks)[::-1]:
+                tensor = resnet_block(tensor, inference_pass=True)
+            tensor = self.generative_base(batch_size=batch_size, width=width, height=height)
+            for resnet_block in self.residual_blocks:
+                tensor = resnet_block(tensor, inference_pass=False, sample_args=sample_args)
+            reconstruction = self._finish(tensor)
+        log_scale = self.likelihood_log_scale if self.likelihood_log_scales is None else self.likelihood_log_scales
+        self.log_likelihood = ideal.log_likelihood(images, reconstruction, log_scale, binsize)
+        return reconstruction + 0.5
+
+    def kl_divergence(self, reduce=True):
+        """resnet_vae.py:729-750 for the last `forward`: float64 [N], the sum over the residual blocks of an image's KL in nats;
+        reduce=False: the list of the blocks' [N]."""
+        kls = [block.kl for block in self.residual_blocks]
+        if any(kl is None for kl in kls):
+            raise ModelError("kl_divergence needs a forward(images, seed) pass first")
+        return torch.stack(kls).sum(dim=0) if reduce else kls
+
+    @torch.no_grad()
+    def coded_kl(self):
+        """float64 [N]: the KL of the posteriors and priors that the last pass left in the residual blocks (after a compress pass: the
+        distributions the indices were coded under), through the kernel of irec.ideal.posterior_draw (its sample is dropped)."""
+        from .. import ideal
+        if any(block.posterior is None or block.prior is None for block in self.residual_blocks):
+            raise ModelError("coded_kl needs the posteriors and priors of a pass over some images first")
+        return torch.stack([ideal.posterior_draw(block.posterior, block.prior, 0, block.index)[1] for block in self.residual_blocks]).sum(dim=0)
 
     @torch.no_grad()
     def update_coders(self, images, seed=42, **fit_args):

@@ -5,8 +5,8 @@ eps = 0 (S = 20), block_size 1000, max_index 20 -- compress_with_lossy_model.py:
 Level 2 is [1, 8, 12, 128] (12 288 dims, 13 blocks), level 1 [1, 32, 48, 196] (301 056 dims, 302 blocks); the two coder calls
 are sequential (level 1's prior is computed from the level-2 sample).  Weights are random-init (no checkpoint exists offline):
 the numbers are throughput / round-trip evidence, not rate-distortion results.  Prints the reference's results row of every image
-(harness.compress_images_lossy(quality=True): kld, lossy_BPP, compressed_file_bits, comp_lossy_BPP, comp_time, PSNR, MS_SSIM), then
-one JSON line of the timings.
+(harness.compress_images_lossy(quality=True, ideal=True): kld, lossy_BPP, compressed_file_bits, comp_lossy_BPP, comp_time, PSNR,
+MS_SSIM, and the ideal half ideal_KL, ideal_lossy_BPP, ideal_PSNR, ideal_MS_SSIM), then one JSON line of the timings.
 """
 import argparse
 import json
@@ -85,19 +85,20 @@ def main():
                          "file_bytes": os.path.getsize(path), "blocks": [len(b) for b in block_indices],
                          "K_max": max(len(ix) for b in block_indices for ix in b),
                          "indices": sum(len(ix) for b in block_indices for ix in b)})
-    # the reference's results row (compress_with_lossy_model.py:192-270) for the same images as one batch, rate and distortion both;
-    # ideal_PSNR / ideal_MS_SSIM need the unseeded sampling forward pass the shim does not have
+    # the reference's results row (compress_with_lossy_model.py:192-270) for the same images as one batch: the compressed half, rate
+    # and distortion both, and the ideal half from a seeded sampling forward pass (ideal=True: irec.ideal's own seeded draws)
     from irec import harness
     sampler.encode, sampler.decode = orig, orig_dec
     g = torch.Generator().manual_seed(11)
     batch = torch.stack([torch.rand(args.height, args.width, 3, generator=g) for _ in range(args.images + 1)])[1:]
     batch = (batch.permute(0, 3, 1, 2).contiguous() - 0.5).cuda()
     results = harness.compress_images_lossy(m, sampler, batch, [f"kodak_{i + 1}" for i in range(args.images)], 42, 1000, out_dir,
-                                            quality=True, image_range=(-0.5, 0.5))
+                                            quality=True, ideal=True, image_range=(-0.5, 0.5))
     for r in results:
         print(json.dumps({"name": r["name"], "kld": r["kld"], "lossy_BPP": r["lossy_bpp"], "compressed_file_bits": r["comp_codelength"],
-                          "comp_lossy_BPP": r["comp_lossy_bpp"], "comp_time": r["comp_time"], "PSNR": r["psnr"], "MS_SSIM": r["ms_ssim"]}),
-              flush=True)
+                          "comp_lossy_BPP": r["comp_lossy_bpp"], "comp_time": r["comp_time"], "PSNR": r["psnr"], "MS_SSIM": r["ms_ssim"],
+                          "ideal_KL": r["ideal_kld"], "ideal_lossy_BPP": r["ideal_lossy_bpp"], "ideal_PSNR": r["ideal_psnr"],
+                          "ideal_MS_SSIM": r["ideal_ms_ssim"]}), flush=True)
     med = lambda k: sorted(r[k] for r in rows)[len(rows) // 2]   # noqa: E731
     pix = args.height * args.width
     print(json.dumps({
