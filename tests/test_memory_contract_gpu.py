@@ -45,6 +45,7 @@ import numpy as np
 import pytest
 import torch
 
+import decode_cases
 import guarded as G
 import kernel_names as kn
 import rec_device_cases as RC
@@ -421,6 +422,7 @@ def test_decode_layouts_select_both_staged_builds():
         upt = -(-n // 1000) * 4
         nw = min(upt, 12)
         assert (3 if -(-upt // nw) <= 3 else 5) == rmax and -(-upt // 12) <= 5, n
+        assert decode_cases.staged_rmax(n, 1000) == rmax and decode_cases.tensors_supported(n, 1000)   # (the full restatement of the dispatch)
     assert -(-(-(-9000 // 1000) * 4) // 12) <= 3 < -(-(-(-9001 // 1000) * 4) // 12)      # 9001 dims: the first tensor of the big build
 
 
