@@ -855,6 +855,29 @@ irec_status irec_loglik_device(const float *x, const float *loc, const float *lo
 irec_status irec_loglik_host(const float *x, const float *loc, const float *log_scales, int32_t n_scales, int32_t n_images, int32_t channels,
                              int64_t plane, double binsize, double *ll, int32_t n_threads);
 
+/* ---- the driver's resize: a batch of images shrunk bilinearly (csrc/irec_image.hip over csrc/irec_image_core.h) --------------------
+ * Replaces `tf.image.resize(image, [h - h % 64, w - w % 64])` of examples/lossy/compress_with_lossy_model.py:183-184: TF 2.1
+ * ResizeBilinear with half_pixel_centers=True and antialias=False, float32 throughout, IEEE operations only (DESIGN.md §3 "resize"
+ * and the core header write the operation sequence down).  src: n images of c channels, in_h x in_w, as [n][c][in_h][in_w]
+ * (IREC_IMAGE_NCHW) or [n][in_h][in_w][c] (IREC_IMAGE_NHWC), float32 (IREC_IMAGE_F32) or uint8 (IREC_IMAGE_U8: v = u / 255 on load);
+ * dst: the same layout with out_h x out_w, float32.  SHRINK ONLY: out_h <= in_h and out_w <= in_w (the driver never enlarges); an
+ * axis of equal sizes is not interpolated, so equal sizes are a bit-for-bit copy (of u / 255 for a uint8 source).
+ * The device entry follows irec_quality_device: device pointers, asynchronous on hip_stream, one launch, no workspace, allocation,
+ * synchronisation, copy or atomic inside, capturable into a HIP graph; it writes exactly dst.  A result is a function of the image
+ * and the sizes only: the same bits from run to run and for an image alone or inside any batch; a NaN or an infinity reaches the
+ * outputs that have it among their four taps and no other.  irec_resize_bilinear_host runs the same core over host memory on
+ * n_threads threads (0 = one per core, at most 32) and gives the device's bits, whatever n_threads is.  Null or misaligned pointers,
+ * a count or size below 1, out > in on either axis, a side above 65536, an unknown layout or dtype: IREC_E_INVALID, no launch, dst
+ * untouched. */
+#define IREC_IMAGE_NCHW 0
+#define IREC_IMAGE_NHWC 1
+#define IREC_IMAGE_F32 0
+#define IREC_IMAGE_U8 1
+irec_status irec_resize_bilinear_device(const void *src, int32_t src_dtype, int32_t n, int32_t c, int32_t in_h, int32_t in_w, int32_t out_h,
+                                        int32_t out_w, int32_t layout, float *dst, void *hip_stream);
+irec_status irec_resize_bilinear_host(const void *src, int32_t src_dtype, int32_t n, int32_t c, int32_t in_h, int32_t in_w, int32_t out_h,
+                                      int32_t out_w, int32_t layout, float *dst, int32_t n_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,9 +8,10 @@ loop on the host for CPU tensors and for samplers the kernels do not cover, as t
 """
 from . import _lib  # noqa: F401
 from . import ideal  # noqa: F401
+from . import image  # noqa: F401
 from . import metrics  # noqa: F401
 from .coding import BeamSearchCoder, Coder, CodingError, GaussianCoder  # noqa: F401
 from .coding.samplers import ImportanceSampler, Sampler  # noqa: F401
 from .engine import Engine, get_engine  # noqa: F401
 
-__all__ = ["BeamSearchCoder", "Coder", "GaussianCoder", "ImportanceSampler", "Sampler", "CodingError", "Engine", "get_engine", "metrics", "ideal"]
+__all__ = ["BeamSearchCoder", "Coder", "GaussianCoder", "ImportanceSampler", "Sampler", "CodingError", "Engine", "get_engine", "metrics", "ideal", "image"]

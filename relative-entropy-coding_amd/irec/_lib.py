@@ -285,6 +285,8 @@ SIGNATURES = {
     "irec_posterior_draw_host": (ctypes.c_int, [_vp] * 4 + [_i32, _i64, _seed, ctypes.c_uint32, _i64, _vp, _vp, _i32]),
     "irec_loglik_device": (ctypes.c_int, [_vp] * 3 + [_i32, _i32, _i32, _i64, ctypes.c_double, _vp, _vp, ctypes.c_size_t, _vp]),
     "irec_loglik_host": (ctypes.c_int, [_vp] * 3 + [_i32, _i32, _i32, _i64, ctypes.c_double, _vp, _i32]),
+    "irec_resize_bilinear_device": (ctypes.c_int, [_vp] + [_i32] * 8 + [_vp, _vp]),
+    "irec_resize_bilinear_host": (ctypes.c_int, [_vp] + [_i32] * 8 + [_vp, _i32]),
     "irec_decode_rows_status": (ctypes.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "irec_test_rows_status_host": (ctypes.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "irec_device_uniform_int": (ctypes.c_int, [_vp, _seed, _i64, _vp, _vp]),

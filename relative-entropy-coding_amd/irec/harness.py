@@ -410,7 +410,7 @@ def decompress_images_lossless(model, paths, batch=None, strict=True):
     return _decompress_images(model, paths, batch, strict, True)
 
 
-# ---- the two-level lossy model (irec.models.lossy.Large2LevelVAE): the same two drivers over ragged files -------------------------
+# ---- the lossy models (irec.models.lossy: Large2LevelVAE, Large1LevelVAE): the same two drivers over ragged files -------------------
 def _gaussian_kl_per_image(posterior, prior):
     """sum over an image's latent dims of KL(N(loc_q, scale_q) || N(loc_p, scale_p)), closed form, float64 on the device: [N]."""
     mq, sq, mp, sp = (t.to(torch.float64) for t in (posterior.loc, posterior.scale, prior.loc, prior.scale))
@@ -418,44 +418,116 @@ def _gaussian_kl_per_image(posterior, prior):
     return kl.reshape(kl.shape[0], -1).sum(dim=1)
 
 
+def _psnr_ms_ssim(reconstruction, chunk, image_range):
+    """(psnr, ms_ssim) float64 [m] on the device, irec.metrics under the reference's convention for images in image_range.  An image
+    with a side below metrics.min_side(5) = 161 has no five-scale MS-SSIM (tf.image.ssim_multiscale asserts there): its ms_ssim is
+    NaN, its psnr what it is.  Only the any-size driver brings such images; at 161 and above the call is metrics.quality, as it was."""
+    from . import metrics
+    kw = metrics.transform_for(image_range)
+    if min(chunk.shape[2:]) >= metrics.min_side(metrics.MAX_SCALES):
+        return metrics.quality(reconstruction, chunk, **kw)[:2]
+    psnr = metrics.psnr(reconstruction, chunk, **kw)
+    return psnr, torch.full_like(psnr, float("nan"))
+
+
 def _lossy_quality_columns(model, chunk, reconstruction, image_range):
     """float64 [3, m] on the device: psnr, ms_ssim of the reconstruction against the chunk (irec.metrics, the reference's convention
-    for images in image_range) and the two levels' KL in nats, from the distributions the model's last pass left.  No synchronisation."""
+    for images in image_range) and the levels' KL in nats, from the distributions the model's last pass left (a two-level model's
+    level_1_* and level_2_*, a one-level model's posterior and prior).  No synchronisation."""
     from . import metrics
-    psnr, ms_ssim, _ = metrics.quality(reconstruction, chunk, **metrics.transform_for(image_range))
-    kld = _gaussian_kl_per_image(model.level_1_posterior, model.level_1_prior) + \
-        _gaussian_kl_per_image(model.level_2_posterior, model.level_2_prior)
+    psnr, ms_ssim = _psnr_ms_ssim(reconstruction, chunk, image_range)
+    if hasattr(model, "level_1_posterior"):
+        kld = _gaussian_kl_per_image(model.level_1_posterior, model.level_1_prior) + \
+            _gaussian_kl_per_image(model.level_2_posterior, model.level_2_prior)
+    else:
+        kld = _gaussian_kl_per_image(model.posterior, model.prior)
     return torch.stack([psnr, ms_ssim, kld])
 
 
 def _lossy_ideal_columns(model, chunk, seed, image_base, image_range):
     """float64 [3, m] on the device: psnr, ms_ssim of the reconstruction of a seeded sampling pass over the chunk against the chunk, and
-    the pass's KL (both levels, irec.ideal.posterior_draw's) in nats.  No synchronisation."""
+    the pass's KL (every level's, irec.ideal.posterior_draw's, added in file order) in nats.  No synchronisation."""
     from . import metrics
     _, reconstruction = model.forward(chunk, seed=seed, image_base=image_base)
-    psnr, ms_ssim, _ = metrics.quality(reconstruction, chunk, **metrics.transform_for(image_range))
-    kl_2, kl_1 = model.kl_divergence()
-    return torch.stack([psnr, ms_ssim, kl_2 + kl_1])
+    psnr, ms_ssim = _psnr_ms_ssim(reconstruction, chunk, image_range)
+    kl, *more = model.kl_divergence()
+    for level in more:
+        kl = kl + level
+    return torch.stack([psnr, ms_ssim, kl])
+
+
+def _lossy_groups(images, resize):
+    """What compress_images_lossy codes: ([(images [m, 3, H, W] float32, members)], sizes) -- the images brought to the size they are
+    coded at and grouped by it, a group's members being its images' numbers in the call, in order, the groups in the order of their
+    first image; sizes[i] = (orig_h, orig_w, h, w), or None for the call of one 4-D float tensor as it is (resize=False), which is one
+    group and passes through untouched.  A list holds [3, h_i, w_i] tensors, float32 or uint8 (x / 255); resize=True brings every
+    image to image.driver_size(h_i, w_i) through image.resize_bilinear, images of one size in one launch.  ValueError, before
+    anything is coded, for an image below 64 x 64 or, with resize=False, one whose sides are not multiples of 64."""
+    from . import image
+    if isinstance(images, torch.Tensor) and images.dim() == 4 and not resize and images.dtype != torch.uint8:
+        return [(images, list(range(images.shape[0])))], None
+    images = list(images)
+    for i, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or im.dim() != 3 or im.shape[0] != 3 or im.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"compress_images_lossy: image {i} is not a [3, h, w] float32 or uint8 tensor")
+    sizes = []
+    for i, im in enumerate(images):
+        h, w = int(im.shape[1]), int(im.shape[2])
+        if resize:
+            sizes.append((h, w, *image.driver_size(h, w)))
+        elif h % 64 or w % 64 or not h or not w:
+            raise ValueError(f"compress_images_lossy: image {i} is {h} x {w}; the models code multiples of 64 (resize=True brings an "
+                             "image to the next one below, as the reference's driver does)")
+        else:
+            sizes.append((h, w, h, w))
+    sources, coded = {}, [None] * len(images)
+    for i, im in enumerate(images):
+        sources.setdefault((sizes[i], im.dtype), []).append(i)
+    for (size, dtype), members in sources.items():
+        stacked = torch.stack([images[i] for i in members])
+        if resize or dtype == torch.uint8:                    # (equal sizes: the copy that converts)
+            stacked = image.resize_bilinear(stacked, size[2:])
+        for k, i in enumerate(members):
+            coded[i] = stacked[k]
+    groups = {}
+    for i, size in enumerate(sizes):
+        groups.setdefault(size[2:], []).append(i)
+    return [(torch.stack([coded[i] for i in members]), members) for members in groups.values()], sizes
+
+
+def _runs(members):
+    """[(a, b)]: members[a:b] the maximal runs of consecutive numbers."""
+    cuts = [0] + [k for k in range(1, len(members)) if members[k] != members[k - 1] + 1] + [len(members)]
+    return list(zip(cuts[:-1], cuts[1:]))
 
 
 def compress_images_lossy(model, sampler, images, names, seed, block_size, out_dir, batch=None, rec_on_device=False, tables=None,
-                          quality=False, image_range=(0., 1.), segment_blocks=None, ideal=False):
-    """compress_images for Large2LevelVAE and its coder `sampler`: images [n, 3, H, W] on the model's device, in batches through
-    model.compress_rec (two coder launches per batch, one read-back), one NAME.rec per image -- byte for byte the file
-    model.compress(file_path, ...) writes for it -- read back and compared with the rows the files were built from.
+                          quality=False, image_range=(0., 1.), segment_blocks=None, ideal=False, resize=False):
+    """compress_images for a lossy model (Large2LevelVAE, Large1LevelVAE) and its coder `sampler`: images [n, 3, H, W] on the model's
+    device, in batches through model.compress_rec (one coder launch per level and batch, one read-back), one NAME.rec per image --
+    byte for byte the file model.compress(file_path, ...) writes for it -- read back and compared with the rows the files were built from.
     rec_on_device: the files are built and checked on the device (irec.io.encode_files_device_ragged / decode_files_device_ragged)
     instead of on host threads, the default.  tables: an irec.io.SymbolTables (fit_symbol_tables_lossy) the files are coded under.
     Returns one dict per image with compress_images' keys.
+    images may also be a LIST of [3, h_i, w_i] tensors, float32 or uint8 (x / 255), of any sizes: with resize=True every image is brought
+    to image.driver_size(h_i, w_i) = (h_i - h_i % 64, w_i - w_i % 64) by image.resize_bilinear -- the reference driver's
+    tf.image.resize (compress_with_lossy_model.py:183-184), on the device -- the images are grouped by the size they are coded at and
+    coded group by group in batches, and the rows come back in the order of the images, each also carrying `orig_h`, `orig_w`, `h`,
+    `w`; quality and ideal measure against the RESIZED image, as the reference does.  resize=True takes a 4-D tensor too.
+    resize=False with a list wants every side a multiple of 64: ValueError otherwise, before out_dir exists.  resize=False with one
+    4-D float tensor: the call, the work and the rows are what they were.
     quality=True: every row also carries the distortion half of the reference's results row
     (examples/lossy/compress_with_lossy_model.py:192-270) -- `psnr` and `ms_ssim` of compress_rec's reconstruction against the
     image (irec.metrics on the device: tf.image.psnr / tf.image.ssim_multiscale of clip(reconstruction) * 255 against image * 255 for
-    images in image_range, (0, 1) as the reference has them, (-0.5, 0.5) as the shim's tests do; images of at least 161 x 161),
-    `kld`, the closed-form Gaussian KL of both levels in nats (float64 on the device), and `lossy_bpp` = kld / (h w ln 2) -- all
+    images in image_range, (0, 1) as the reference has them, (-0.5, 0.5) as the shim's tests do; images of at least 161 x 161 for all
+    five scales of ms_ssim, fewer scales below),
+    `kld`, the closed-form Gaussian KL of every level in nats (float64 on the device), and `lossy_bpp` = kld / (h w ln 2) -- all
     of it in ONE extra read-back per batch.  quality=False: the rows and the work are as before.
     ideal=True: every row also carries the ideal half of that row (compress_with_lossy_model.py:193-215), from a seeded sampling
     forward pass over the batch (model.forward(chunk, seed=seed, image_base=the image's number in the call): the library's own seeded
-    draws, irec.ideal, where the reference's are unseeded) -- `ideal_psnr` and `ideal_ms_ssim` of that pass's reconstruction
-    (irec.metrics, as above), `ideal_kld`, both levels' KL in nats through irec.ideal's kernel, and `ideal_lossy_bpp` =
+    draws, irec.ideal, where the reference's are unseeded; a batch of a group whose images are not neighbours in the call takes one
+    pass per run of neighbours) -- `ideal_psnr` and `ideal_ms_ssim` of that pass's reconstruction
+    (irec.metrics, as above), `ideal_kld`, every level's KL in nats through irec.ideal's kernel, and `ideal_lossy_bpp` =
     ideal_kld / (h w ln 2) -- read back with the batch's one extra copy.  ideal=False: the rows and the work are as before.
     segment_blocks: None for the reference's files; g >= 1 writes NAME.recs, the segmented container (model.compress_rec has the
     description; default symbol models only, so together with tables it is a ValueError), on host threads or on the device alike."""
@@ -463,47 +535,59 @@ def compress_images_lossy(model, sampler, images, names, seed, block_size, out_d
     if segment_blocks is not None and tables is not None:
         raise ValueError("compress_images_lossy: the segmented container codes under the default symbol models only (tables= with segment_blocks=)")
     seed = header_seed(seed, "compress_images_lossy")      # (before out_dir is made or a batch coded)
+    groups, sizes = _lossy_groups(images, resize)           # (likewise)
     os.makedirs(out_dir, exist_ok=True)
-    n = images.shape[0]
-    batch = n if not batch else int(batch)
     S = model._max_index(sampler)
     ragged, segmented = (decode_files_device_ragged, decode_files_device_segmented) if rec_on_device else (decode_files_ragged, decode_files_segmented)
+    out = [None] * sum(len(members) for _, members in groups)
 
-    def leg(lo, hi):
-        chunk = images[lo:hi]
-        _, _, h, w = chunk.shape
-        t0 = time.perf_counter()
-        (blob, off, reconstruction), (K, idx, bpr) = model.compress_rec(chunk, seed, sampler, block_size=block_size, rec_on_device=rec_on_device,
-                                                                        return_pendings=True, tables=tables, segment_blocks=segment_blocks)
-        columns = _lossy_quality_columns(model, chunk, reconstruction, image_range) if quality else None   # (launched; read below)
-        if ideal:                                                            # (after the quality columns: the pass replaces the model's distributions)
-            ideal_columns = _lossy_ideal_columns(model, chunk, seed, lo, image_range)
-            columns = ideal_columns if columns is None else torch.cat([columns, ideal_columns])
-        t_compress, t1 = time.perf_counter() - t0, time.perf_counter()
-        if segment_blocks is None:
-            decode = lambda b, o: ragged(b, o, bpr, idx.shape[2], tables=tables)  # noqa: E731
-        else:
-            decode = lambda b, o: segmented(b, o, bpr, idx.shape[2], segment_blocks)  # noqa: E731
-        rows = _check_leg(out_dir, names[lo:hi], "rec" if segment_blocks is None else "recs", blob, off, K, idx, decode,
-                          (seed, block_size, h, w, 3), S, t_compress, t1)
-        host = columns.cpu().numpy() if (quality or ideal) else None         # the one extra read-back
-        if quality:
-            psnr, ms_ssim, kld = host[:3]
-            for i, row in enumerate(rows):
-                row.update({"psnr": float(psnr[i]), "ms_ssim": float(ms_ssim[i]), "kld": float(kld[i]),
-                            "lossy_bpp": float(kld[i]) / (h * w * float(np.log(2.0)))})
-        if ideal:
-            psnr, ms_ssim, kld = host[-3:]
-            for i, row in enumerate(rows):
-                row.update({"ideal_psnr": float(psnr[i]), "ideal_ms_ssim": float(ms_ssim[i]), "ideal_kld": float(kld[i]),
-                            "ideal_lossy_bpp": float(kld[i]) / (h * w * float(np.log(2.0)))})
-        return rows
-    return [row for rows in _in_batches(n, batch, names, leg) for row in rows]
+    for group, members in groups:
+        group_names = [names[i] for i in members]
+
+        def leg(lo, hi):
+            chunk = group[lo:hi]
+            _, _, h, w = chunk.shape
+            t0 = time.perf_counter()
+            (blob, off, reconstruction), (K, idx, bpr) = model.compress_rec(chunk, seed, sampler, block_size=block_size, rec_on_device=rec_on_device,
+                                                                            return_pendings=True, tables=tables, segment_blocks=segment_blocks)
+            columns = _lossy_quality_columns(model, chunk, reconstruction, image_range) if quality else None   # (launched; read below)
+            if ideal:                                                            # (after the quality columns: the pass replaces the model's distributions)
+                ideal_columns = [_lossy_ideal_columns(model, chunk[a:b], seed, members[lo + a], image_range) for a, b in _runs(members[lo:hi])]
+                ideal_columns = ideal_columns[0] if len(ideal_columns) == 1 else torch.cat(ideal_columns, dim=1)
+                columns = ideal_columns if columns is None else torch.cat([columns, ideal_columns])
+            t_compress, t1 = time.perf_counter() - t0, time.perf_counter()
+            if segment_blocks is None:
+                decode = lambda b, o: ragged(b, o, bpr, idx.shape[2], tables=tables)  # noqa: E731
+            else:
+                decode = lambda b, o: segmented(b, o, bpr, idx.shape[2], segment_blocks)  # noqa: E731
+            rows = _check_leg(out_dir, group_names[lo:hi], "rec" if segment_blocks is None else "recs", blob, off, K, idx, decode,
+                              (seed, block_size, h, w, 3), S, t_compress, t1)
+            host = columns.cpu().numpy() if (quality or ideal) else None         # the one extra read-back
+            if quality:
+                psnr, ms_ssim, kld = host[:3]
+                for i, row in enumerate(rows):
+                    row.update({"psnr": float(psnr[i]), "ms_ssim": float(ms_ssim[i]), "kld": float(kld[i]),
+                                "lossy_bpp": float(kld[i]) / (h * w * float(np.log(2.0)))})
+            if ideal:
+                psnr, ms_ssim, kld = host[-3:]
+                for i, row in enumerate(rows):
+                    row.update({"ideal_psnr": float(psnr[i]), "ideal_ms_ssim": float(ms_ssim[i]), "ideal_kld": float(kld[i]),
+                                "ideal_lossy_bpp": float(kld[i]) / (h * w * float(np.log(2.0)))})
+            return rows
+        m = len(members)
+        for i, row in zip(members, (row for rows in _in_batches(m, m if not batch else int(batch), group_names, leg) for row in rows)):
+            if sizes is not None and "error" not in row:
+                row.update(dict(zip(("orig_h", "orig_w", "h", "w"), sizes[i])))
+            out[i] = row
+    return out
 
 
 def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_on_device=False, tables=None):
-    """decompress_images for Large2LevelVAE and its coder `sampler`: .rec files -> (images, rows), the files grouped by header (seed,
-    shape, block structure) and each group decoded in batches by model.decompress_rec -- on host threads, or with rec_on_device on
+    """decompress_images for a lossy model (Large2LevelVAE, Large1LevelVAE) and its coder `sampler`: .rec files -> (images, rows), the
+    files grouped by header (seed, shape, block structure) -- files of several image sizes, as compress_images_lossy writes for a list,
+    decode in one call and come back as a list in the order of `paths`; a file whose block structure is not the model's own (another
+    level count among them: a two-level file under a one-level model) has status 17 -- and each group decoded in batches by
+    model.decompress_rec -- on host threads, or with rec_on_device on
     the device -- with one read-back per batch, the per-image status.  images, rows and strict as decompress_images has them.
     tables: the irec.io.SymbolTables the files were written under (files without header flags decode in the same call).
     Segmented files (NAME.recs) are told from the reference's by their magic and decoded in groups of their own, under the
@@ -512,8 +596,10 @@ def decompress_images_lossy(model, sampler, paths, batch=None, strict=True, rec_
 
     def fits(info, key):
         _, (h, w, c), R, _ = key
-        return R == 2 and c == 3 and h % 64 == 0 and w % 64 == 0 and h > 0 and w > 0 and info.get("segment_blocks") != 0 and \
-            list(info["bpt"]) == model.blocks_per_res((1, c, h, w), sampler.block_size)
+        if not (c == 3 and h % 64 == 0 and w % 64 == 0 and h > 0 and w > 0 and info.get("segment_blocks") != 0):
+            return False
+        bpr = model.blocks_per_res((1, c, h, w), sampler.block_size)    # (one entry per level: a file of R blocks is a model of R levels')
+        return R == len(bpr) and list(info["bpt"]) == bpr
 
     def decode(part, info, blob, off, seed, shape, max_K):
         g = info.get("segment_blocks")                   # None: the reference's container
@@ -571,7 +657,8 @@ def fit_likelihood_scale(model, images, seed, per_channel=False, batch=None, blo
 
 
 def fit_symbol_tables_lossy(model, sampler, images, seed, block_size, batch=None, max_K=None):
-    """fit_symbol_tables for Large2LevelVAE and its coder `sampler`: one index table, one count table for each of the two levels.
+    """fit_symbol_tables for a lossy model (Large2LevelVAE, Large1LevelVAE) and its coder `sampler`: one index table, one count table
+    for each of the model's levels.
     block_size: the coder's, as compress_images_lossy takes it (the layout is the sampler's own)."""
     from .coding.pending import PendingCode
     n = images.shape[0]

@@ -1,12 +1,18 @@
-"""PyTorch-ROCm host shim of the reference's two-level lossy VAE call surface
-(rec/models/lossy/large_2_level_vae.py:320-456): `call(tensor, sampling_fn)`, `compress(file_path, image, seed, sampler,
-block_size, max_index)` and `decompress(file_path, sampler)` -- two SEQUENTIAL `sampler.encode` calls per image
-(level 2, then level 1 whose prior is synthesised from the coded level-2 latent) followed by `write_compressed_code`.
+"""PyTorch-ROCm host shims of the reference's lossy VAE call surfaces: the two-level model
+(rec/models/lossy/large_2_level_vae.py:320-456) and the one-level model, the lossy driver's default
+(rec/models/lossy/large_1_level_vae.py:120-244) -- `call(tensor, sampling_fn)`, `compress(file_path, image, seed, sampler,
+block_size, max_index)` and `decompress(file_path, sampler)`: one `sampler.encode` call per level and image, SEQUENTIAL where there
+are two (level 2, then level 1 whose prior is synthesised from the coded level-2 latent), followed by `write_compressed_code`.
 
 As with the RVAE shim, only the hand-off is modelled: the Balle-style analysis / synthesis transforms are plain strided
 (transposed) convolutions with random-init weights (GDN, SignalConv2D and the trained checkpoints are out of scope,
-SURVEY.md §2 rows 12-14).  Latent shapes follow the reference: level 1 = [1, H/16, W/16, 196], level 2 = [1, H/64, W/64, 128]
-(large_2_level_vae.py:313, compress_with_lossy_model.py:36-37), handed to the coder in NHWC order.
+SURVEY.md §2 rows 12-14).  Latent shapes follow the reference: two levels, level 1 = [1, H/16, W/16, 196], level 2 = [1, H/64, W/64, 128]
+(large_2_level_vae.py:313, compress_with_lossy_model.py:36-37); one level, [1, H/16, W/16, num_filters], 192 by default
+(large_1_level_vae.py:155, compress_with_lossy_model.py:26-35) -- handed to the coder in NHWC order.
+
+What the two models share -- everything but their transforms and the order of their levels -- is _LevelsVAE: a model names its levels
+in file order (`_latent_dims`, `_ideal_tags`), codes them (`_code_levels`) and decodes them (`_decode_levels`); the list path, the
+packed path and the .rec paths are written once over those.
 """
 import numpy as np
 import torch
@@ -37,49 +43,36 @@ def _up(cin, cmid, cout, n):
     return nn.Sequential(*layers)
 
 
-class Large2LevelVAE(nn.Module):
-    def __init__(self, level_1_filters=196, level_2_filters=128, name="large_level_2_vae", **kwargs):
-        super().__init__()
-        self.level_1_filters, self.level_2_filters = level_1_filters, level_2_filters
-        f1, f2 = level_1_filters, level_2_filters
-        self.analysis_transform = _down(3, 2 * f1, 4)                      # -> loc | log_scale, H/16
-        self.hyper_analysis_transform = _down(f1, 2 * f2, 2)               # -> loc | log_scale, H/64
-        self.hyper_synthesis_transform = _up(f2, f1, 2 * f1, 2)            # -> level-1 prior loc | log_scale
-        self.synthesis_transform = _up(f1, f1, 3, 4)
-        self._prior_base = nn.Parameter(torch.zeros(1, f2, 1, 1))
-        self._prior_conv = nn.Conv2d(f2, f2, 3, padding=1)
-        self._prior_loc_head = nn.Conv2d(f2, f2, 3, padding=1)
-        self._prior_log_scale_head = nn.Conv2d(f2, f2, 3, padding=1)
-        self._level_1_posterior_loc_combiner = nn.Conv2d(2 * f1, f1, 1)
-        self._level_1_posterior_log_scale_combiner = nn.Conv2d(2 * f1, f1, 1)
+class _LevelsVAE(nn.Module):
+    """The call surface of a lossy model of R = len(_ideal_tags) levels, the levels in FILE order (block_indices[r], the rows of residual
+    block r).  A model supplies:
+      _ideal_tags                    irec.ideal.posterior_draw's tag per level, in file order
+      _latent_dims(h, w)             the latent elements per level of an h x w image
+      _code_levels(tensor, sampling_fn) -> (block_indices, y NHWC): the inference and generative passes up to the coded last latent,
+                                     one sampling_fn(target=posterior, coder=prior) call per level, the distributions left as attributes
+      _decode_levels(n, h, w, decode) -> y NHWC: the generative pass, decode(prior, r) giving level r's latent
+      synthesis_transform, _prior_base"""
+    _ideal_tags = ()
 
-    def prior_base(self, batch_size, height, width):
-        """large_2_level_vae.py:312-313."""
-        return self._prior_base.expand(batch_size, -1, height // 64, width // 64).contiguous()
-
-    def _level_2_prior(self, batch_size, height, width):
-        t = F.elu(self._prior_conv(self.prior_base(batch_size, height, width)))
-        return self._prior_loc_head(t), F.softplus(self._prior_log_scale_head(t)) + 1e-7
-
-    def _level_1_prior(self, level_2_latent):
-        loc, log_scale = torch.chunk(self.hyper_synthesis_transform(level_2_latent), 2, dim=1)
-        return loc, F.softplus(log_scale) + 1e-7, log_scale
+    @property
+    def n_levels(self):
+        return len(self._ideal_tags)
 
     @torch.no_grad()
     def forward(self, tensor, sampling_fn=None, seed=None, image_base=0):
-        """large_2_level_vae.py:320-404.  tensor: [N, 3, H, W] (the reference's N = 1, or a batch that `sampling_fn` codes with
-        batched=True); returns ([level_2_indices, level_1_indices], reconstruction).
-        seed (instead of sampling_fn): the sampling pass of the reference's evaluation script (`model(image)`) -- level 2 is DRAWN from
-        its posterior (irec.ideal.posterior_draw, tag 2), the level-1 prior synthesised from the draw, level 1 drawn (tag 1), image i
-        drawing as image number image_base + i; nothing is coded or read back.  Returns (None, reconstruction) and leaves the two
-        levels' KL for kl_divergence()."""
+        """large_2_level_vae.py:320-404, large_1_level_vae.py:160-203.  tensor: [N, 3, H, W] (the reference's N = 1, or a batch that
+        `sampling_fn` codes with batched=True); returns (block_indices, reconstruction), block_indices one entry per level.
+        seed (instead of sampling_fn): the sampling pass of the reference's evaluation script (`model(image)`) -- every level is DRAWN
+        from its posterior (irec.ideal.posterior_draw under the level's tag: 2 and 1 for the two levels of Large2LevelVAE, the level-1
+        prior synthesised from the level-2 draw; 3 for the one level of Large1LevelVAE), image i drawing as image number
+        image_base + i; nothing is coded or read back.  Returns (None, reconstruction) and leaves the levels' KL for kl_divergence()."""
         if sampling_fn is None and seed is None:
             raise NotImplementedError("training / sampling passes are outside the compression shim")
         if seed is not None:
             if sampling_fn is not None:
                 raise ValueError("forward takes sampling_fn (a coded pass) or seed (a sampling pass), not both")
             from .. import ideal
-            levels, kls = iter((2, 1)), []
+            levels, kls = iter(self._ideal_tags), []
 
             def sampling_fn(target, coder):
                 sample, kl = ideal.posterior_draw(target, coder, seed, next(levels), image_base)
@@ -92,30 +85,14 @@ class Large2LevelVAE(nn.Module):
         return block_indices, self.synthesis_transform(_nchw(y))
 
     def kl_divergence(self):
-        """large_2_level_vae.py's kl_divergence for the last forward(tensor, seed=): [kl_level_2, kl_level_1], float64 [N] each, nats."""
+        """The reference's kl_divergence for the last forward(tensor, seed=): one float64 [N] per level, in file order ([kl_level_2,
+        kl_level_1]; [kl] for one level), nats."""
         if getattr(self, "_kl", None) is None:
             raise ModelError("kl_divergence needs a forward(tensor, seed=) pass first")
         return list(self._kl)
 
-    def _code_levels(self, tensor, sampling_fn):
-        """`forward` up to the coded level-1 sample: ([level_2_indices, level_1_indices], y NHWC)."""
-        batch_size, _, height, width = tensor.shape
-        l1_post_loc, l1_post_log_scale = torch.chunk(self.analysis_transform(tensor), 2, dim=1)
-        l2_post_loc, l2_post_log_scale = torch.chunk(self.hyper_analysis_transform(l1_post_loc), 2, dim=1)
-        self.level_2_posterior = _Normal(_nhwc(l2_post_loc), _nhwc(F.softplus(l2_post_log_scale) + 1e-7))
-        l2_prior_loc, l2_prior_scale = self._level_2_prior(batch_size, height, width)
-        self.level_2_prior = _Normal(_nhwc(l2_prior_loc), _nhwc(l2_prior_scale))
-        level_2_indices, z = sampling_fn(target=self.level_2_posterior, coder=self.level_2_prior)            # :359-360
-        l1_prior_loc, l1_prior_scale, l1_prior_log_scale = self._level_1_prior(_nchw(z))
-        loc = self._level_1_posterior_loc_combiner(F.elu(torch.cat([l1_post_loc, l1_prior_loc], dim=1)))
-        log_scale = self._level_1_posterior_log_scale_combiner(F.elu(torch.cat([l1_post_log_scale, l1_prior_log_scale], dim=1)))
-        self.level_1_prior = _Normal(_nhwc(l1_prior_loc), _nhwc(l1_prior_scale))
-        self.level_1_posterior = _Normal(_nhwc(loc), _nhwc(F.softplus(log_scale) + 1e-7))
-        level_1_indices, y = sampling_fn(target=self.level_1_posterior, coder=self.level_1_prior)            # :394-395
-        return [level_2_indices, level_1_indices], y
-
     def compress(self, file_path, image, seed, sampler, block_size, max_index):
-        """large_2_level_vae.py:406-419.  image: [H, W, 3] tensor (the reference's layout)."""
+        """large_2_level_vae.py:406-419, large_1_level_vae.py:205-218.  image: [H, W, 3] tensor (the reference's layout)."""
         seed = header_seed(seed, "compress")               # (before anything is coded: the file could not name another seed)
         sampling_fn = lambda target, coder: sampler.encode(target, coder, seed=seed)  # noqa: E731  (:408)
         x = image.permute(2, 0, 1)[None].contiguous()
@@ -127,26 +104,21 @@ class Large2LevelVAE(nn.Module):
 
     @torch.no_grad()
     def decompress(self, file_path, sampler):
-        """large_2_level_vae.py:421-456 (the reference unpacks image_shape as (batch, height, width); here (h, w, c))."""
+        """large_2_level_vae.py:421-456, large_1_level_vae.py:220-244 (the reference unpacks image_shape as (batch, height, width);
+        here (h, w, c))."""
         seed, image_shape, block_size, block_indices = read_compressed_code(file_path=file_path)
         height, width, _ = image_shape
         with deterministic_transforms():
-            l2_prior_loc, l2_prior_scale = self._level_2_prior(1, height, width)
-            self.level_2_prior = _Normal(_nhwc(l2_prior_loc), _nhwc(l2_prior_scale))
-            z = sampler.decode(self.level_2_prior, seed=seed, indices=block_indices[0])                       # :441
-            l1_prior_loc, l1_prior_scale, _ = self._level_1_prior(_nchw(z))
-            self.level_1_prior = _Normal(_nhwc(l1_prior_loc), _nhwc(l1_prior_scale))
-            y = sampler.decode(self.level_1_prior, seed=seed, indices=block_indices[1])                       # :451
+            y = self._decode_levels(1, height, width, lambda prior, r: sampler.decode(prior, seed=seed, indices=block_indices[r]))
             return self.synthesis_transform(_nchw(y))
 
     # ---- the packed path: a batch per call, indices as rows (K [N, T], idx [N, T, max_K]), ragged .rec files ----------------------
-    # The two levels differ in size (a Kodak image: 13 coder blocks at level 2, 302 at level 1), so an image is T = sum(blocks_per_res)
-    # rows, level 2's first -- file order, block_indices = [level_2, level_1].
+    # The levels differ in size (a Kodak image under Large2LevelVAE: 13 coder blocks at level 2, 302 at level 1), so an image is
+    # T = sum(blocks_per_res) rows in file order, block_indices = [level_2, level_1]; one level is R = 1 of the same containers.
     def blocks_per_res(self, image_shape, block_size):
-        """[level-2 blocks, level-1 blocks] of an image (Coder.split, coder.py:69-83).  image_shape: [N, 3, H, W]."""
+        """The coder blocks of an image's levels, in file order (Coder.split, coder.py:69-83).  image_shape: [N, 3, H, W]."""
         _, _, h, w = image_shape
-        dims = [(h // 64) * (w // 64) * self.level_2_filters, (h // 16) * (w // 16) * self.level_1_filters]
-        return [1 if block_size is None else -(-n // int(block_size)) for n in dims]
+        return [1 if block_size is None else -(-n // int(block_size)) for n in self._latent_dims(h, w)]
 
     @staticmethod
     def _max_index(sampler):
@@ -154,8 +126,8 @@ class Large2LevelVAE(nn.Module):
         return sampler.sampler.n_samples() if getattr(sampler, "sampler", None) is not None else sampler.n_samples
 
     def _compress_device(self, images, seed, sampler):
-        """The coding half of a batched compress, on the device with no host synchronisation: ([level-2, level-1] PendingCode, y).  The
-        two calls are sequential (level 1's prior comes from the coded level-2 sample) and deferred."""
+        """The coding half of a batched compress, on the device with no host synchronisation: (one PendingCode per level, y).  The
+        calls are sequential (level 1's prior comes from the coded level-2 sample) and deferred."""
         sampling_fn = lambda target, coder: sampler.encode(target, coder, seed=seed, batched=True, defer=True)  # noqa: E731
         with deterministic_transforms():
             return self._code_levels(images, sampling_fn)
@@ -218,12 +190,8 @@ class Large2LevelVAE(nn.Module):
                              f"{tuple(image_shape)} are coded in {bpr} blocks")
         rows = packed_rows(n, bpr, K.device)
         with deterministic_transforms():
-            l2_prior_loc, l2_prior_scale = self._level_2_prior(n, height, width)
-            self.level_2_prior = _Normal(_nhwc(l2_prior_loc), _nhwc(l2_prior_scale))
-            z = sampler.decode(self.level_2_prior, None, seed=seed, batched=True, packed=(K, idx, rows[0]), status=status)
-            l1_prior_loc, l1_prior_scale, _ = self._level_1_prior(_nchw(z))
-            self.level_1_prior = _Normal(_nhwc(l1_prior_loc), _nhwc(l1_prior_scale))
-            y = sampler.decode(self.level_1_prior, None, seed=seed, batched=True, packed=(K, idx, rows[1]), status=status)
+            y = self._decode_levels(n, height, width, lambda prior, r: sampler.decode(prior, None, seed=seed, batched=True,
+                                                                                      packed=(K, idx, rows[r]), status=status))
             return self.synthesis_transform(_nchw(y))
 
     @staticmethod
@@ -249,7 +217,8 @@ class Large2LevelVAE(nn.Module):
         """The inverse of compress_rec: N .rec files (file i = blob[offsets[i]:offsets[i + 1]]) to reconstructions [N, 3, H, W].
         rec_on_device=False: the files are read on host threads (irec.io.decode_files_ragged; blob / offsets numpy or tensors) and the
         rows uploaded once; rec_on_device=True: blob is a CUDA tensor and the rows never leave the device
-        (irec.io.decode_files_device_ragged's launch form).  Either way the headers are checked against seed, image_shape and R = 2,
+        (irec.io.decode_files_device_ragged's launch form).  Either way the headers are checked against seed, image_shape and the
+        model's level count (R = 2 for Large2LevelVAE, R = 1 for Large1LevelVAE: a file of the other model is refused with a status),
         each level's coder reads its rows in place and checks them on the device, and there is ONE read-back, the per-image status, in
         the encoding of BidirectionalResNetVAE.decompress_rec: 0 ok; 1 .. 18 irec_rec_status; STATUS_HEADER; STATUS_ROWS +
         irec_rows_status; first cause in that order.  strict: CodingError with the cause, "(image i)" appended; strict=False:
@@ -272,5 +241,107 @@ class Large2LevelVAE(nn.Module):
             raise ModelError(f"{len(rec_status)} files for images of shape {tuple(image_shape)}")
         rows_status = torch.zeros(n, dtype=torch.int32, device=device)
         reconstruction = self._decompress_device(K, idx, seed, image_shape, sampler, rows_status)
-        joined = join_status(rec_status, words, header_want(seed, (n, 3, height, width), 2, device), rows_status)
+        joined = join_status(rec_status, words, header_want(seed, (n, 3, height, width), self.n_levels, device), rows_status)
         return finish(reconstruction, joined.cpu().numpy(), strict)
+
+
+class Large2LevelVAE(_LevelsVAE):
+    _ideal_tags = (2, 1)                                                       # file order: level 2, then level 1
+
+    def __init__(self, level_1_filters=196, level_2_filters=128, name="large_level_2_vae", **kwargs):
+        super().__init__()
+        self.level_1_filters, self.level_2_filters = level_1_filters, level_2_filters
+        f1, f2 = level_1_filters, level_2_filters
+        self.analysis_transform = _down(3, 2 * f1, 4)                      # -> loc | log_scale, H/16
+        self.hyper_analysis_transform = _down(f1, 2 * f2, 2)               # -> loc | log_scale, H/64
+        self.hyper_synthesis_transform = _up(f2, f1, 2 * f1, 2)            # -> level-1 prior loc | log_scale
+        self.synthesis_transform = _up(f1, f1, 3, 4)
+        self._prior_base = nn.Parameter(torch.zeros(1, f2, 1, 1))
+        self._prior_conv = nn.Conv2d(f2, f2, 3, padding=1)
+        self._prior_loc_head = nn.Conv2d(f2, f2, 3, padding=1)
+        self._prior_log_scale_head = nn.Conv2d(f2, f2, 3, padding=1)
+        self._level_1_posterior_loc_combiner = nn.Conv2d(2 * f1, f1, 1)
+        self._level_1_posterior_log_scale_combiner = nn.Conv2d(2 * f1, f1, 1)
+
+    def prior_base(self, batch_size, height, width):
+        """large_2_level_vae.py:312-313."""
+        return self._prior_base.expand(batch_size, -1, height // 64, width // 64).contiguous()
+
+    def _latent_dims(self, h, w):
+        return [(h // 64) * (w // 64) * self.level_2_filters, (h // 16) * (w // 16) * self.level_1_filters]
+
+    def _level_2_prior(self, batch_size, height, width):
+        t = F.elu(self._prior_conv(self.prior_base(batch_size, height, width)))
+        return self._prior_loc_head(t), F.softplus(self._prior_log_scale_head(t)) + 1e-7
+
+    def _level_1_prior(self, level_2_latent):
+        loc, log_scale = torch.chunk(self.hyper_synthesis_transform(level_2_latent), 2, dim=1)
+        return loc, F.softplus(log_scale) + 1e-7, log_scale
+
+    def _code_levels(self, tensor, sampling_fn):
+        """`forward` up to the coded level-1 sample: ([level_2_indices, level_1_indices], y NHWC)."""
+        batch_size, _, height, width = tensor.shape
+        l1_post_loc, l1_post_log_scale = torch.chunk(self.analysis_transform(tensor), 2, dim=1)
+        l2_post_loc, l2_post_log_scale = torch.chunk(self.hyper_analysis_transform(l1_post_loc), 2, dim=1)
+        self.level_2_posterior = _Normal(_nhwc(l2_post_loc), _nhwc(F.softplus(l2_post_log_scale) + 1e-7))
+        l2_prior_loc, l2_prior_scale = self._level_2_prior(batch_size, height, width)
+        self.level_2_prior = _Normal(_nhwc(l2_prior_loc), _nhwc(l2_prior_scale))
+        level_2_indices, z = sampling_fn(target=self.level_2_posterior, coder=self.level_2_prior)            # :359-360
+        l1_prior_loc, l1_prior_scale, l1_prior_log_scale = self._level_1_prior(_nchw(z))
+        loc = self._level_1_posterior_loc_combiner(F.elu(torch.cat([l1_post_loc, l1_prior_loc], dim=1)))
+        log_scale = self._level_1_posterior_log_scale_combiner(F.elu(torch.cat([l1_post_log_scale, l1_prior_log_scale], dim=1)))
+        self.level_1_prior = _Normal(_nhwc(l1_prior_loc), _nhwc(l1_prior_scale))
+        self.level_1_posterior = _Normal(_nhwc(loc), _nhwc(F.softplus(log_scale) + 1e-7))
+        level_1_indices, y = sampling_fn(target=self.level_1_posterior, coder=self.level_1_prior)            # :394-395
+        return [level_2_indices, level_1_indices], y
+
+    def _decode_levels(self, n, height, width, decode):
+        """large_2_level_vae.py:430-451."""
+        l2_prior_loc, l2_prior_scale = self._level_2_prior(n, height, width)
+        self.level_2_prior = _Normal(_nhwc(l2_prior_loc), _nhwc(l2_prior_scale))
+        z = decode(self.level_2_prior, 0)                                                                     # :441
+        l1_prior_loc, l1_prior_scale, _ = self._level_1_prior(_nchw(z))
+        self.level_1_prior = _Normal(_nhwc(l1_prior_loc), _nhwc(l1_prior_scale))
+        return decode(self.level_1_prior, 1)                                                                  # :451
+
+
+class Large1LevelVAE(_LevelsVAE):
+    """The lossy driver's default model (compress_with_lossy_model.py:26, :137-140): one latent [N, H/16, W/16, num_filters].  Plain
+    strided convolutions stand in for the reference's SignalConv2D / GDN stacks (only the hand-off is modelled): four stride-2 layers
+    down to H/16 ending in the loc | log-scale heads, four up."""
+    _ideal_tags = (3,)                                                         # (the two-level model's levels draw under 2 and 1)
+
+    def __init__(self, num_filters=192, name="large_1_level_vae", **kwargs):
+        super().__init__()
+        self.num_filters = f = num_filters
+        self.analysis_transform = _down(3, 2 * f, 4)                           # -> posterior loc | log_scale, H/16 (:63-70)
+        self.synthesis_transform = _up(f, f, 3, 4)
+        self._prior_base = nn.Parameter(torch.zeros(1, f, 1, 1))               # :125
+        self._prior_conv = nn.Conv2d(f, f, 3, padding=1)
+        self._prior_loc_head = nn.Conv2d(f, f, 3, padding=1)
+        self._prior_log_scale_head = nn.Conv2d(f, f, 3, padding=1)
+
+    def prior_base(self, batch_size, height, width):
+        """large_1_level_vae.py:154-155."""
+        return self._prior_base.expand(batch_size, -1, height // 16, width // 16).contiguous()
+
+    def _latent_dims(self, h, w):
+        return [(h // 16) * (w // 16) * self.num_filters]
+
+    def _prior(self, batch_size, height, width):
+        """large_1_level_vae.py:177-186 (and :229-237)."""
+        t = F.elu(self._prior_conv(self.prior_base(batch_size, height, width)))
+        return _Normal(_nhwc(self._prior_loc_head(t)), _nhwc(F.softplus(self._prior_log_scale_head(t))))
+
+    def _code_levels(self, tensor, sampling_fn):
+        """`forward` up to the coded sample: ([indices], y NHWC) (:168-194)."""
+        batch_size, _, height, width = tensor.shape
+        loc, log_scale = torch.chunk(self.analysis_transform(tensor), 2, dim=1)
+        self.posterior = _Normal(_nhwc(loc), _nhwc(F.softplus(log_scale)))
+        self.prior = self._prior(batch_size, height, width)
+        indices, y = sampling_fn(target=self.posterior, coder=self.prior)                                     # :193-194
+        return [indices], y
+
+    def _decode_levels(self, n, height, width, decode):
+        self.prior = self._prior(n, height, width)
+        return decode(self.prior, 0)                                                                          # :240

@@ -13,7 +13,11 @@ synchronise).  Each at --scale 0.2 on the random-init head weights (K = 1 per bl
 scale at which a level-1 block takes 100 partitions or more -- the regime of a trained model at 0.2-1 bpp); the measured K range and
 indices per image are reported.
 Shapes: Kodak size (768 x 512: 13 + 302 blocks per image) at N = 1, 8, 24 and 64 x 64 crops (1 + 4 blocks) at N = 300.  Before anything
-is timed the packed paths' files are compared byte for byte, and at N = 1 with the list path's."""
+is timed the packed paths' files are compared byte for byte, and at N = 1 with the list path's.
+
+--model 1: the same three paths for the one-level model (Large1LevelVAE, the lossy driver's default: one level of 48 x 32 x 192 latents,
+295 blocks, on a Kodak-size image) on the Kodak-size shapes, written to profiles/lossy/bench_one_level.json; the search then looks at
+the one level, and the rows' K_level_2 is null."""
 import argparse
 import json
 import os
@@ -46,13 +50,15 @@ def median_ms(fn, reps, warmup):
     return [round(statistics.median(ts), 3), round(min(ts), 3), round(max(ts), 3)]
 
 
-def model_at(scale):
-    from irec.models import Large2LevelVAE
+def model_at(scale, levels=2):
+    from irec.models import Large1LevelVAE, Large2LevelVAE
     torch.manual_seed(3)
-    m = Large2LevelVAE().cuda().eval()
+    m = (Large2LevelVAE() if levels == 2 else Large1LevelVAE()).cuda().eval()
+    heads = (m.analysis_transform[-1], m.hyper_analysis_transform[-1], m.hyper_synthesis_transform[-1], m._prior_loc_head,
+             m._prior_log_scale_head, m._level_1_posterior_loc_combiner, m._level_1_posterior_log_scale_combiner) if levels == 2 else \
+        (m.analysis_transform[-1], m._prior_loc_head, m._prior_log_scale_head)
     with torch.no_grad():
-        for mod in (m.analysis_transform[-1], m.hyper_analysis_transform[-1], m.hyper_synthesis_transform[-1], m._prior_loc_head,
-                    m._prior_log_scale_head, m._level_1_posterior_loc_combiner, m._level_1_posterior_log_scale_combiner):
+        for mod in heads:
             mod.weight.mul_(scale)
     return m
 
@@ -73,7 +79,8 @@ def read_files(paths):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lossy", "bench.json"))
+    ap.add_argument("--model", type=int, choices=(1, 2), default=2, help="the levels of the model: Large2LevelVAE, or Large1LevelVAE")
+    ap.add_argument("--out", default=None, help="default: profiles/lossy/bench.json, bench_one_level.json with --model 1")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--scale", type=float, default=0.2)
@@ -84,26 +91,30 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_lossy.py measures a GPU: none here")
     import irec
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "lossy", "bench.json" if args.model == 2 else "bench_one_level.json")
+    shapes = SHAPES if args.model == 2 else SHAPES[:3]
     rows, search = [], []
     if args.high_scale is None:                  # the random-init weights have no natural scale: find the one that gives a trained model's K
         g = torch.Generator().manual_seed(11)
         probe = (torch.rand(1, 3, 512, 768, generator=g) - 0.5).cuda()
         for scale in HIGH_LADDER:
-            K, _, bpr, _ = model_at(scale).compress_packed(probe, SEED, irec.BeamSearchCoder(kl_per_partition=3., n_beams=10, extra_samples=1.,
+            K, _, bpr, _ = model_at(scale, args.model).compress_packed(probe, SEED, irec.BeamSearchCoder(kl_per_partition=3., n_beams=10, extra_samples=1.,
                                                                                             block_size=BLOCK))
-            search.append({"head_weight_scale": scale, "K_level_1": [int(K[:, bpr[0]:].min()), int(np.median(K[:, bpr[0]:])), int(K[:, bpr[0]:].max())]})
+            K_1 = K[:, sum(bpr[:-1]):]                                 # (level 1: the last residual block of the file)
+            search.append({"head_weight_scale": scale, "K_level_1": [int(K_1.min()), int(np.median(K_1)), int(K_1.max())]})
             print(json.dumps(search[-1]), flush=True)
-            if K[:, bpr[0]:].max() >= 100:
+            if K_1.max() >= 100:
                 args.high_scale = scale
                 break
         if args.high_scale is None:
             raise SystemExit("no scale of HIGH_LADDER gave a level-1 block 100 partitions: pass --high-scale")
     out_dir = tempfile.mkdtemp(prefix="irec_lossy_")
     for setting, scale in (("low_K", args.scale), ("high_K", args.high_scale)):
-        m = model_at(scale)
+        m = model_at(scale, args.model)
         sampler = irec.BeamSearchCoder(kl_per_partition=3., n_beams=10, extra_samples=1., block_size=BLOCK)
         S = m._max_index(sampler)
-        for name, n, h, w in SHAPES:
+        for name, n, h, w in shapes:
             if args.only and args.only != name:
                 continue
             g = torch.Generator().manual_seed(11)
@@ -139,9 +150,9 @@ def main():
                 assert open(paths["packed_host"][0], "rb").read() == open(paths["list"][0], "rb").read(), name
             assert all(open(a, "rb").read() == open(b, "rb").read() for a, b in zip(paths["packed_host"], paths["packed_device"])), name
             max_K = max(int(K.max()), 1)
-            first_rows = np.concatenate([[0], np.cumsum(bpr)])
-            row = {"setting": setting, "head_weight_scale": scale, "shape": name, "n_images": n, "height": h, "width": w, "blocks_per_res": bpr,
-                   "K_level_2": [int(K[:, :first_rows[1]].min()), int(K[:, :first_rows[1]].max())],
+            first_rows = [0, sum(bpr[:-1])]                                  # (level 1 is the last residual block of the file; one level: all of it)
+            row = {"model": type(m).__name__, "setting": setting, "head_weight_scale": scale, "shape": name, "n_images": n, "height": h, "width": w, "blocks_per_res": bpr,
+                   "K_level_2": [int(K[:, :first_rows[1]].min()), int(K[:, :first_rows[1]].max())] if args.model == 2 else None,
                    "K_level_1": [int(K[:, first_rows[1]:].min()), int(K[:, first_rows[1]:].max())], "K_level_1_median": int(np.median(K[:, first_rows[1]:])),
                    "indices_per_image": int(K.sum()) // n, "file_bytes_per_image": sum(os.path.getsize(p) for p in paths["packed_host"]) // n,
                    "reps": args.reps, "unit": "ms per batch: [median, min, max]"}
